@@ -9,9 +9,18 @@ MuJoCo's composite documentation describes it (fix rows + neighbour equalities, 
 U(300,1400) (BASELINE.json configs[2]; with N > 1 each rank draws from its own stiffness bin, configs[3]), following the
 reference's 200-step squeeze schedule (create_dataset.py:41-60) from a fresh reset, state resident in HBM.
 
-Timed region: --steps S a multiple of 200 = S/200 whole episodes (resets included).  Any other S: one episode is run from
-reset and S of its 200 steps, spread evenly over it, are timed one by one (sync + timer around each) -- an estimate of the
-episode average, not of an episode prefix (the first 40 steps have no contacts and cost a third of the average).
+Timed region: exactly --steps S steps.  S = 200 q + r: q whole episodes from reset, timed as one interval (resets included); then,
+if r > 0, one more episode is run from reset and r of its 200 steps, spread evenly over it, are timed one by one (sync + timer
+around each) -- an estimate of the episode average, not of an episode prefix (the first 40 steps have no contacts and cost a third
+of the average).  `ms_per_step` = the timed seconds / S.
+
+A plain run (`--gpus N --steps S --warmup W`) sets up, warms up, times the S steps and prints the line: `metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`.  `--full` adds everything else the benchmark measures, each in runs of its
+own after the headline pass: the same timed region again with HIP events around every kernel chain (kernel durations, the
+roofline block), the fix-rows-only model variant and the CPU oracle baseline (`--no-event-pass`, `--no-fix-variant`,
+`--no-cpu-baseline` leave one of them out).  `--dump-outputs DIR` writes what the headline pass computed (the sensor rows and flags
+of its last timed step, a seeded sample of envs of the episode block) as DIR/<name>.npy; with the same arguments every run has the
+same inputs.
 
 `python bench.py --gpus N` without a launcher starts its own N ranks (N child processes of a parent that never touches a GPU);
 started by `torch.distributed.run` it runs as a rank.  Either way the ranks share nothing but a common start and their timings, which
@@ -149,26 +158,31 @@ class Runner:
         profile=False: the headline pass -- nothing but the path itself inside the timed interval.  profile=True: the same region again
         with HIP events on the launch stream around every sg_step call's kernel chain and around every solver-kernel launch (7 per
         call): the event records sit in the stream between the kernels, so that pass yields the kernel durations (roofline), not `value`
-        (ADVICE r02)."""
+        (ADVICE r02).  steps = q T + r: q whole episodes as one interval, then r stratified steps of one more episode (module
+        docstring).  Afterwards self.last_t is the episode index of the last timed step and self.last_flags its flags."""
         torch, T, b = self.torch, self.T, self.batch
         b.profile_enable(False)
         b.profile_read(reset=True)
         b.profile_read_solver(reset=True)
-        if steps % T == 0:
+        whole, rest = divmod(steps, T)
+        dt, parts = 0.0, []
+        if whole:
             barrier()
             b.profile_enable(profile)
             t0 = time.perf_counter()
-            for t in range(steps):
+            for t in range(whole * T):
                 self.step(t)
                 if after_episode is not None and (t + 1) % T == 0:
                     after_episode(self)
             barrier()
-            dt = time.perf_counter() - t0
-            desc = "%d whole episode(s) from reset (resets included)" % (steps // T)
-        else:
-            pick = set(stratified_steps(steps, T))
+            dt += time.perf_counter() - t0
+            b.profile_enable(False)
+            self.last_t, self.last_flags = T - 1, self.flags.clone()
+            parts.append("%d whole episode(s) from reset (resets included)" % whole)
+        if rest:
+            pick = set(stratified_steps(rest, T))
+            last = max(pick)
             barrier()
-            dt = 0.0
             for t in range(T):
                 if t in pick:
                     device_sync()
@@ -178,12 +192,15 @@ class Runner:
                     device_sync()
                     dt += time.perf_counter() - t0
                     b.profile_enable(False)
+                    if t == last:
+                        self.last_t, self.last_flags = t, self.flags.clone()
                 else:
                     self.step(t)
             barrier()
-            desc = ("stratified over the episode: %d of the 200 env steps of one episode from reset, evenly spaced (steps %s), "
-                    "each timed on its own between device syncs; the other steps run untimed" % (len(pick), ",".join(map(str, sorted(pick)))))
-            steps = len(pick)
+            parts.append("stratified over the episode: %d of the 200 env steps of one episode from reset, evenly spaced (steps %s), "
+                         "each timed on its own between device syncs; the other steps run untimed" % (len(pick), ",".join(map(str, sorted(pick)))))
+            assert whole * T + len(pick) == steps
+        desc = "; then ".join(parts)
         kernel_ms, launches = b.profile_read(reset=True)
         self.solver_ms, self.solver_launches = b.profile_read_solver(reset=True)
         b.profile_enable(False)
@@ -197,6 +214,17 @@ class Runner:
             return dt, 0.0, 0, desc, nsteps, dt
         dtp, kernel_ms, launches, _, _ = self.timed(steps, barrier, None, profile=True)
         return dt, kernel_ms, launches, desc, nsteps, dtp
+
+    def outputs(self, max_episode_envs=1024):
+        """what the last timed pass handed its caller, as float64 host arrays: the sensor rows [n, nsd] and the flags [n] of its last
+        timed step, and the episode block [m, 200, nsd] (the episode that pass ended with, from reset: what the dataset path stores)
+        for m envs drawn without replacement by a fixed seed, m <= max_episode_envs and <= ~40 MB"""
+        n, T = self.n, self.T
+        m = min(n, max_episode_envs, max(1, int(40e6 // (T * self.nsd * 8))))
+        envs = np.arange(n) if m == n else np.sort(np.random.RandomState(0).choice(n, m, replace=False))
+        return {"sensors": self.out[:, self.last_t].double().cpu().numpy(),
+                "flags": self.last_flags.double().cpu().numpy(),
+                "episode_sensors": self.out[self.torch.as_tensor(envs, device=self.out.device)].double().cpu().numpy()}
 
 
 def _positive_or_none(v):
@@ -213,11 +241,17 @@ def main():
     ap.add_argument("--scene", default="softbox", help="softbox (default: MuJoCo's documented composite) | softbox_fix | softball | softcylinder ...")
     ap.add_argument("--tendon-damper", default=None, choices=["explicit", "implicit"],
                     help="integration of the composite volume tendon's damper (DESIGN.md D5); default: explicit (MuJoCo's Euler) for softbox, implicit for the ball / cylinder scenes, which do not run otherwise")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fix-variant", action="store_true", help="skip the labelled secondary measurement on the fix-rows-only model")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline pass, also measure what it does not need: the HIP-event pass (kernel durations, roofline), the "
+                         "fix-rows-only model variant and the CPU oracle baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline pass computed as DIR/<name>.npy (float64): sensors and flags of its last timed step, "
+                         "episode_sensors (a seeded sample of envs of the episode block), regressor_loss with --with-regressor; rank 0 only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-fix-variant", action="store_true", help="with --full: skip the labelled secondary measurement on the fix-rows-only model")
     ap.add_argument("--with-regressor", action="store_true", help="BASELINE configs[4]: ConvNet forward + one Adam step on every finished [n,200,12] block, inside the timed region (needs --steps a multiple of 200)")
     ap.add_argument("--no-event-pass", action="store_true",
-                    help="profiler runs (scripts/profile_round.sh): skip the second, HIP-event-instrumented pass over the timed region, so that the "
+                    help="with --full, for profiler runs (scripts/profile_round.sh): skip the second, HIP-event-instrumented pass over the timed region, so that the "
                          "trace holds exactly one reset + the timed steps; the line then carries no kernel durations")
     ap.add_argument("--dist-backend", default="store", choices=["store", "nccl", "gloo"],
                     help="what carries the barriers and the max-over-ranks time of an N > 1 run: store (default) = a TCP key-value store, no collective "
@@ -231,6 +265,8 @@ def main():
         raise SystemExit(ranks.spawn_ranks(args.gpus))   # the parent: starts N copies of this command line as ranks, touches no GPU
     if world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.with_regressor and args.steps % 200 != 0:
         raise SystemExit("--with-regressor needs --steps as a multiple of 200 (whole episodes)")
 
@@ -297,7 +333,20 @@ def main():
         del wnet, wx
     barrier()
     R.flags_or.zero_()
-    dt, kernel_ms, launches, desc, nsteps, dt_prof = R.measure(args.steps, barrier, after_episode, not args.no_event_pass)
+    dt, _, _, desc, nsteps = R.timed(args.steps, barrier, after_episode, profile=False)
+    if args.dump_outputs and rank == 0:
+        outs = R.outputs()
+        if reg is not None:
+            outs["regressor_loss"] = np.array([float(x) for x in reg["loss"]])
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    event_pass = args.full and not args.no_event_pass
+    if event_pass:   # --full: the same timed region once more with the HIP events on, for the kernel durations
+        dt_prof, kernel_ms, launches, _, _ = R.timed(args.steps, barrier, None, profile=True)
+    else:
+        dt_prof, kernel_ms, launches = dt, 0.0, 0
+        R.solver_ms, R.solver_launches = 0.0, 0
     if group is not None:  # every rank's time through the store; the job's time is the slowest rank's
         per_rank_dt = group.gather("dt", dt)
         dt = max(per_rank_dt)
@@ -323,7 +372,7 @@ def main():
         res = {
             "metric": "env steps/sec (whole node) at batch=4096",
             "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / nsteps * 1e3, "ms_per_step_with_hip_events": dt_prof / nsteps * 1e3,
+            "ms_per_step": dt / nsteps * 1e3,
             "ms_per_step_per_rank": [d / nsteps * 1e3 for d in per_rank_dt], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
             "config": {"workload": "configs[%d]: %d envs/GPU, %s scene (nv=%d), stiffness ~ U(300,1400)%s, reference 200-step squeeze "
@@ -332,21 +381,25 @@ def main():
                                        " split in per-rank bins" if world > 1 else "", model.neq, "on" if nb_on else "off") + ("; volume tendon damper integrated %sly" % damper) + (
                                        "; + ConvNet regressor: channel stats, noise augmentation, forward and one Adam step on every finished [n,200,12] block, on device, inside the timed region" if args.with_regressor else ""),
                        "envs_per_gpu": n, "substeps_per_step": R.sim_step, "physics_substeps_per_s": value * R.sim_step,
-                       "envs_flagged_bad": nbad, "launches_timed": launches, "steps_timed": nsteps, "timed_region": desc,
+                       "envs_flagged_bad": nbad, "steps_timed": nsteps, "timed_region": desc,
                        "tree_workgroups_per_cu": _positive_or_none(R.batch.tree_workgroups_per_cu() if hasattr(R.batch, "tree_workgroups_per_cu") else 0),
                        "rank_sync": {"store": "TCP key-value store (barriers + per-rank times), no collective library", "nccl": "torch.distributed on RCCL",
                                      "gloo": "torch.distributed on gloo"}[args.dist_backend] if world > 1 else None},
-            "roofline": {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                         "traffic": None, "traffic_source": None, "traffic_measured_in_this_run": False,
-                         "kernel": {"rows": "sg_chain_kernel + sg_phase_kernel + sg_pgs_rows_kernel chain of one sg_step call (rows pipeline; dominant: sg_pgs_rows_kernel)", "split": "sg_chain_kernel + sg_phase_kernel + sg_pgs_kernel chain of one sg_step call (split pipeline)",
-                                    "tree": "sg_tree_kernel: one launch per sg_step call, one env per wavefront (tree pipeline)"}.get(pipe, "sg_step_kernel"),
-                         "avg_kernel_ms": kernel_ms,
-                         "algorithmic_bytes_per_env_step": abytes,
-                         "note": "one 'launch' = the kernel chain of one sg_step call (7 substeps), HIP events on the launch stream over the timed steps only "
-                                 "(a second pass over the same timed region: `value` is measured without the events in the stream); "
-                                 "the path is instruction-issue-bound (serial Gauss-Seidel per finger), not HBM-bound; traffic is mostly contact blocks "
-                                 "re-read from L2/Infinity Cache by each sweep (DESIGN.md 4.3)"},
+            "full": bool(args.full),
         }
+        if args.full:   # what the headline does not need: the event pass's kernel durations and the roofline built on them
+            res["ms_per_step_with_hip_events"] = dt_prof / nsteps * 1e3
+            res["config"]["launches_timed"] = launches
+            res["roofline"] = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                               "traffic": None, "traffic_source": None, "traffic_measured_in_this_run": False,
+                               "kernel": {"rows": "sg_chain_kernel + sg_phase_kernel + sg_pgs_rows_kernel chain of one sg_step call (rows pipeline; dominant: sg_pgs_rows_kernel)", "split": "sg_chain_kernel + sg_phase_kernel + sg_pgs_kernel chain of one sg_step call (split pipeline)",
+                                          "tree": "sg_tree_kernel: one launch per sg_step call, one env per wavefront (tree pipeline)"}.get(pipe, "sg_step_kernel"),
+                               "avg_kernel_ms": kernel_ms,
+                               "algorithmic_bytes_per_env_step": abytes,
+                               "note": "one 'launch' = the kernel chain of one sg_step call (7 substeps), HIP events on the launch stream over the timed steps only "
+                                       "(a second pass over the same timed region: `value` is measured without the events in the stream); "
+                                       "the path is instruction-issue-bound (serial Gauss-Seidel per finger), not HBM-bound; traffic is mostly contact blocks "
+                                       "re-read from L2/Infinity Cache by each sweep (DESIGN.md 4.3)"}
         if R.solver_launches:
             # the dominant kernel on its own: its average launch (HIP events around every launch of it in the timed steps; the committed
             # rocprofv3 --stats summary's AverageNs for the same kernel agrees) against the algorithmic bytes of one substep of one call
@@ -361,7 +414,7 @@ def main():
         # Episode-average counters of this very workload from committed rocprofv3 PMC passes (profiles/<tag>_<scene>_*.json).  They
         # describe the whole 200-step episode, which is what both kinds of timed region measure or estimate; they are attached
         # only for the workload they were collected on.
-        attach = n == 4096 and pipe in ("rows", "tree") and not args.with_regressor
+        attach = args.full and n == 4096 and pipe in ("rows", "tree") and not args.with_regressor
         tp = os.path.join(ROOT, "profiles", "%s_%s_hbm_traffic.json" % (PROFILE_TAG, args.scene))
         if attach and os.path.exists(tp):
             res["roofline"]["traffic"] = json.load(open(tp))["per_sg_step_call_bytes"]
@@ -386,7 +439,7 @@ def main():
                           ("the tree kernel runs one env per wavefront, %s workgroups per CU (one wavefront each: %s of a CU's four SIMDs busy), a wavefront alone on its SIMD "
                            "issues one instruction per ~7 cycles: ~%.2f is its ceiling at this occupancy" % (wg, wg, 0.57 * min(wg or 4, 4) / 4.0)) if pipe == "tree" else
                           "the PGS kernel runs one wavefront per SIMD (1024 at 4096 envs: 4 envs per wavefront) and a wavefront alone on its SIMD issues one instruction per ~7-8 cycles, so ~0.5 is this design's ceiling for it")}
-        if world == 1 and nb_on and not args.no_fix_variant and not args.with_regressor and args.scene.endswith(("softbox", "softball", "softcylinder")):
+        if args.full and world == 1 and nb_on and not args.no_fix_variant and not args.with_regressor and args.scene.endswith(("softbox", "softball", "softcylinder")):
             # labelled secondary: the same workload on the fix-rows-only model (composite_neighbors=False)
             del R
             torch.cuda.empty_cache()
@@ -398,7 +451,7 @@ def main():
             res["config"]["fix_only_variant"] = {"value": n * ns2 / dt2, "unit": "env-steps/s", "avg_kernel_ms": km2, "equality_rows": R2.model.neq,
                                                  "note": "same workload on models/%s_fix.sgmodel (composite without its neighbour equalities) -- NOT the headline" % args.scene}
             del R2
-        if not args.no_cpu_baseline and world == 1:  # reported at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported at N = 1 only
             cores = usable_cores()
             envs = 8 * cores  # 8 full episodes per core: about 10-20 s of wall time
             ks = np.random.RandomState(0).uniform(300, 1400, n)

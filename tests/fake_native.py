@@ -14,12 +14,15 @@ class FakeModel:
 class FakeBatch:
     """records every physics call; sensordata = running substep count (like the stub simulator of the fixture)"""
     log = []
+    batches = 0        # batches created and profile_enable(True) calls: counted beside `log` (whose order the harness tests read)
+    profile_on = 0
 
     def __init__(self, nmodel, n_envs, device=0):
         self.n, self.nmodel, self.device = n_envs, nmodel, torch.device("cpu")
         self.ctrl = np.zeros(2)
         self.nsub = 0
         self.k = None
+        FakeBatch.batches += 1
 
     def set_stiffness(self, k, jids, tids):
         self.k = np.array(k, copy=True)
@@ -52,7 +55,7 @@ class FakeBatch:
         return dict(ncon=torch.zeros(self.n, dtype=torch.int32))
 
     def profile_enable(self, on=True):
-        pass
+        FakeBatch.profile_on += bool(on)
 
     def profile_read(self, reset=True):
         return 0.0, 0

@@ -4,6 +4,8 @@ Nothing in the product knows about this file; the ranks a script starts re-run t
 so come through here again.
 
 usage: python tests/run_with_fake_native.py <script.py | -m module> [args ...]"""
+import atexit
+import json
 import os
 import runpy
 import sys
@@ -22,6 +24,24 @@ torch.cuda.synchronize = lambda *a, **k: None
 torch.cuda.device_count = lambda: 8
 torch.cuda.set_device = lambda *a, **k: None
 print("run_with_fake_native: FAKE native batch (plumbing test, not a measurement)", file=sys.stderr)
+
+# the work this process did, as one stderr line at exit (what a test reads to see that a pass did or did not run): fake batches
+# created, resets, substeps, profile_enable(True) calls, and step_many calls of the CPU oracle
+from oracle import oracle as _oracle  # noqa: E402
+_calls = {"oracle_step_many": 0}
+_step_many = _oracle.step_many
+
+
+def _counted_step_many(*a, **k):
+    _calls["oracle_step_many"] += 1
+    return _step_many(*a, **k)
+
+
+_oracle.step_many = _counted_step_many
+B = fake_native.FakeBatch
+atexit.register(lambda: print("run_with_fake_native: work " + json.dumps(dict(
+    batches=B.batches, resets=sum(1 for e in B.log if e[0] == "reset"), substeps=sum(1 for e in B.log if e[0] == "substep"),
+    profile_on=B.profile_on, **_calls)), file=sys.stderr, flush=True))
 
 if sys.argv[1] == "-m":
     sys.argv = [sys.argv[2]] + sys.argv[3:]

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import softgrip_amd as sg
-from helpers import ROOT, oracle_sim
+from helpers import ROOT, model_path, oracle_sim
 from softgrip_amd.create_dataset import episode_schedule
 from softgrip_amd.mjcf import quat_mul, quat_to_mat
 
@@ -101,16 +101,20 @@ def test_torque_free_tumbling_conserves_angular_momentum(brick):
     assert np.abs(s1.qvel[3:6] - [0.2, 3.0, 0.1]).max() > 0.3          # the unstable axis is leaving
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="needs the reference's MJCF files (build container only)")
 def test_reference_free_ball_scene_on_the_oracle():
     """soft_experiments_softball.xml as the reference ships it: the ball's composite on a free body (8 gripper dofs + 6 + 218 sliders).
     Sizes, then the whole squeeze schedule on the oracle, no warning: everything stays finite, the quaternion normalised; the kernels
-    refuse the model with a reason."""
-    m = sg.compile_mjcf(REF, composite_neighbors=False)
+    refuse the model with a reason.  The scene is its committed blobs (models/freeball_fix.sgmodel, models/freeball.sgmodel, which
+    scripts/compile_models.py compiles from that file); where the MJCF file is at hand, a fresh compile must equal them byte for byte."""
+    m = sg.load_model(model_path("freeball_fix"))
+    if os.path.exists(REF):
+        for name, nb in (("freeball_fix", False), ("freeball", True)):
+            with open(model_path(name), "rb") as f:
+                assert f.read() == sg.compile_mjcf(REF, composite_neighbors=nb).to_blob(), name
     assert (m.nq, m.nv, m.njnt, m.neq) == (233, 232, 227, 219)
     j = int(np.flatnonzero(m.jnt_type == 0)[0])
     assert m.jnt_dofadr[j] == 8 and m.jnt_qposadr[j] == 8 and m.body_geomnum[m.jnt_bodyid[j]] == 1     # the free body carries OBJGcenter
-    assert sg.compile_mjcf(REF).neq == 651
+    assert sg.load_model(model_path("freeball")).neq == 651
     m.opt_implicit_tendon_damping = 1                      # D5 (DESIGN.md 2), as every ball scene
     s = oracle_sim(m)
     elem_joints = list(range(9, 227))                      # joint ids of the 218 sliders (the free joint is joint 8)

@@ -321,12 +321,11 @@ def test_free_object_squeezed_by_the_own_gripper(tmp_path):
     np.testing.assert_allclose(e.qpos, s.qpos, atol=1e-7)
 
 
-@pytest.mark.skipif(not __import__("os").path.exists("/root/reference/data/gripper/soft_experiments_softball.xml"), reason="needs the reference's MJCF files (build container only)")
 def test_reference_free_ball_scene_free_running():
     """soft_experiments_softball.xml as the reference ships it (8 gripper dofs + 6 + 218 sliders, the shell inside the fingers at the
-    start, D5 damper): the whole squeeze episode free-running against the oracle -- sensors 1e-7, contact / row / sweep counts exact"""
-    m = sg.compile_mjcf("/root/reference/data/gripper/soft_experiments_softball.xml", composite_neighbors=False)
-    m.opt_implicit_tendon_damping = 1
+    start, D5 damper): the whole squeeze episode free-running against the oracle -- sensors 1e-7, contact / row / sweep counts exact.
+    The scene is its committed blob, models/freeball_fix.sgmodel (tests/test_freejoint.py holds it against a fresh compile)."""
+    m = sg.load_model(model_path("freeball_fix"), "implicit")
     jids = list(range(9, 227))
     s = oracle_sim(m)
     s.jnt_stiffness[jids] = 700.0
