@@ -153,6 +153,27 @@ int sg_solver_envs_per_wavefront(const sg_batch* b);
  * 0 for a batch that does not run the tree pipeline; negative: an error code. */
 int sg_tree_workgroups_per_cu(const sg_batch* b);
 
+/* ---- pose read-out: replaces reading data.xpos / data.xquat / data.geom_xpos / data.geom_xmat after mj_kinematics.
+ * mj_kinematics for the listed envs: [n_ids][nbody][3|4] body xpos / xquat, [n_ids][ngeom][3|9] geom_xpos / geom_xmat (row-major).
+ * env_ids: HOST pointer to n_ids env indices (NULL: all envs in order, n_ids == n_envs); outputs: device pointers, any may be NULL.
+ * Reads the batch's current qpos and changes nothing in it; an env whose qpos holds a NaN or inf gets NaN poses. */
+int sg_get_poses(sg_batch* b, const int32_t* env_ids, int n_ids, double* xpos, double* xquat, double* geom_xpos, double* geom_xmat, void* stream);
+int sg_model_nbody(const sg_model* m);
+int sg_model_ngeom(const sg_model* m);
+
+/* ---- headless renderer (no window, no GL; replaces MjViewer's picture, manenv.py:114-116).  Every geom is drawn as its own primitive
+ * (plane, sphere, capsule, box; a model with another geom type fails with SG_ERR_MODEL) with a fixed shading.
+ * cam[7]: MuJoCo's free camera = lookat xyz, distance, azimuth, elevation, fovy (degrees, vertical); forward =
+ * (cos el cos az, cos el sin az, sin el), eye = lookat - distance forward, up = +z.
+ * sg_model_default_camera: a camera that frames the scene at qpos0 (host only, needs no device).
+ * sg_render: ray-cast images of the listed envs, device pointers, any may be NULL:
+ *   rgba  [n_ids][height][width][4] uint8, depth [n_ids][height][width] f32 (distance along the optical axis, +inf = background),
+ *   segid [n_ids][height][width] int32 (geom id, -1 = background).  Reads the batch's current state; changes nothing in it.
+ *   An env whose qpos holds a NaN or inf renders as background.  env_ids as in sg_get_poses. */
+int sg_model_default_camera(const sg_model* m, double cam[7]);
+int sg_render(sg_batch* b, const double* cam, const int32_t* env_ids, int n_ids, int width, int height,
+              uint8_t* rgba, float* depth, int32_t* segid, void* stream);
+
 /* kernel timing hook for bench.py: average device time (ms) of one sg_step/sg_reset call's kernels over the
  * calls since the last call with reset != 0, measured with HIP events on the launch
  * stream.  Synchronises the host. */

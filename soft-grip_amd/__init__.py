@@ -7,6 +7,6 @@ from .mjcf import Model, compile_mjcf, load_model  # noqa: F401
 def __getattr__(name):  # lazy: importing the package must not need torch or the HIP library
     if name in ("ManEnv", "Env", "SimulationError"):
         return getattr(importlib.import_module(__name__ + ".manenv"), name)
-    if name in ("native", "manenv", "create_dataset", "build_native"):
+    if name in ("native", "manenv", "create_dataset", "build_native", "pngio"):
         return importlib.import_module(__name__ + "." + name)
     raise AttributeError(name)

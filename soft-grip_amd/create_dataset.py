@@ -93,12 +93,15 @@ def log_into_file(args):
     env_spec["device"] = int(os.environ.get("LOCAL_RANK", getattr(args, "device", 0)))
     if getattr(args, "force_device", -1) >= 0:
         env_spec["device"] = args.force_device
+    name = args.data_name if world == 1 else "%s.rank%d" % (args.data_name, rank)
+    if getattr(args, "render_dir", None):   # frames of the squeeze steps (the reference's env.render(), :49); no part of the data
+        env_spec.update(render_dir=os.path.join(args.render_dir, name), render_envs=range(max(0, min(args.render_envs, getattr(args, "n_envs", 1)))),
+                        render_size=tuple(args.render_size), render_every=args.render_every)
     env = ManEnv(**env_spec)
     n = env.n_envs
     lo, hi = stiffness_bin(rank, world) if world > 1 else (300, 1400)   # stiffness sweep sharded by bin (BASELINE.json configs[3])
 
     os.makedirs(args.data_folder, exist_ok=True)
-    name = args.data_name if world == 1 else "%s.rank%d" % (args.data_name, rank)
     path = os.path.join(args.data_folder, "{}.pickle".format(name))
     data, stiffness = list(), list()
     n_skipped = 0
@@ -121,6 +124,7 @@ def log_into_file(args):
             env.rng.set_state(d["rng_state"])
             n_skipped += 1
         else:
+            env.render_prefix = "s%d_b%d" % (current_env, ep % num_batches)
             current_stiffness = np.array(env.reset(lo, hi), dtype=np.float64).reshape(-1).copy()   # the label is the pre-episode draw (reference :35,65)
 
             samples = list()
@@ -239,6 +243,11 @@ def make_parser():
     parser.add_argument('--max-capacity-resets', type=float, default=0.001,
                         help="fail when more than this share of the simulated episodes hit the kernels' contact capacity (an env MuJoCo, with the "
                              "reference's nconmax = 500, would have kept: resetting it is a selection the reference does not make)")
+    parser.add_argument('--render-dir', type=str, default=None,
+                        help="write PNG frames of the squeeze steps to DIR/<data-name>[.rankR]/s<scene>_b<batch>_e<env>_t<step>.png (headless renderer)")
+    parser.add_argument('--render-envs', type=int, default=1, help="with --render-dir: frames of the first N envs of a batch")
+    parser.add_argument('--render-size', type=int, nargs=2, default=[320, 240], metavar=("W", "H"), help="with --render-dir: frame size")
+    parser.add_argument('--render-every', type=int, default=1, help="with --render-dir: a frame every K-th squeeze step")
     parser.add_argument('--force-device', type=int, default=-1, help="testing only: put every rank on this GPU")
     return parser
 

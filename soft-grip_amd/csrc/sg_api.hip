@@ -9,6 +9,7 @@
 #include "sg_mjcf.h"
 #include "sg_tree.h"
 #include "sg_work.h"
+#include "sg_kin.hip"   // pose read-out and renderer kernels (compiled in this translation unit)
 #ifdef SG_LEGACY_PIPELINES
 #include "sg_kernels_args.h"
 #endif
@@ -55,6 +56,7 @@ struct sg_model {
   bool has_tree;    // the tree pipeline (sg_tree.h) runs it
   SgPlan tplan;     // the tree pipeline's plan: same elements / equalities / statics, chains in `tree`, flat box references
   SgTreeDev tree;
+  SgKinHost kin;    // kinematics table of sg_get_poses / sg_render (sg_kin.hip)
 };
 
 struct sg_batch {
@@ -93,6 +95,13 @@ struct sg_batch {
   std::vector<hipEvent_t> ev_pool;  // events handed back by sg_profile_read*: a profiled call creates none once the pool is warm
   double prof_pgs_ms;
   long long prof_pgs_n;
+  // pose read-out / renderer (sg_kin.hip), allocated at first use
+  double* kin_d;
+  int* kin_i;
+  int* kin_ids;        // the listed env ids on the device
+  int kin_ids_cap;
+  float* rrecs;        // [n_ids][ngeom][SGR_REC] fp32 geom records of the last sg_render
+  size_t rrecs_cap;    // floats
 };
 
 static int begin_event_pair(sg_batch* b, std::vector<std::pair<hipEvent_t, hipEvent_t>>& list, hipStream_t s);
@@ -199,6 +208,7 @@ int sg_model_create(const void* blob, size_t nbytes, sg_model** out) {
     return fail(SG_ERR_MODEL, "sg_model_create: " + err + " (two-finger kernels); " + terr + " (tree pipeline)");
   }
   if (!m->has_fast) m->plan = m->tplan;
+  sgk_build(blob, nbytes, m->has_fast ? m->plan : m->tplan, m->has_tree ? &m->tree : nullptr, m->has_fast, &m->kin);
   m->rounds = (m->plan.h.nelem + 63) / 64;
   if (m->rounds > 4) {
     delete m;
@@ -249,7 +259,7 @@ void sg_batch_destroy(sg_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
   tree_free(b);
-  void* ptrs[] = {b->dtab, b->dcpos, b->dgpairs, b->dnbtab, b->dsched, b->dH, b->delem, b->qpos, b->qvel, b->warm, b->act, b->ctrl, b->kenv, b->ctrl_row, b->kmask_jnt, b->kmask_ten,
+  void* ptrs[] = {b->kin_d, b->kin_i, b->kin_ids, b->rrecs, b->dtab, b->dcpos, b->dgpairs, b->dnbtab, b->dsched, b->dH, b->delem, b->qpos, b->qvel, b->warm, b->act, b->ctrl, b->kenv, b->ctrl_row, b->kmask_jnt, b->kmask_ten,
                   b->flags, b->touch, b->ncon, b->nefc, b->iters};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -271,6 +281,7 @@ int sg_batch_create(const sg_model* m, int n_envs, int device, sg_batch** out) {
   b->m = m; b->n = n_envs; b->device = device; b->lds_attr_set = false; b->prof = false; b->prof_ms = 0; b->prof_n = 0; b->prof_pgs_ms = 0; b->prof_pgs_n = 0;
   b->dnbtab = nullptr; b->dsched = nullptr; b->dgpairs = nullptr; b->dtab = nullptr; b->dcpos = nullptr; b->epw_override = 0;
   b->dTH = nullptr; b->dT = nullptr; b->dtelem = b->tcws = nullptr; b->dtpairs = nullptr; b->touch_words = nullptr; b->tree_ready = false; b->tree_attr_set = false; b->dtsched = nullptr; b->dtnbtab = nullptr;
+  b->kin_d = nullptr; b->kin_i = nullptr; b->kin_ids = nullptr; b->kin_ids_cap = 0; b->rrecs = nullptr; b->rrecs_cap = 0;
   b->dH = nullptr; b->delem = b->qpos = b->qvel = b->warm = b->act = b->ctrl = b->kenv = b->ctrl_row = nullptr;
   b->kmask_jnt = b->kmask_ten = b->flags = b->touch = b->ncon = b->nefc = b->iters = nullptr;
   const SgPlanHeader& H = m->plan.h;
@@ -746,4 +757,109 @@ int sg_profile_read(sg_batch* b, int reset, double* avg_ms, long long* launches)
   return SG_OK;
 }
 
+// ---- pose read-out and renderer (sg_kin.hip) ----
+int sg_model_nbody(const sg_model* m) { return m ? m->kin.o.nbody : 0; }
+int sg_model_ngeom(const sg_model* m) { return m ? m->kin.o.ngeom : 0; }
+
+int sg_model_default_camera(const sg_model* m, double* cam) {
+  if (!m || !cam) return fail(SG_ERR_INVALID, "sg_model_default_camera: null argument");
+  if (!m->kin.ok) return fail(SG_ERR_MODEL, "sg_model_default_camera: " + m->kin.err);
+  sgk_default_camera(m->kin, cam);
+  return SG_OK;
+}
+
+// the kinematics table on the batch's device and the listed env ids (host array, range-checked here) in a device buffer
+static int kin_prepare(sg_batch* b, const char* fn, const int32_t* env_ids, int n_ids, hipStream_t s, const int** dids) {
+  const SgKinHost& K = b->m->kin;
+  if (!K.ok) return fail(SG_ERR_MODEL, std::string(fn) + ": " + K.err);
+  if (n_ids <= 0) return fail(SG_ERR_INVALID, std::string(fn) + ": n_ids must be positive");
+  if (!env_ids && n_ids != b->n) return fail(SG_ERR_INVALID, std::string(fn) + ": env_ids == NULL needs n_ids == the batch's env count");
+  if (env_ids)
+    for (int i = 0; i < n_ids; i++)
+      if (env_ids[i] < 0 || env_ids[i] >= b->n)
+        return fail(SG_ERR_INVALID, std::string(fn) + ": env id " + std::to_string(env_ids[i]) + " out of range [0, " + std::to_string(b->n) + ")");
+  HIPCHK(hipSetDevice(b->device));
+  if (!b->kin_d) {
+    double* d = nullptr;
+    int* ip = nullptr;
+    if (hipMalloc((void**)&d, sizeof(double) * K.dbl.size()) != hipSuccess) return fail(SG_ERR_NOMEM, std::string(fn) + ": hipMalloc");
+    if (hipMalloc((void**)&ip, sizeof(int) * K.ints.size()) != hipSuccess) { (void)hipFree(d); return fail(SG_ERR_NOMEM, std::string(fn) + ": hipMalloc"); }
+    b->kin_d = d; b->kin_i = ip;
+    HIPCHK(hipMemcpy(b->kin_d, K.dbl.data(), sizeof(double) * K.dbl.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b->kin_i, K.ints.data(), sizeof(int) * K.ints.size(), hipMemcpyHostToDevice));
+  }
+  *dids = nullptr;
+  if (env_ids) {
+    if (n_ids > b->kin_ids_cap) {
+      HIPCHK(hipStreamSynchronize(s));   // (the old buffer may still be read by an earlier launch on this stream)
+      if (b->kin_ids) (void)hipFree(b->kin_ids);
+      b->kin_ids = nullptr; b->kin_ids_cap = 0;
+      if (hipMalloc((void**)&b->kin_ids, sizeof(int) * n_ids) != hipSuccess) return fail(SG_ERR_NOMEM, std::string(fn) + ": hipMalloc");
+      b->kin_ids_cap = n_ids;
+    }
+    HIPCHK(hipMemcpyAsync(b->kin_ids, env_ids, sizeof(int) * n_ids, hipMemcpyHostToDevice, s));
+    *dids = b->kin_ids;
+  }
+  return SG_OK;
+}
+
+static int launch_kin(sg_batch* b, const int* dids, int n_ids, double* xpos, double* xquat, double* gxpos, double* gxmat, float* recs,
+                      const double* eye, hipStream_t s) {
+  const SgKinHost& K = b->m->kin;
+  SgKinArgs a;
+  a.D = b->kin_d; a.I = b->kin_i; a.o = K.o; a.qpos = b->qpos; a.env_ids = dids; a.n_ids = n_ids;
+  a.xpos = xpos; a.xquat = xquat; a.gxpos = gxpos; a.gxmat = gxmat; a.recs = recs;
+  for (int c = 0; c < 3; c++) a.eye[c] = eye ? eye[c] : 0.0;
+  hipLaunchKernelGGL(sg_kin_kernel, dim3(n_ids), dim3(64), sizeof(double) * 7 * K.o.nbody, s, a);
+  HIPCHK(hipGetLastError());
+  return SG_OK;
+}
+
+int sg_get_poses(sg_batch* b, const int32_t* env_ids, int n_ids, double* xpos, double* xquat, double* geom_xpos, double* geom_xmat, void* stream) {
+  if (!b) return fail(SG_ERR_INVALID, "sg_get_poses: null batch");
+  hipStream_t s = (hipStream_t)stream;
+  const int* dids = nullptr;
+  if (int rc = kin_prepare(b, "sg_get_poses", env_ids, n_ids, s, &dids)) return rc;
+  if (!xpos && !xquat && !geom_xpos && !geom_xmat) return SG_OK;
+  return launch_kin(b, dids, n_ids, xpos, xquat, geom_xpos, geom_xmat, nullptr, nullptr, s);
+}
+
+int sg_render(sg_batch* b, const double* cam, const int32_t* env_ids, int n_ids, int width, int height, uint8_t* rgba, float* depth, int32_t* segid,
+              void* stream) {
+  if (!b || !cam) return fail(SG_ERR_INVALID, "sg_render: null batch or camera");
+  if (width <= 0 || height <= 0 || width > 16384 || height > 16384) return fail(SG_ERR_INVALID, "sg_render: image size out of range (1 .. 16384)");
+  for (int c = 0; c < 7; c++)
+    if (!std::isfinite(cam[c])) return fail(SG_ERR_INVALID, "sg_render: camera values must be finite");
+  if (!(cam[3] > 0) || !(cam[6] > 0 && cam[6] < 180)) return fail(SG_ERR_INVALID, "sg_render: camera distance must be > 0 and fovy in (0, 180)");
+  const SgKinHost& K = b->m->kin;
+  if (K.ok && K.bad_type >= 0)
+    return fail(SG_ERR_MODEL, "sg_render: geom type " + std::to_string(K.bad_type) + " has no ray intersection (plane, sphere, capsule and box only)");
+  if (K.ok && K.o.ngeom > SGR_MAXGEOM) return fail(SG_ERR_MODEL, "sg_render: more than " + std::to_string(SGR_MAXGEOM) + " geoms");
+  hipStream_t s = (hipStream_t)stream;
+  const int* dids = nullptr;
+  if (int rc = kin_prepare(b, "sg_render", env_ids, n_ids, s, &dids)) return rc;
+  const size_t need = (size_t)n_ids * K.o.ngeom * SGR_REC;
+  if (need > b->rrecs_cap) {
+    HIPCHK(hipStreamSynchronize(s));
+    if (b->rrecs) (void)hipFree(b->rrecs);
+    b->rrecs = nullptr; b->rrecs_cap = 0;
+    if (hipMalloc((void**)&b->rrecs, sizeof(float) * need) != hipSuccess) return fail(SG_ERR_NOMEM, "sg_render: hipMalloc (geom records)");
+    b->rrecs_cap = need;
+  }
+  SgRenderArgs a;
+  double eye[3];
+  sgr_camera(cam, width, height, eye, &a.cam);
+  if (int rc = launch_kin(b, dids, n_ids, nullptr, nullptr, nullptr, nullptr, b->rrecs, eye, s)) return rc;
+  a.recs = b->rrecs; a.ngeom = K.o.ngeom; a.n_ids = n_ids;
+  a.tiles_x = (width + SGR_TILE - 1) / SGR_TILE;
+  a.ntiles = a.tiles_x * ((height + SGR_TILE - 1) / SGR_TILE);
+  a.rgba = rgba; a.depth = depth; a.segid = segid;
+  if (!rgba && !depth && !segid) return SG_OK;
+  if ((long long)a.ntiles * n_ids > 0x7fffffffll) return fail(SG_ERR_INVALID, "sg_render: too many tiles x envs for one launch");
+  hipLaunchKernelGGL(sg_render_kernel, dim3((unsigned)(a.ntiles * n_ids)), dim3(256), 0, s, a);
+  HIPCHK(hipGetLastError());
+  return SG_OK;
+}
+
 }  // extern "C"
+

@@ -7,6 +7,8 @@ reference returns (``step() -> (ndarray(12,), bool)``, ``reset() -> float``); wi
 ``n_envs > 1`` the same calls act on all envs in lockstep and return device tensors
 (``[n,12]`` float64, ``[n]`` bool) / an ``ndarray[n]`` of stiffnesses.
 """
+import os
+
 import numpy as np
 
 from . import native
@@ -40,13 +42,18 @@ class ManEnv(Env):
     n_actuated = 2    # close_hand / loose_hand drive ctrl[0 .. n_actuated - 1] (`for i in range(2)`, reference manenv.py:93-101); 4 for the four-finger gripper
 
     def __init__(self, sim_start, sim_step, env_paths, is_vis=True, n_envs=1, device=0, contact_flag_mode="intent", check_scene=True,
-                 tendon_damper="auto", joint_ids=None, tendon_ids=None, finger_names=None, n_actuated=None, max_cached_scenes=4):
+                 tendon_damper="auto", joint_ids=None, tendon_ids=None, finger_names=None, n_actuated=None, max_cached_scenes=4,
+                 render_dir=None, render_envs=(0,), render_size=(320, 240), render_every=1, camera=None):
         """``joint_ids`` / ``tendon_ids``: which model entries ``set_new_stiffness`` writes; default = the reference's class attributes
         (joints 11..63 and tendon 0: manenv.py:12-13), to be overridden for a scene with another layout (e.g. a smaller shell).
         ``tendon_damper``: how the damper of the composite's volume tendon is integrated (mjcf.load_model).
         "explicit" = MuJoCo's Euler step as restated; "implicit" = the rank-one implicit treatment; "auto" (default) = explicit,
         and a scene that fails the load-time check under it (the reference's soft ball / cylinder) is reloaded with "implicit",
-        with a printed notice.  ``self.tendon_damper`` holds what the loaded scene runs with."""
+        with a printed notice.  ``self.tendon_damper`` holds what the loaded scene runs with.
+        ``render_dir``: when set, every ``render_every``-th call of ``render()`` writes PNGs of the envs ``render_envs`` at
+        ``render_size`` (width, height) seen through ``camera`` (7 numbers of MuJoCo's free camera; None = the scene's default camera)
+        as <render_dir>/<render_prefix>_e<env>_t<call>.png; ``render_prefix`` defaults to s<scene>_b<episode>.  Without it
+        ``render()`` stays the no-op it is (``is_vis`` starts nothing)."""
         super().__init__(sim_start, sim_step)
         assert len(env_paths) > 0
         assert contact_flag_mode in ("intent", "reference")
@@ -72,6 +79,10 @@ class ManEnv(Env):
         self.n_capacity_resets = 0   # ... of which: envs that ran out of the KERNELS' contact capacity (SG_FLAG_CONTACTFULL: 64 per finger stream /
                                      # 128 per env) -- not a MuJoCo warning: the reference's nconmax is 500 (soft_grip_two_fingers.xml:8) and MuJoCo
                                      # would have carried on.  Counted apart so that a dataset job can refuse to paper over it (create_dataset)
+        self.render_dir, self.render_envs, self.render_every, self.camera = render_dir, [int(e) for e in render_envs], int(render_every), camera
+        self.render_size = (int(render_size[0]), int(render_size[1]))
+        self.render_prefix = None     # file-name prefix of the frames (None: s<scene>_b<episode>)
+        self.current_scene, self._episode, self._render_calls = 0, -1, 0
         self._scenes = {}     # path -> the loaded scene (model, batch, buffers, the damper it runs with): load_env() of a scene seen before
                               # neither compiles, allocates nor dry-runs again (the reference's loop switches scene after EVERY episode)
         self._load(env_paths[0])
@@ -190,6 +201,7 @@ class ManEnv(Env):
     def load_env(self, num):
         if num < len(self.env_paths):
             self._load(self.env_paths[num])
+            self.current_scene = num
         else:
             print("Wrong number,")
 
@@ -209,6 +221,8 @@ class ManEnv(Env):
         """reference manenv.py:55-63; the stiffness range is an extension (the reference always draws from U(300, 1400)):
         a rank of a sharded run passes its stiffness bin"""
         current_stiffness = self.set_new_stiffness(range_min, range_max)
+        self._episode += 1
+        self._render_calls = 0
         self.env.reset(max(self.sim_start, 0), sens=self._sens, flags=self._flags, touch=self._touch)
         self._ctrl[:] = 0  # mj_resetData clears ctrl
         bad = (self._flags != 0)
@@ -302,7 +316,25 @@ class ManEnv(Env):
         return self.env
 
     def render(self):
-        pass  # viewer is out of scope
+        """reference manenv.py:114-116 drives MuJoCo's viewer; here a no-op unless the env was made with ``render_dir``: then every
+        ``render_every``-th call since the last reset() writes PNG frames of ``render_envs`` (headless renderer, sg_render)"""
+        if self.render_dir is None or not self.render_envs:
+            return
+        t = self._render_calls
+        self._render_calls += 1
+        if t % max(1, self.render_every):
+            return
+        from .pngio import write_png
+        rgb = self.render_frames(envs=self.render_envs, camera=self.camera, size=self.render_size, depth=False, seg=False)["rgb"].cpu().numpy()
+        os.makedirs(self.render_dir, exist_ok=True)
+        prefix = self.render_prefix or "s%d_b%d" % (self.current_scene, max(self._episode, 0))
+        for k, e in enumerate(self.render_envs):
+            write_png(os.path.join(self.render_dir, "%s_e%d_t%d.png" % (prefix, e, t)), rgb[k])
+
+    def render_frames(self, envs=None, camera=None, size=(320, 240), rgb=True, depth=True, seg=True):
+        """images of the listed envs (None: all) on the current state: NativeBatch.render's dict of device tensors (rgba / rgb
+        [k, H, W, 4|3] uint8, depth [k, H, W] float32, seg [k, H, W] int32); size = (width, height)"""
+        return self.env.render(camera=camera, env_ids=envs, width=int(size[0]), height=int(size[1]), rgb=rgb, depth=depth, seg=seg)
 
     # ---- fused episode: the create_dataset.py schedule without a host round trip per step ----
     def rollout(self, schedule, out=None, reset=True):

@@ -22,6 +22,7 @@ SYMBOLS = [
     "sg_set_state", "sg_get_solver_stats", "sg_set_pipeline", "sg_profile_enable", "sg_profile_read", "sg_profile_read_solver",
     "sg_model_compile", "sg_mjcf_compile", "sg_blob_free", "sg_set_solver_envs_per_wavefront", "sg_solver_envs_per_wavefront",
     "sg_get_touch_words", "sg_model_nboxes", "sg_model_nv", "sg_model_njnt", "sg_tree_workgroups_per_cu",
+    "sg_get_poses", "sg_model_nbody", "sg_model_ngeom", "sg_model_default_camera", "sg_render",
 ]
 SG_COMPILE_NO_NEIGHBORS, SG_COMPILE_IMPLICIT_TENDON_DAMPER = 1, 2
 
@@ -79,6 +80,11 @@ def load_library(path):
     L.sg_set_solver_envs_per_wavefront.argtypes = [vp, C.c_int]
     L.sg_solver_envs_per_wavefront.argtypes = [vp]
     L.sg_tree_workgroups_per_cu.argtypes = [vp]
+    L.sg_model_nbody.argtypes = [vp]
+    L.sg_model_ngeom.argtypes = [vp]
+    L.sg_model_default_camera.argtypes = [vp, C.POINTER(C.c_double)]
+    L.sg_get_poses.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, dp, dp, dp, vp]
+    L.sg_render.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.sg_profile_enable.argtypes = [vp, C.c_int]
     L.sg_profile_read.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
     L.sg_profile_read_solver.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
@@ -118,6 +124,14 @@ class NativeModel:
         self.ntendon = L.sg_model_ntendon(self.ptr)
         self.nelem = L.sg_model_nelem(self.ptr)
         self.nboxes = L.sg_model_nboxes(self.ptr)     # moving finger boxes = bits of the contact read-out
+        self.nbody = L.sg_model_nbody(self.ptr)
+        self.ngeom = L.sg_model_ngeom(self.ptr)
+
+    def default_camera(self):
+        """MuJoCo free camera [lookat xyz, distance, azimuth, elevation, fovy] that frames the scene at qpos0 (sg_model_default_camera)"""
+        cam = (C.c_double * 7)()
+        check(self.L.sg_model_default_camera(self.ptr, cam), self.L)
+        return np.array(cam[:], dtype=np.float64)
 
     def __del__(self):
         if getattr(self, "ptr", None) and getattr(self, "L", None) is not None:
@@ -202,6 +216,44 @@ class NativeBatch:
         t = self.torch
         out = t.empty(self.n, nwords, dtype=t.int32, device=self.device)
         self._check(self.L.sg_get_touch_words(self.ptr, _ptr(out), nwords, self._stream()))
+        return out
+
+    def _ids(self, env_ids):
+        if env_ids is None:
+            return None, self.n
+        ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+        return ids, len(ids)
+
+    def poses(self, env_ids=None):
+        """mj_kinematics of the listed envs (None: all) on the current state (sg_get_poses): dict of float64 device tensors
+        xpos [k, nbody, 3], xquat [k, nbody, 4], geom_xpos [k, ngeom, 3], geom_xmat [k, ngeom, 9]"""
+        t, m = self.torch, self.nmodel
+        ids, k = self._ids(env_ids)
+        kw = dict(dtype=t.float64, device=self.device)
+        out = dict(xpos=t.empty(k, m.nbody, 3, **kw), xquat=t.empty(k, m.nbody, 4, **kw), geom_xpos=t.empty(k, m.ngeom, 3, **kw),
+                   geom_xmat=t.empty(k, m.ngeom, 9, **kw))
+        self._check(self.L.sg_get_poses(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, _ptr(out["xpos"]),
+                                        _ptr(out["xquat"]), _ptr(out["geom_xpos"]), _ptr(out["geom_xmat"]), self._stream()))
+        return out
+
+    def render(self, camera=None, env_ids=None, width=320, height=240, rgb=True, depth=True, seg=True):
+        """ray-cast images of the listed envs (None: all) on the current state (sg_render): dict of device tensors rgba [k, H, W, 4]
+        uint8 with its view rgb [..., :3], depth [k, H, W] float32 (+inf = background), seg [k, H, W] int32 (geom id, -1 = background).
+        camera: 7 numbers (lookat xyz, distance, azimuth, elevation, fovy); None = the model's default camera."""
+        t = self.torch
+        cam = np.ascontiguousarray(self.nmodel.default_camera() if camera is None else camera, dtype=np.float64).reshape(7)
+        ids, k = self._ids(env_ids)
+        out = {}
+        if rgb:
+            out["rgba"] = t.empty(k, height, width, 4, dtype=t.uint8, device=self.device)
+            out["rgb"] = out["rgba"][..., :3]
+        if depth:
+            out["depth"] = t.empty(k, height, width, dtype=t.float32, device=self.device)
+        if seg:
+            out["seg"] = t.empty(k, height, width, dtype=t.int32, device=self.device)
+        self._check(self.L.sg_render(self.ptr, cam.ctypes.data_as(C.POINTER(C.c_double)),
+                                     None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, int(width), int(height),
+                                     _ptr(out.get("rgba")), _ptr(out.get("depth")), _ptr(out.get("seg")), self._stream()))
         return out
 
     def set_solver_envs_per_wavefront(self, epw):

@@ -1,0 +1,268 @@
+"""Independent NumPy (fp64) ray caster for the headless renderer (soft-grip_amd/csrc/sg_render.h, sg_render): same camera, primitives,
+rules and shading as the header documents, written from those rules and not from the header's code.  Poses come from
+mjcf.Model.kinematics() plus each geom's local pose; categories from the model's structure alone."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+from softgrip_amd.mjcf import quat_to_mat
+
+PLANE, SPHERE, CAPSULE, BOX = 0, 2, 3, 6
+GROUND, STATIC, FINGER, ELEM, CENTER = 0, 1, 2, 3, 4
+ALBEDO = {ELEM: (0.8, 0.2, 0.1), CENTER: (0.8, 0.2, 0.1), FINGER: (0.3, 0.45, 0.8), STATIC: (0.6, 0.6, 0.6)}
+CHECKER = ((0.2, 0.3, 0.4), (0.1, 0.15, 0.2))
+BACKGROUND = (0.3, 0.5, 0.7)
+
+
+def geom_poses(model, qpos):
+    """world geom_xpos [ngeom, 3] and geom_xmat [ngeom, 3, 3] at qpos"""
+    kin = model.kinematics(np.asarray(qpos, dtype=np.float64))
+    b = np.asarray(model.geom_bodyid)
+    xm = kin["xmat"][b]
+    gx = kin["xpos"][b] + np.einsum("gij,gj->gi", xm, model.geom_pos)
+    gm = np.einsum("gij,gjk->gik", xm, np.array([quat_to_mat(q) for q in model.geom_quat]))
+    return gx, gm
+
+
+def categories(model):
+    """ground: planes; object: capsules on slider bodies and spheres (the composite's centre); finger: boxes on moving bodies;
+    static: the rest"""
+    cat = np.full(model.ngeom, STATIC, dtype=np.int32)
+    jt = np.asarray(model.jnt_type)
+    for g in range(model.ngeom):
+        b, t = model.geom_bodyid[g], model.geom_type[g]
+        moving = model.body_weldid[b] != 0
+        js = jt[model.body_jntadr[b]:model.body_jntadr[b] + model.body_jntnum[b]]
+        if t == PLANE:
+            cat[g] = GROUND
+        elif t == CAPSULE and len(js) == 1 and js[0] == 2:
+            cat[g] = ELEM
+        elif t == SPHERE:
+            cat[g] = CENTER
+        elif t == BOX and moving:
+            cat[g] = FINGER
+    return cat
+
+
+def default_camera(model):
+    """lookat = centre of the bounding box of the non-plane geoms' centres at qpos0, distance = 2 x (its half-diagonal + the largest
+    geom_rbound of those geoms), azimuth 90, elevation -30, fovy 45"""
+    gx, _ = geom_poses(model, model.qpos0)
+    keep = np.asarray(model.geom_type) != PLANE
+    lo, hi = gx[keep].min(0), gx[keep].max(0)
+    half = 0.5 * np.linalg.norm(hi - lo)
+    return np.array([*(0.5 * (lo + hi)), 2.0 * (half + np.max(np.asarray(model.geom_rbound)[keep])), 90.0, -30.0, 45.0])
+
+
+def camera_rays(cam, width, height):
+    """eye [3], forward [3], unit ray directions [H, W, 3] through the pixel centres (row 0 = top)"""
+    az, el = np.radians(cam[4]), np.radians(cam[5])
+    f = np.array([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)])
+    r = np.cross(f, [0.0, 0.0, 1.0])
+    r = r / np.linalg.norm(r)
+    u = np.cross(r, f)
+    eye = np.asarray(cam[:3], dtype=np.float64) - cam[3] * f
+    th = np.tan(np.radians(cam[6]) / 2)
+    i, j = np.meshgrid(np.arange(width) + 0.5, np.arange(height) + 0.5)
+    uu = (2 * i / width - 1) * th * width / height
+    vv = (1 - 2 * j / height) * th
+    d = f + uu[..., None] * r + vv[..., None] * u
+    return eye, f, d / np.linalg.norm(d, axis=-1, keepdims=True)
+
+
+def _sphere_t(o, dl, r):
+    """smallest positive root of |o + t dl| = r for unit dl; o [3] or [N, 3]"""
+    tl = -np.sum(o * dl, -1)
+    q = o + tl[:, None] * dl
+    h2 = r * r - np.sum(q * q, -1)
+    with np.errstate(invalid="ignore"):
+        t = tl - np.sqrt(h2)
+    return np.where((h2 >= 0) & (t > 0), t, np.inf)
+
+
+def _intersect(t_, size, o, dl):
+    """distance [N] (inf: miss) and local normal [N, 3] of rays o + t dl (local frame) with one primitive"""
+    n = len(dl)
+    nl = np.zeros((n, 3))
+    nl[:, 2] = 1
+    t = np.full(n, np.inf)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if t_ == PLANE:
+            tt = -o[2] / dl[:, 2]
+            ok = (dl[:, 2] < 0) & (o[2] > 0)
+            x, y = o[0] + tt * dl[:, 0], o[1] + tt * dl[:, 1]
+            if size[0] > 0 and size[1] > 0:
+                ok &= (np.abs(x) <= size[0]) & (np.abs(y) <= size[1])
+            t = np.where(ok, tt, np.inf)
+        elif t_ == SPHERE:
+            t = _sphere_t(np.broadcast_to(o, dl.shape), dl, size[0])
+            nl = (o + t[:, None] * dl) / size[0]
+        elif t_ == CAPSULE:
+            r, hl = size[0], size[1]
+            a = dl[:, 0] ** 2 + dl[:, 1] ** 2
+            tl = -(o[0] * dl[:, 0] + o[1] * dl[:, 1]) / a
+            q0, q1 = o[0] + tl * dl[:, 0], o[1] + tl * dl[:, 1]
+            h2 = r * r - (q0 * q0 + q1 * q1)
+            ts = tl - np.sqrt(h2 / a)
+            side = (a > 1e-12) & (h2 >= 0) & (ts > 0) & (np.abs(o[2] + ts * dl[:, 2]) <= hl)
+            t = np.where(side, ts, np.inf)
+            for zc in (hl, -hl):
+                t = np.minimum(t, _sphere_t(np.broadcast_to(o - [0, 0, zc], dl.shape), dl, r))
+            h = o + t[:, None] * dl
+            nl = h - np.stack([np.zeros(n), np.zeros(n), np.clip(h[:, 2], -hl, hl)], -1)
+            nl = nl / r
+        elif t_ == BOX:
+            t1 = (-size - o) / dl
+            t2 = (size - o) / dl
+            lo, hi = np.minimum(t1, t2), np.maximum(t1, t2)
+            par = dl == 0                               # parallel to a slab: inside it or a miss
+            inslab = np.abs(o) <= size
+            lo = np.where(par, -np.inf, lo)
+            hi = np.where(par, np.inf, hi)
+            miss = np.any(par & ~inslab, -1)
+            tn, tf = lo.max(-1), hi.min(-1)
+            ax = lo.argmax(-1)
+            ok = ~miss & (tn <= tf) & (tn > 0)
+            t = np.where(ok, tn, np.inf)
+            nl = np.zeros((n, 3))
+            nl[np.arange(n), ax] = -np.sign(dl[np.arange(n), ax])
+    return t, nl
+
+
+def u8(c):
+    return np.clip(np.floor(np.asarray(c) * 255.0 + 0.5), 0, 255).astype(np.uint8)
+
+
+def render(gx, gm, types, sizes, cats, cam, width, height):
+    """-> depth [H, W] float64 (inf background), seg [H, W] int32 (-1), rgb [H, W, 3] uint8, and the pixels whose ground hit lies
+    within 1e-4 m of a checker line [H, W] bool (the texture's own silhouettes: fp32 may land on the other square there)"""
+    eye, f, d = camera_rays(cam, width, height)
+    d = d.reshape(-1, 3)
+    ng = len(types)
+    T = np.full((ng, len(d)), np.inf)
+    NL = np.zeros((ng, len(d), 3))
+    for g in range(ng):
+        R = gm[g]
+        o = R.T @ (eye - gx[g])
+        dl = d @ R
+        T[g], NL[g] = _intersect(int(types[g]), np.asarray(sizes[g], dtype=np.float64), o, dl)
+    seg = np.argmin(T, 0)                         # (first = smallest id among equal distances)
+    t = T[seg, np.arange(len(d))]
+    hitm = np.isfinite(t)
+    seg = np.where(hitm, seg, -1)
+    depth = np.where(hitm, t * (d @ f), np.inf)
+    rgb = np.tile(u8(BACKGROUND), (len(d), 1))
+    edge = np.zeros(len(d), bool)
+    for p in np.flatnonzero(hitm):
+        g = seg[p]
+        R = gm[g]
+        n = R @ NL[g, p]
+        c = cats[g]
+        if c == GROUND:
+            hl = R.T @ (eye + t[p] * d[p] - gx[g])
+            alb = CHECKER[int(np.floor(hl[0] / 0.5) + np.floor(hl[1] / 0.5)) % 2]
+            fr = np.abs(hl[:2] / 0.5 - np.round(hl[:2] / 0.5)) * 0.5
+            edge[p] = fr.min() < 1e-4
+        else:
+            alb = ALBEDO.get(int(c), ALBEDO[STATIC])
+        shade = 0.25 + 0.45 * max(0.0, -(n @ f)) + 0.30 * max(0.0, n[2])
+        rgb[p] = u8(np.array(alb) * shade)
+    return depth.reshape(height, width), seg.reshape(height, width).astype(np.int32), rgb.reshape(height, width, 3), edge.reshape(height, width)
+
+
+def render_model(model, qpos, cam, width, height, cats=None):
+    gx, gm = geom_poses(model, qpos)
+    return render(gx, gm, model.geom_type, model.geom_size, categories(model) if cats is None else cats, cam, width, height)
+
+
+def silhouette(seg):
+    """pixels whose 4-neighbourhood (in the reference's segmentation) holds another id"""
+    s = np.zeros(seg.shape, bool)
+    s[1:] |= seg[1:] != seg[:-1]
+    s[:-1] |= seg[:-1] != seg[1:]
+    s[:, 1:] |= seg[:, 1:] != seg[:, :-1]
+    s[:, :-1] |= seg[:, :-1] != seg[:, 1:]
+    return s
+
+
+def compare(ref, got, what=""):
+    """the parity criteria: depth within 1e-4 m off the silhouettes, at most 0.5 % differing ids and only on silhouettes, rgb within
+    2 levels where the ids agree (off the checker lines of the ground)"""
+    rd, rs, rc = ref[:3]
+    gd, gs, gc = got
+    sil = silhouette(rs)
+    diff = rs != gs
+    assert diff.mean() <= 0.005, "%s: %d of %d pixels differ in segid" % (what, diff.sum(), diff.size)
+    assert not (diff & ~sil).any(), "%s: segid differs off the silhouettes at %s" % (what, np.argwhere(diff & ~sil)[:5].tolist())
+    inner = ~sil & ~diff
+    both = inner & np.isfinite(rd)
+    assert (np.isfinite(gd) == np.isfinite(rd))[inner].all(), what
+    if both.any():
+        err = np.abs(gd.astype(np.float64) - rd)[both].max()
+        assert err <= 1e-4, "%s: depth off by %.3g m" % (what, err)
+    same = ~diff & ~(ref[3] if len(ref) > 3 else False)
+    cerr = np.abs(gc.astype(np.int32) - rc.astype(np.int32)).max(-1)
+    assert cerr[same].max(initial=0) <= 2, "%s: rgb off by %d levels at %s" % (what, cerr[same].max(), np.argwhere(same & (cerr > 2))[:5].tolist())
+
+
+# ---- the g++ build of sg_render.h: every pixel through the header's camera, tile culling and trace, as the kernel does ----
+HOST_DRIVER = r"""
+#include <cstdio>
+#include <vector>
+#include "sg_render.h"
+extern "C" void render_host(const double* cam, int W, int H, int ng, const double* gx, const double* gm, const double* gs, const int* type,
+                            const int* cat, float* depth, int* seg, unsigned char* rgba) {
+  SgrCam c;
+  double eye[3];
+  sgr_camera(cam, W, H, eye, &c);
+  std::vector<float> recs((size_t)ng * SGR_REC);
+  for (int g = 0; g < ng; g++) sgr_make_record(gx + 3 * g, gm + 9 * g, gs + 3 * g, type[g], cat[g], eye, &recs[(size_t)SGR_REC * g]);
+  std::vector<unsigned short> list(ng);
+  for (int ty = 0; ty < (H + SGR_TILE - 1) / SGR_TILE; ty++)
+    for (int tx = 0; tx < (W + SGR_TILE - 1) / SGR_TILE; tx++) {
+      const int i0 = tx * SGR_TILE, j0 = ty * SGR_TILE, i1 = i0 + SGR_TILE - 1 < W - 1 ? i0 + SGR_TILE - 1 : W - 1, j1 = j0 + SGR_TILE - 1 < H - 1 ? j0 + SGR_TILE - 1 : H - 1;
+      float d0[3], d1[3], d2[3], d3[3], axis[3], cs, sn;
+      sgr_ray(c, i0, j0, d0); sgr_ray(c, i1, j0, d1); sgr_ray(c, i0, j1, d2); sgr_ray(c, i1, j1, d3);
+      sgr_tile_cone(d0, d1, d2, d3, axis, &cs, &sn);
+      int n = 0;
+      for (int g = 0; g < ng; g++)
+        if (sgr_cone_keep(&recs[(size_t)SGR_REC * g], axis, cs, sn)) list[n++] = (unsigned short)g;
+      for (int j = j0; j <= j1; j++)
+        for (int i = i0; i <= i1; i++) {
+          float d[3];
+          sgr_ray(c, i, j, d);
+          SgrHit h = sgr_trace(recs.data(), list.data(), n, c, d);
+          const size_t p = (size_t)j * W + i;
+          depth[p] = h.depth; seg[p] = h.geom;
+          for (int k = 0; k < 4; k++) rgba[4 * p + k] = h.rgba[k];
+        }
+    }
+}
+"""
+
+
+def build_host(tmpdir):
+    """compiles sg_render.h with g++ into tmpdir -> ctypes function render_host"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = os.path.join(tmpdir, "render_host.cpp")
+    so = os.path.join(tmpdir, "librender_host.so")
+    with open(src, "w") as f:
+        f.write(HOST_DRIVER)
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(root, "soft-grip_amd", "csrc"), "-o", so, src])
+    L = C.CDLL(so)
+    L.render_host.restype = None
+    return L.render_host
+
+
+def render_with(fn, gx, gm, types, sizes, cats, cam, width, height):
+    a = lambda x, dt: np.ascontiguousarray(x, dtype=dt)  # noqa: E731
+    gx, gm, gs = a(gx, np.float64), a(np.reshape(gm, (-1, 9)), np.float64), a(sizes, np.float64)
+    ty, ct, cm = a(types, np.int32), a(cats, np.int32), a(cam, np.float64)
+    depth = np.empty((height, width), np.float32)
+    seg = np.empty((height, width), np.int32)
+    rgba = np.empty((height, width, 4), np.uint8)
+    p = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
+    fn(p(cm), C.c_int(width), C.c_int(height), C.c_int(len(ty)), p(gx), p(gm), p(gs), p(ty), p(ct), p(depth), p(seg), p(rgba))
+    return depth, seg, rgba
