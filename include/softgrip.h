@@ -174,6 +174,27 @@ int sg_model_default_camera(const sg_model* m, double cam[7]);
 int sg_render(sg_batch* b, const double* cam, const int32_t* env_ids, int n_ids, int width, int height,
               uint8_t* rgba, float* depth, int32_t* segid, void* stream);
 
+/* ---- contact read-out: replaces the loop `for i in range(data.ncon): data.contact[i]` (manenv.py:65-85).
+ * mj_collision for the listed envs at the batch's CURRENT qpos -- what sim.forward(); sim.data.contact[:ncon] would hold: the oracle's
+ * candidate pairs, order, bounding tests, narrowphase and cap.  Geometry only (no forces, no solver parameters).  Device pointers, any
+ * may be NULL:
+ *   ncon  [n_ids] int32: the number of contacts mj_collision keeps for the env (at most the model's nconmax when positive, and 512); it
+ *         MAY EXCEED max_contacts; -1 for an env whose qpos holds a NaN or inf (or whose geom poses leave +-1e10);
+ *   geom  [n_ids][max_contacts][2] int32: geom1, geom2 in mj_collideGeoms' by-type order (plane < sphere < capsule < box);
+ *   dist  [n_ids][max_contacts], pos [n_ids][max_contacts][3], frame [n_ids][max_contacts][9] (normal geom1 -> geom2 in the first row,
+ *         completed as mju_makeFrame; the first tangent of a plane - capsule contact follows the capsule's axis).
+ * The arrays receive the first min(ncon, max_contacts) contacts in mj_collision's order; slots past that are NOT written (the call does
+ * not clear the buffers).  env_ids as in sg_get_poses.  Reads the batch and changes nothing in it; does not synchronise the host.
+ * After sg_step the batch's qpos is one Euler integration PAST the collision pass whose list produced touch_out, so this is the NEXT
+ * forward pass's list; directly after sg_reset(..., sim_start = 0, ...) or sg_set_state nothing lies between the two and the touch
+ * bits recomputed from this list equal sg_get_touch_words.
+ * SG_ERR_INVALID (checked before anything touches the device): NULL batch, n_ids <= 0, max_contacts <= 0 with a contact array given, an
+ * env id out of range.  sg_model_ncollision_pairs: the candidate geom pairs after the static filters (contype / conaffinity, weld group,
+ * parent - child), which the kernel's broadphase walks for every env. */
+int sg_get_contacts(sg_batch* b, const int32_t* env_ids, int n_ids, int max_contacts,
+                    int32_t* ncon, int32_t* geom, double* dist, double* pos, double* frame, void* stream);
+int sg_model_ncollision_pairs(const sg_model* m);
+
 /* kernel timing hook for bench.py: average device time (ms) of one sg_step/sg_reset call's kernels over the
  * calls since the last call with reset != 0, measured with HIP events on the launch
  * stream.  Synchronises the host. */

@@ -10,6 +10,7 @@
 #include "sg_tree.h"
 #include "sg_work.h"
 #include "sg_kin.hip"   // pose read-out and renderer kernels (compiled in this translation unit)
+#include "sg_contacts.hip"   // contact-list read-out kernel (compiled in this translation unit, after sg_kin.hip)
 #ifdef SG_LEGACY_PIPELINES
 #include "sg_kernels_args.h"
 #endif
@@ -57,6 +58,7 @@ struct sg_model {
   SgPlan tplan;     // the tree pipeline's plan: same elements / equalities / statics, chains in `tree`, flat box references
   SgTreeDev tree;
   SgKinHost kin;    // kinematics table of sg_get_poses / sg_render (sg_kin.hip)
+  SgConHost con;    // candidate pairs, margins and bounding radii of sg_get_contacts (sg_contacts.hip)
 };
 
 struct sg_batch {
@@ -102,6 +104,12 @@ struct sg_batch {
   int kin_ids_cap;
   float* rrecs;        // [n_ids][ngeom][SGR_REC] fp32 geom records of the last sg_render
   size_t rrecs_cap;    // floats
+  // contact read-out (sg_contacts.hip), allocated at first use
+  int* con_pairs;
+  double* con_gaux;
+  double* con_scratch;     // per-env pose blocks of a model whose poses do not fit LDS
+  size_t con_scratch_cap;  // doubles
+  bool con_attr_set;
 };
 
 static int begin_event_pair(sg_batch* b, std::vector<std::pair<hipEvent_t, hipEvent_t>>& list, hipStream_t s);
@@ -209,6 +217,7 @@ int sg_model_create(const void* blob, size_t nbytes, sg_model** out) {
   }
   if (!m->has_fast) m->plan = m->tplan;
   sgk_build(blob, nbytes, m->has_fast ? m->plan : m->tplan, m->has_tree ? &m->tree : nullptr, m->has_fast, &m->kin);
+  sgc_from_blob(blob, nbytes, m->kin, &m->con);
   m->rounds = (m->plan.h.nelem + 63) / 64;
   if (m->rounds > 4) {
     delete m;
@@ -259,7 +268,7 @@ void sg_batch_destroy(sg_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
   tree_free(b);
-  void* ptrs[] = {b->kin_d, b->kin_i, b->kin_ids, b->rrecs, b->dtab, b->dcpos, b->dgpairs, b->dnbtab, b->dsched, b->dH, b->delem, b->qpos, b->qvel, b->warm, b->act, b->ctrl, b->kenv, b->ctrl_row, b->kmask_jnt, b->kmask_ten,
+  void* ptrs[] = {b->con_pairs, b->con_gaux, b->con_scratch, b->kin_d, b->kin_i, b->kin_ids, b->rrecs, b->dtab, b->dcpos, b->dgpairs, b->dnbtab, b->dsched, b->dH, b->delem, b->qpos, b->qvel, b->warm, b->act, b->ctrl, b->kenv, b->ctrl_row, b->kmask_jnt, b->kmask_ten,
                   b->flags, b->touch, b->ncon, b->nefc, b->iters};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -282,6 +291,7 @@ int sg_batch_create(const sg_model* m, int n_envs, int device, sg_batch** out) {
   b->dnbtab = nullptr; b->dsched = nullptr; b->dgpairs = nullptr; b->dtab = nullptr; b->dcpos = nullptr; b->epw_override = 0;
   b->dTH = nullptr; b->dT = nullptr; b->dtelem = b->tcws = nullptr; b->dtpairs = nullptr; b->touch_words = nullptr; b->tree_ready = false; b->tree_attr_set = false; b->dtsched = nullptr; b->dtnbtab = nullptr;
   b->kin_d = nullptr; b->kin_i = nullptr; b->kin_ids = nullptr; b->kin_ids_cap = 0; b->rrecs = nullptr; b->rrecs_cap = 0;
+  b->con_pairs = nullptr; b->con_gaux = nullptr; b->con_scratch = nullptr; b->con_scratch_cap = 0; b->con_attr_set = false;
   b->dH = nullptr; b->delem = b->qpos = b->qvel = b->warm = b->act = b->ctrl = b->kenv = b->ctrl_row = nullptr;
   b->kmask_jnt = b->kmask_ten = b->flags = b->touch = b->ncon = b->nefc = b->iters = nullptr;
   const SgPlanHeader& H = m->plan.h;
@@ -861,5 +871,57 @@ int sg_render(sg_batch* b, const double* cam, const int32_t* env_ids, int n_ids,
   return SG_OK;
 }
 
-}  // extern "C"
+// ---- contact read-out (sg_contacts.hip) ----
+int sg_model_ncollision_pairs(const sg_model* m) {
+  if (!m) return 0;
+  if (!m->con.ok) return fail(SG_ERR_MODEL, "sg_model_ncollision_pairs: " + m->con.err);
+  return (int)(m->con.pairs.size() / 2);
+}
 
+int sg_get_contacts(sg_batch* b, const int32_t* env_ids, int n_ids, int max_contacts, int32_t* ncon, int32_t* geom, double* dist, double* pos,
+                    double* frame, void* stream) {
+  // (argument checks first, in an order that lets each be reached without a device)
+  if (n_ids <= 0) return fail(SG_ERR_INVALID, "sg_get_contacts: n_ids must be positive");
+  if (max_contacts <= 0 && (geom || dist || pos || frame)) return fail(SG_ERR_INVALID, "sg_get_contacts: max_contacts must be positive when a contact array is given");
+  if (!b) return fail(SG_ERR_INVALID, "sg_get_contacts: null batch");
+  const SgConHost& Cn = b->m->con;
+  const SgKinHost& K = b->m->kin;
+  if (K.ok && !Cn.ok) return fail(SG_ERR_MODEL, "sg_get_contacts: " + Cn.err);
+  hipStream_t s = (hipStream_t)stream;
+  const int* dids = nullptr;
+  if (int rc = kin_prepare(b, "sg_get_contacts", env_ids, n_ids, s, &dids)) return rc;
+  if (!ncon && !geom && !dist && !pos && !frame) return SG_OK;
+  if (!b->con_pairs) {
+    int* dp = nullptr;
+    double* dg = nullptr;
+    if (hipMalloc((void**)&dp, sizeof(int) * (Cn.pairs.size() + 2)) != hipSuccess) return fail(SG_ERR_NOMEM, "sg_get_contacts: hipMalloc");
+    if (hipMalloc((void**)&dg, sizeof(double) * (Cn.gaux.size() + 2)) != hipSuccess) { (void)hipFree(dp); return fail(SG_ERR_NOMEM, "sg_get_contacts: hipMalloc"); }
+    b->con_pairs = dp; b->con_gaux = dg;
+    HIPCHK(hipMemcpy(b->con_pairs, Cn.pairs.data(), sizeof(int) * Cn.pairs.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b->con_gaux, Cn.gaux.data(), sizeof(double) * Cn.gaux.size(), hipMemcpyHostToDevice));
+  }
+  const size_t npose = sgc_pose_doubles(K.o);
+  const size_t lds = sizeof(double) * (SGC_FIXED_DBL + npose);
+  const bool in_lds = lds <= 159 * 1024;   // (the kernel has 256 B of static LDS besides; the CU has 160 KB)
+  if (!in_lds && (size_t)n_ids * npose > b->con_scratch_cap) {
+    HIPCHK(hipStreamSynchronize(s));   // (the old block may still be in use by an earlier launch on this stream)
+    if (b->con_scratch) (void)hipFree(b->con_scratch);
+    b->con_scratch = nullptr; b->con_scratch_cap = 0;
+    if (hipMalloc((void**)&b->con_scratch, sizeof(double) * n_ids * npose) != hipSuccess) return fail(SG_ERR_NOMEM, "sg_get_contacts: hipMalloc (pose blocks)");
+    b->con_scratch_cap = (size_t)n_ids * npose;
+  }
+  if (in_lds && !b->con_attr_set) {   // per device, as the solver kernels' attribute; what this model's launches ask for (above 64 KB it must be granted)
+    HIPCHK(hipFuncSetAttribute((const void*)sg_contacts_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    b->con_attr_set = true;
+  }
+  SgConArgs a;
+  a.D = b->kin_d; a.I = b->kin_i; a.o = K.o; a.gaux = b->con_gaux; a.pairs = b->con_pairs; a.npair = (int)(Cn.pairs.size() / 2); a.cap = Cn.cap;
+  a.qpos = b->qpos; a.env_ids = dids; a.n_ids = n_ids; a.max_contacts = max_contacts;
+  a.ncon = ncon; a.geom = geom; a.dist = dist; a.pos = pos; a.frame = frame; a.scratch = in_lds ? nullptr : b->con_scratch;
+  if (in_lds) hipLaunchKernelGGL(sg_contacts_kernel<true>, dim3(n_ids), dim3(64), lds, s, a);
+  else hipLaunchKernelGGL(sg_contacts_kernel<false>, dim3(n_ids), dim3(64), sizeof(double) * SGC_FIXED_DBL, s, a);
+  HIPCHK(hipGetLastError());
+  return SG_OK;
+}
+
+}  // extern "C"

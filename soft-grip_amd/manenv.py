@@ -336,6 +336,16 @@ class ManEnv(Env):
         [k, H, W, 4|3] uint8, depth [k, H, W] float32, seg [k, H, W] int32); size = (width, height)"""
         return self.env.render(camera=camera, env_ids=envs, width=int(size[0]), height=int(size[1]), rgb=rgb, depth=depth, seg=seg)
 
+    def get_contacts(self, env_ids=None, max_contacts=256):
+        """the contact list of the listed envs (None: all) at the current state -- what `sim.forward(); sim.data.contact[:ncon]` holds
+        in the reference's read-out loop (manenv.py:65-85): NativeBatch.contacts' dict of device tensors (ncon [k], geom [k, C, 2],
+        dist [k, C], pos [k, C, 3], frame [k, C, 9]) plus ``geom_names``, the model's list, so that a caller can write the reference's
+        substring test itself: ``"OBJ" in geom_names[geom[e, i, 0]]``.  After step() the list is the NEXT forward pass's (qpos is one
+        integration past the collision pass behind the touch flags); after reset() with sim_start = 0 the two coincide."""
+        out = self.env.contacts(env_ids=env_ids, max_contacts=max_contacts)
+        out["geom_names"] = [n or "" for n in self.model.geom_names]
+        return out
+
     # ---- fused episode: the create_dataset.py schedule without a host round trip per step ----
     def rollout(self, schedule, out=None, reset=True):
         """Runs ``len(schedule)`` env steps; ``schedule[t]`` is the broadcast ctrl (or None = unchanged) applied

@@ -23,6 +23,7 @@ SYMBOLS = [
     "sg_model_compile", "sg_mjcf_compile", "sg_blob_free", "sg_set_solver_envs_per_wavefront", "sg_solver_envs_per_wavefront",
     "sg_get_touch_words", "sg_model_nboxes", "sg_model_nv", "sg_model_njnt", "sg_tree_workgroups_per_cu",
     "sg_get_poses", "sg_model_nbody", "sg_model_ngeom", "sg_model_default_camera", "sg_render",
+    "sg_get_contacts", "sg_model_ncollision_pairs",
 ]
 SG_COMPILE_NO_NEIGHBORS, SG_COMPILE_IMPLICIT_TENDON_DAMPER = 1, 2
 
@@ -85,6 +86,8 @@ def load_library(path):
     L.sg_model_default_camera.argtypes = [vp, C.POINTER(C.c_double)]
     L.sg_get_poses.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, dp, dp, dp, vp]
     L.sg_render.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.sg_get_contacts.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, ip, ip, dp, dp, dp, vp]
+    L.sg_model_ncollision_pairs.argtypes = [vp]
     L.sg_profile_enable.argtypes = [vp, C.c_int]
     L.sg_profile_read.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
     L.sg_profile_read_solver.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
@@ -126,6 +129,7 @@ class NativeModel:
         self.nboxes = L.sg_model_nboxes(self.ptr)     # moving finger boxes = bits of the contact read-out
         self.nbody = L.sg_model_nbody(self.ptr)
         self.ngeom = L.sg_model_ngeom(self.ptr)
+        self.ncollision_pairs = L.sg_model_ncollision_pairs(self.ptr)   # candidate geom pairs of the contact read-out
 
     def default_camera(self):
         """MuJoCo free camera [lookat xyz, distance, azimuth, elevation, fovy] that frames the scene at qpos0 (sg_model_default_camera)"""
@@ -235,6 +239,37 @@ class NativeBatch:
         self._check(self.L.sg_get_poses(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, _ptr(out["xpos"]),
                                         _ptr(out["xquat"]), _ptr(out["geom_xpos"]), _ptr(out["geom_xmat"]), self._stream()))
         return out
+
+    def contacts(self, env_ids=None, max_contacts=256):
+        """mj_collision of the listed envs (None: all) on the current state (sg_get_contacts): dict of device tensors ncon [k] int32
+        (the full count, may exceed max_contacts; -1: the env's qpos is not finite), geom [k, max_contacts, 2] int32, dist
+        [k, max_contacts], pos [k, max_contacts, 3], frame [k, max_contacts, 9] float64.  Rows hold the first min(ncon, max_contacts)
+        contacts in mj_collision's order; the slots past them are zero (the tensors start zeroed, the call writes nothing there)."""
+        t = self.torch
+        ids, k = self._ids(env_ids)
+        mc = int(max_contacts)
+        kw = dict(dtype=t.float64, device=self.device)
+        out = dict(ncon=t.zeros(k, dtype=t.int32, device=self.device), geom=t.zeros(k, mc, 2, dtype=t.int32, device=self.device),
+                   dist=t.zeros(k, mc, **kw), pos=t.zeros(k, mc, 3, **kw), frame=t.zeros(k, mc, 9, **kw))
+        self.contacts_into(out, env_ids)
+        return out
+
+    def contacts_into(self, out, env_ids=None):
+        """sg_get_contacts into caller-owned tensors: `out` maps any of ncon / geom / dist / pos / frame to contiguous device tensors of
+        the shapes contacts() returns (max_contacts is read off the contact arrays; slots past an env's count keep their contents)"""
+        t = self.torch
+        ids, k = self._ids(env_ids)
+        mc = 0
+        for name, tail, dt in (("ncon", (), t.int32), ("geom", (2,), t.int32), ("dist", (), t.float64), ("pos", (3,), t.float64), ("frame", (9,), t.float64)):
+            x = out.get(name)
+            if x is None:
+                continue
+            assert x.is_cuda and x.dtype == dt and x.is_contiguous() and x.shape[0] == k, name
+            if name != "ncon":
+                assert x.shape[2:] == tail and (mc == 0 or x.shape[1] == mc), name
+                mc = x.shape[1]
+        self._check(self.L.sg_get_contacts(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, mc, _ptr(out.get("ncon")),
+                                           _ptr(out.get("geom")), _ptr(out.get("dist")), _ptr(out.get("pos")), _ptr(out.get("frame")), self._stream()))
 
     def render(self, camera=None, env_ids=None, width=320, height=240, rgb=True, depth=True, seg=True):
         """ray-cast images of the listed envs (None: all) on the current state (sg_render): dict of device tensors rgba [k, H, W, 4]

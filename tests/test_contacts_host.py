@@ -1,0 +1,178 @@
+"""Contact read-out (sg_get_contacts) without a GPU: the g++ build of csrc/sg_contacts.h -- the pair table and the per-pair math the
+kernel runs -- against the oracle's forward(); contacts(), the new ABI entry points that need no device, and the kept assembly of the
+new kernel."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import contacts_ref as CR
+from helpers import JOINT_IDS, ROOT, model_path, oracle_sim, random_gripper_xml
+from test_render_host import perturbed
+
+import softgrip_amd as sg
+from softgrip_amd.create_dataset import episode_schedule
+
+# scene -> (tendon damper, joints and tendons that take the stiffness)
+COMMITTED = {"softbox": (None, JOINT_IDS, [0]), "softball": ("implicit", JOINT_IDS, [0]), "softcylinder": ("implicit", JOINT_IDS, [0]),
+             "fourfinger_softball_fix": ("implicit", list(range(65, 283)), [0]), "freeball_fix": ("implicit", list(range(9, 227)), [0])}
+DATA_XML = ["capbox", "capbox_slide", "boxbox", "mini_gripper"]
+NPAIRS = {"softbox": 1018, "softball": 1990, "softcylinder": 1756, "fourfinger_softball_fix": 17016}
+SCRATCH_BYTES = 320   # per lane, what DESIGN.md 8.1 states: the shared box - box routine indexes its 3 x 3 axis tables at run time
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    return CR.build_host(str(tmp_path_factory.mktemp("contacts_host")))
+
+
+def _check_states(host, m, sim, qs, what):
+    """the host build's list against the oracle's at every qpos of qs; -> (states, most contacts, pair-type set)"""
+    most, kinds, worst = 0, set(), 0.0
+    for i, q in enumerate(qs):
+        ref = CR.oracle_contacts(sim, q)
+        got = CR.host_contacts(host, m, q)
+        worst = max(worst, CR.compare(got, ref, "%s state %d" % (what, i)))
+        most = max(most, ref["ncon"])
+        kinds |= {(int(m.geom_type[a]), int(m.geom_type[b])) for a, b in ref["geom"]}
+    return len(qs), most, kinds, worst
+
+
+def _episode_states(m, sim, jids, tids, k, nsteps, nu_ctrl=-0.2):
+    """qpos of an oracle squeeze episode at the reset state and after every 10th env step (stops at the first simulation warning)"""
+    if jids:
+        sim.jnt_stiffness[jids] = k
+    if tids is not None and len(sim.tendon_stiffness):
+        sim.tendon_stiffness[tids] = k
+    sim.reset(); sim.forward(); sim.step()
+    qs = [sim.qpos.copy()]
+    for t, c in enumerate(episode_schedule()[:nsteps]):
+        if c is not None:
+            sim.ctrl[:] = c
+        if any(sim.step() for _ in range(7)):
+            break
+        if (t + 1) % 10 == 0:
+            qs.append(sim.qpos.copy())
+    return qs
+
+
+@pytest.mark.parametrize("scene", sorted(COMMITTED))
+def test_host_build_matches_oracle_on_committed_scenes(host, scene):
+    damper, jids, tids = COMMITTED[scene]
+    m = sg.load_model(model_path(scene), damper)
+    sim = oracle_sim(m)
+    qs = [np.array(m.qpos0, dtype=np.float64)] + [perturbed(m, s) for s in range(3)]
+    qs += _episode_states(m, sim, jids, tids, 850.0, 200)
+    n, most, kinds, worst = _check_states(host, m, sim, qs, scene)
+    assert n == 4 + 21, n            # (the committed scenes run their whole schedule without a warning)
+    assert most >= 10, most          # (the lists are not empty)
+    print("%s: %d states, up to %d contacts, pair types %s, max deviation %.2e" % (scene, n, most, sorted(kinds), worst))
+
+
+def _wide(model, seed):
+    """qpos0 with every slider moved by up to +-1 m and every hinge by up to +-0.5 rad: the small scenes' geoms start apart"""
+    rs = np.random.RandomState(seed)
+    q = np.array(model.qpos0, dtype=np.float64)
+    for j, t in enumerate(model.jnt_type):
+        a = model.jnt_qposadr[j]
+        if t == 3:
+            q[a] += rs.uniform(-0.5, 0.5)
+        elif t == 2:
+            q[a] += rs.uniform(-1.0, 1.0)
+    return q
+
+
+@pytest.mark.parametrize("name", DATA_XML)
+def test_host_build_matches_oracle_on_small_scenes(host, name):
+    m = sg.compile_mjcf(os.path.join(ROOT, "tests", "data", name + ".xml"), composite_neighbors=False)
+    sim = oracle_sim(m)
+    qs = [np.array(m.qpos0, dtype=np.float64)] + [perturbed(m, s) for s in range(3)] + [_wide(m, s) for s in range(40)]
+    qs += _episode_states(m, sim, None, None, 0.0, 200)
+    n, most, kinds, worst = _check_states(host, m, sim, qs, name)
+    assert most >= 1, most
+    print("%s: %d states, up to %d contacts, pair types %s, max deviation %.2e" % (name, n, most, sorted(kinds), worst))
+
+
+def test_host_build_matches_oracle_on_random_grippers(host, tmp_path):
+    """16 seeded random grippers (half with the object on a free joint): their roof boxes and ground plane bring plane - box and
+    box - box pairs into the lists"""
+    rng = np.random.RandomState(77)
+    kinds, states, most_all = set(), 0, 0
+    for i in range(16):
+        path = tmp_path / ("g%d.xml" % i)
+        path.write_text(random_gripper_xml(rng, free=bool(i % 2)))
+        m = sg.compile_mjcf(str(path), composite_neighbors=False)
+        nchain = int(np.flatnonzero(m.jnt_type != 3)[0])
+        jids = [j for j in range(nchain, m.njnt) if m.jnt_type[j] == 2]
+        sim = oracle_sim(m)
+        qs = [np.array(m.qpos0, dtype=np.float64)] + [perturbed(m, 10 * i + s) for s in range(3)]
+        qs += _episode_states(m, sim, jids, [0], rng.uniform(300, 1400), 200)
+        n, most, kd, worst = _check_states(host, m, sim, qs, "random gripper %d" % i)
+        kinds |= kd
+        states += n
+        most_all = max(most_all, most)
+    print("random grippers: %d states, up to %d contacts, pair types %s" % (states, most_all, sorted(kinds)))
+    assert (0, 6) in kinds and (6, 6) in kinds and (3, 6) in kinds, kinds     # plane - box, box - box, capsule - box all occurred
+
+
+def test_pair_table_counts(host):
+    """candidate pairs after the static filters, by pair_allowed's rule: the host build's table and the library's"""
+    from softgrip_amd import native
+    for scene, want in NPAIRS.items():
+        m = sg.load_model(model_path(scene))
+        assert CR.host_npairs(host, m) == want, scene
+        assert native.NativeModel(m).ncollision_pairs == want, scene
+
+
+def test_abi_entry_points_without_a_device():
+    from softgrip_amd import native
+    with open(os.path.join(ROOT, "include", "softgrip.h")) as f:
+        declared = set(re.findall(r"(sg_[a-z_]+)\s*\(", f.read()))
+    new = {"sg_get_contacts", "sg_model_ncollision_pairs"}
+    assert new <= declared and new <= set(native.SYMBOLS)
+    L = native.lib()
+    for s in new:
+        assert hasattr(L, s)
+    dummy = C.c_void_p(8)          # a contact array "given": never dereferenced, the argument checks come first
+    # NULL batch
+    assert L.sg_get_contacts(None, None, 1, 16, None, None, None, None, None, None) == native.SG_ERR_INVALID
+    assert b"sg_get_contacts" in L.sg_last_error() and b"null batch" in L.sg_last_error()
+    # n_ids <= 0
+    for n in (0, -3):
+        assert L.sg_get_contacts(None, None, n, 16, None, None, None, None, None, None) == native.SG_ERR_INVALID
+        assert b"n_ids" in L.sg_last_error()
+    # max_contacts <= 0 with any contact array given
+    for slot in range(4):
+        arrs = [None] * 4
+        arrs[slot] = dummy
+        for mc in (0, -1):
+            assert L.sg_get_contacts(None, None, 1, mc, None, *arrs, None) == native.SG_ERR_INVALID
+            assert b"max_contacts" in L.sg_last_error()
+    assert L.sg_model_ncollision_pairs(None) == 0
+    # (an env id out of range needs a batch: tests/test_gpu_contacts.py)
+
+
+def test_kernel_in_the_kept_assembly():
+    """sg_contacts.hip is compiled inside sg_api.hip: both instantiations of the kernel are in sg_api.device.s, the assembly check is
+    clean, no VGPR spills, and the scratch memory is exactly what DESIGN.md 8.1 states: the staging records and the box - box polygon
+    work space live in LDS, what is left are the axis tables the shared box - box routine indexes at run time"""
+    from softgrip_amd import build_native, isa_check
+    build_native.build()
+    api = [f for f in build_native.device_asm_files() if os.path.basename(f) == "sg_api.device.s"]
+    assert len(api) == 1
+    assert not isa_check.check_asm(api[0])
+    text = open(api[0]).read()
+    seen = {}
+    for block in text.split("  - .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", block).group(1)
+        val = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))  # noqa: E731
+        seen[name] = dict(scratch=val("private_segment_fixed_size"), vspill=val("vgpr_spill_count"), sspill=val("sgpr_spill_count"), vgpr=val("vgpr_count"),
+                          agpr=int(re.match(r"\s*(\d+)", block).group(1)), lds=val("group_segment_fixed_size"))
+    con = {k: v for k, v in seen.items() if "sg_contacts_kernel" in k}
+    assert len(con) == 2, sorted(seen)
+    for k, v in con.items():
+        print(k, v)
+        assert v["vspill"] == 0 and v["scratch"] == SCRATCH_BYTES, (k, v)
+        assert v["vgpr"] + v["agpr"] <= 512, (k, v)
