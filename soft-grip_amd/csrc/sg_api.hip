@@ -3,6 +3,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -11,6 +12,7 @@
 #include "sg_work.h"
 #include "sg_kin.hip"   // pose read-out and renderer kernels (compiled in this translation unit)
 #include "sg_contacts.hip"   // contact-list read-out kernel (compiled in this translation unit, after sg_kin.hip)
+#include "sg_devmem.h"   // SgArena, SgScratch: the owners of every device buffer below (after the HIP runtime's declarations)
 #ifdef SG_LEGACY_PIPELINES
 #include "sg_kernels_args.h"
 #endif
@@ -32,6 +34,11 @@ int fail(int code, const std::string& msg) {
     hipError_t e_ = (x);                                                                       \
     if (e_ != hipSuccess) return fail(SG_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
   } while (0)
+// a failed sg_devmem.h call on the buffers of `what`: SG_ERR_NOMEM for the allocation, SG_ERR_HIP for a memset, a copy or the synchronise
+int devmem_fail(bool nomem, const std::string& what) {
+  (void)hipGetLastError();   // (the failed call's error must not stay behind as the thread's last one: the next launch check, ours or the caller's, would report it)
+  return fail(nomem ? SG_ERR_NOMEM : SG_ERR_HIP, what + (nomem ? ": out of device memory" : ": a HIP memset, copy or synchronise failed"));
+}
 
 __global__ void sg_fill_rows_kernel(double* dst, const double* row, int n, int w) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -57,117 +64,96 @@ struct sg_model {
   bool has_tree;    // the tree pipeline (sg_tree.h) runs it
   SgPlan tplan;     // the tree pipeline's plan: same elements / equalities / statics, chains in `tree`, flat box references
   SgTreeDev tree;
+  size_t tree_lds = 0;       // the tree kernel's LDS block in bytes and an env's slice of its work space in doubles (sgt::lds_bytes,
+  long long tree_cws = 0;    // sgt::cws_doubles: each walks lds_carve, so once per model)
   SgKinHost kin;    // kinematics table of sg_get_poses / sg_render (sg_kin.hip)
   SgConHost con;    // candidate pairs, margins and bounding radii of sg_get_contacts (sg_contacts.hip)
 };
 
+// device tables and work space of the tree pipeline (sg_tree.h), allocated when the pipeline is first selected
+struct SgTreeBufs {
+  SgPlanHeader* H = nullptr;
+  SgTreeDev* T = nullptr;
+  double *elem = nullptr, *cws = nullptr;
+  SgGenPair* pairs = nullptr;
+  SgEqSlot* sched = nullptr;  // neighbour-row models: the tree plan's block schedule and neighbour tables
+  int* nbtab = nullptr;
+  int* touch_words = nullptr;   // [n][2]
+};
+
 struct sg_batch {
-  const sg_model* m;
-  int n, device;
-  SgPlanHeader* dH;
-  double *delem, *qpos, *qvel, *warm, *act, *ctrl, *kenv, *ctrl_row;
-  SgGenPair* dgpairs;  // SgPlan::gpairs on the device (the general contact path's candidate pairs)
-  int* dnbtab;       // SgPlan::nbtab on the device (neighbour-row models)
-  SgEqSlot* dsched;  // SgPlan::sched + one spare round of idle slots
-  unsigned* dtab;    // the same schedule as the solver's LDS table words
-  int* dcpos;        // per element: where its equality block's step factors sit in a solver wavefront's stream (SgWork::cst)
-  int *kmask_jnt, *kmask_ten, *flags, *touch, *ncon, *nefc, *iters;
+  const sg_model* m = nullptr;
+  int n = 0, device = 0;
+  SgArena mem;       // every buffer that lives as long as the batch: state, tables, the rows work space, the read-outs' tables
+  SgArena tree_mem;  // the buffers of `t`: all of them or none (tree_alloc)
+  SgPlanHeader* dH = nullptr;
+  double *delem = nullptr, *qpos = nullptr, *qvel = nullptr, *warm = nullptr, *act = nullptr, *ctrl = nullptr, *kenv = nullptr, *ctrl_row = nullptr;
+  SgGenPair* dgpairs = nullptr;  // SgPlan::gpairs on the device (the general contact path's candidate pairs)
+  int* dnbtab = nullptr;       // SgPlan::nbtab on the device (neighbour-row models)
+  SgEqSlot* dsched = nullptr;  // SgPlan::sched + eight spare rounds of idle slots
+  unsigned* dtab = nullptr;    // the same schedule as the solver's LDS table words
+  int* dcpos = nullptr;        // per element: where its equality block's step factors sit in a solver wavefront's stream (SgWork::cst)
+  int *kmask_jnt = nullptr, *kmask_ten = nullptr, *flags = nullptr, *touch = nullptr, *ncon = nullptr, *nefc = nullptr, *iters = nullptr;
   std::vector<int> kmask_jnt_host, kmask_ten_host;   // what the device masks hold (sg_set_stiffness copies them only when they change)
-  int epw_override;  // sg_set_solver_envs_per_wavefront: 0 = automatic
-  int pipeline;  // 0 fused (one kernel per call), 1 split (chain / phase / pgs kernel chain), 2 split with the row-parallel PGS kernel, 3 tree
-  // tree pipeline (allocated when first selected)
-  SgPlanHeader* dTH;
-  SgTreeDev* dT;
-  double *dtelem, *tcws;
-  SgGenPair* dtpairs;
-  SgEqSlot* dtsched;  // neighbour-row models: the tree plan's block schedule and neighbour tables
-  int* dtnbtab;
-  int* touch_words;   // [n][2]
-  bool tree_ready;    // every table and the work space of the tree pipeline allocated and filled (tree_alloc)
-  bool tree_attr_set;
-  SgWork w;
-  std::vector<void*> wbufs;
-  bool lds_attr_set;  // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done on this batch's device
+  int epw_override = 0;  // sg_set_solver_envs_per_wavefront: 0 = automatic
+  int pipeline = 3;  // 0 fused (one kernel per call), 1 split (chain / phase / pgs kernel chain), 2 split with the row-parallel PGS kernel, 3 tree
+  SgTreeBufs t;
+  bool tree_ready = false;    // every table and the work space of the tree pipeline allocated and filled (tree_alloc)
+  bool tree_attr_set = false;
+  SgWork w = {};
+  bool lds_attr_set = false;  // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done on this batch's device
   // profiling
-  bool prof;
+  bool prof = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-  double prof_ms;
-  long long prof_n;
+  double prof_ms = 0;
+  long long prof_n = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pgs;  // around every solver-kernel launch (the dominant kernel)
   std::vector<hipEvent_t> ev_pool;  // events handed back by sg_profile_read*: a profiled call creates none once the pool is warm
-  double prof_pgs_ms;
-  long long prof_pgs_n;
+  double prof_pgs_ms = 0;
+  long long prof_pgs_n = 0;
   // pose read-out / renderer (sg_kin.hip), allocated at first use
-  double* kin_d;
-  int* kin_i;
-  int* kin_ids;        // the listed env ids on the device
-  int kin_ids_cap;
-  float* rrecs;        // [n_ids][ngeom][SGR_REC] fp32 geom records of the last sg_render
-  size_t rrecs_cap;    // floats
+  double* kin_d = nullptr;
+  int* kin_i = nullptr;
+  SgScratch<int> kin_ids;    // the listed env ids on the device
+  SgScratch<float> rrecs;    // [n_ids][ngeom][SGR_REC] fp32 geom records of the last sg_render
   // contact read-out (sg_contacts.hip), allocated at first use
-  int* con_pairs;
-  double* con_gaux;
-  double* con_scratch;     // per-env pose blocks of a model whose poses do not fit LDS
-  size_t con_scratch_cap;  // doubles
-  bool con_attr_set;
+  int* con_pairs = nullptr;
+  double* con_gaux = nullptr;
+  SgScratch<double> con_scratch;   // per-env pose blocks of a model whose poses do not fit LDS
+  bool con_attr_set = false;
+  ~sg_batch() {   // (on the batch's device: sg_batch_destroy.  The arenas and scratch buffers free themselves)
+    for (auto& e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    for (auto& e : ev_pgs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    for (auto& e : ev_pool) (void)hipEventDestroy(e);
+  }
 };
 
 static int begin_event_pair(sg_batch* b, std::vector<std::pair<hipEvent_t, hipEvent_t>>& list, hipStream_t s);
 
-// device tables and work space of the tree pipeline (sg_tree.h), allocated when the pipeline is first selected
-static void tree_free(sg_batch* b) {
-  void** tptrs[] = {(void**)&b->dTH, (void**)&b->dT, (void**)&b->dtelem, (void**)&b->tcws, (void**)&b->dtpairs, (void**)&b->touch_words, (void**)&b->dtsched,
-                    (void**)&b->dtnbtab};
-  for (void** p : tptrs) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  b->tree_ready = false;
-}
-static int tree_alloc_all(sg_batch* b);
 // all or nothing: a failed allocation (the work space is ~0.5 MB per env for the four-finger scene) leaves no half-built pipeline behind
 // that a second sg_set_pipeline call would take for a complete one
 static int tree_alloc(sg_batch* b) {
   if (b->tree_ready) return SG_OK;
-  const int rc = tree_alloc_all(b);
-  if (rc != SG_OK) tree_free(b);
-  else b->tree_ready = true;
-  return rc;
-}
-static int tree_alloc_all(sg_batch* b) {
   const sg_model* m = b->m;
   if (!m->has_tree) return fail(SG_ERR_MODEL, "the tree pipeline does not run this model");
   const size_t n = b->n;
-  const long long cwd = sgt::cws_doubles(m->tree, m->tplan.h.nelem, m->tplan.h.has_free, m->tplan.h.nnb);
-#define TALLOC(p, bytes)                                                                  \
-  do {                                                                                    \
-    hipError_t e_ = hipMalloc((void**)&(p), (bytes));                                     \
-    if (e_ != hipSuccess) return fail(SG_ERR_NOMEM, std::string("hipMalloc (tree pipeline): ") + hipGetErrorString(e_)); \
-  } while (0)
-  TALLOC(b->dTH, sizeof(SgPlanHeader));
-  TALLOC(b->dT, sizeof(SgTreeDev));
-  TALLOC(b->dtelem, sizeof(double) * m->tplan.elem.size());
-  TALLOC(b->dtpairs, sizeof(SgGenPair) * (m->tplan.gpairs.size() + 1));
-  TALLOC(b->tcws, sizeof(double) * n * (size_t)cwd);
-  TALLOC(b->touch_words, sizeof(int) * 2 * n);
-  TALLOC(b->dtsched, sizeof(SgEqSlot) * (m->tplan.sched.size() + 1));
-  TALLOC(b->dtnbtab, sizeof(int) * (m->tplan.nbtab.size() + 1));
-#undef TALLOC
-  HIPCHK(hipMemcpy(b->dtsched, m->tplan.sched.data(), sizeof(SgEqSlot) * m->tplan.sched.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(b->dtnbtab, m->tplan.nbtab.data(), sizeof(int) * m->tplan.nbtab.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(b->dTH, &m->tplan.h, sizeof(SgPlanHeader), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(b->dT, &m->tree, sizeof(SgTreeDev), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(b->dtelem, m->tplan.elem.data(), sizeof(double) * m->tplan.elem.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(b->dtpairs, m->tplan.gpairs.data(), sizeof(SgGenPair) * m->tplan.gpairs.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(b->tcws, 0, sizeof(double) * n * (size_t)cwd));
-  HIPCHK(hipMemset(b->touch_words, 0, sizeof(int) * 2 * n));
-  if (!b->w.secprof) {   // (a model outside the two-finger class has no split-pipeline work space)
-    void* p = nullptr;
-    if (hipMalloc(&p, sizeof(unsigned long long) * 48) != hipSuccess) return fail(SG_ERR_NOMEM, "hipMalloc (tree pipeline)");
-    b->wbufs.push_back(p);
-    b->w.secprof = (unsigned long long*)p;
-    HIPCHK(hipMemset(p, 0, sizeof(unsigned long long) * 48));
+  SgArena& A = b->tree_mem;
+  SgTreeBufs& t = b->t;
+  bool ok = A.zeros(&t.H, 1) && A.zeros(&t.T, 1) && A.upload(&t.elem, m->tplan.elem) && A.upload(&t.pairs, m->tplan.gpairs) &&
+            A.zeros(&t.cws, n * (size_t)m->tree_cws) && A.zeros(&t.touch_words, 2 * n) && A.upload(&t.sched, m->tplan.sched) &&
+            A.upload(&t.nbtab, m->tplan.nbtab) && hipMemcpy(t.H, &m->tplan.h, sizeof(SgPlanHeader), hipMemcpyHostToDevice) == hipSuccess &&
+            hipMemcpy(t.T, &m->tree, sizeof(SgTreeDev), hipMemcpyHostToDevice) == hipSuccess;
+  bool nomem = A.nomem;
+  if (ok && !b->w.secprof) {   // (a model outside the two-finger class has no split-pipeline work space)
+    ok = b->mem.zeros(&b->w.secprof, 48);
+    nomem = b->mem.nomem;
   }
+  if (!ok) {
+    A.release();
+    t = SgTreeBufs();
+    return devmem_fail(nomem, "tree pipeline");
+  }
+  b->tree_ready = true;
   return SG_OK;
 }
 
@@ -176,22 +162,21 @@ static int launch_tree(sg_batch* b, int mode, const uint8_t* mask, int nsub, dou
                        hipStream_t s) {
   const sg_model* m = b->m;
   sgt::TreeArgs a;
-  a.H = b->dTH; a.T = b->dT; a.elem = b->dtelem; a.gpairs = b->dtpairs; a.sched = b->dtsched; a.nbtab = b->dtnbtab;
+  a.H = b->t.H; a.T = b->t.T; a.elem = b->t.elem; a.gpairs = b->t.pairs; a.sched = b->t.sched; a.nbtab = b->t.nbtab;
   a.qpos = b->qpos; a.qvel = b->qvel; a.warm = b->warm; a.act = b->act; a.ctrl = b->ctrl;
   a.kenv = b->kenv; a.kmask_jnt = b->kmask_jnt; a.kmask_ten = b->kmask_ten;
   a.mask = mask; a.sens = sens; a.sens_stride = stride > 0 ? stride : m->tplan.h.nsensordata;
-  a.flags = flags ? flags : b->flags; a.touch = touch ? touch : b->touch; a.touch_words = b->touch_words;
+  a.flags = flags ? flags : b->flags; a.touch = touch ? touch : b->touch; a.touch_words = b->t.touch_words;
   a.ncon = b->ncon; a.nefc = b->nefc; a.iters = b->iters;
-  a.cws = b->tcws; a.cws_stride = sgt::cws_doubles(m->tree, m->tplan.h.nelem, m->tplan.h.has_free, m->tplan.h.nnb);
+  a.cws = b->t.cws; a.cws_stride = m->tree_cws;
   a.nenv = b->n; a.nsub = nsub; a.mode = mode; a.secprof = b->w.secprof;
-  const size_t lds = sgt::lds_bytes(m->tree, m->tplan.h.nelem, m->tplan.h.has_free, m->tplan.h.nnb);
   if (!b->tree_attr_set) {
     HIPCHK(sg_tree_prepare());
     b->tree_attr_set = true;
   }
   if (b->prof)
     if (int rc = begin_event_pair(b, b->ev, s)) return rc;
-  HIPCHK(sg_launch_tree(a, m->tree.CS, lds, s));
+  HIPCHK(sg_launch_tree(a, m->tree.CS, m->tree_lds, s));
   if (b->prof) HIPCHK(hipEventRecord(b->ev.back().second, s));
   return SG_OK;
 }
@@ -207,7 +192,11 @@ int sg_model_create(const void* blob, size_t nbytes, sg_model** out) {
   std::string err, terr;
   m->has_fast = sg_plan_build(blob, nbytes, &m->plan, &err);
   m->has_tree = sg_tree_plan_build(blob, nbytes, &m->tplan, &m->tree, &terr);
-  if (m->has_tree && sgt::lds_bytes(m->tree, m->tplan.h.nelem, m->tplan.h.has_free, m->tplan.h.nnb) > 160 * 1024) {
+  if (m->has_tree) {
+    m->tree_lds = sgt::lds_bytes(m->tree, m->tplan.h.nelem, m->tplan.h.has_free, m->tplan.h.nnb);
+    m->tree_cws = sgt::cws_doubles(m->tree, m->tplan.h.nelem, m->tplan.h.has_free, m->tplan.h.nnb);
+  }
+  if (m->has_tree && m->tree_lds > 160 * 1024) {
     m->has_tree = false;
     terr = "the env's state does not fit the 160 KB of LDS";
   }
@@ -267,16 +256,6 @@ int sg_model_nelem(const sg_model* m) { return m->plan.h.nelem; }
 void sg_batch_destroy(sg_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
-  tree_free(b);
-  void* ptrs[] = {b->con_pairs, b->con_gaux, b->con_scratch, b->kin_d, b->kin_i, b->kin_ids, b->rrecs, b->dtab, b->dcpos, b->dgpairs, b->dnbtab, b->dsched, b->dH, b->delem, b->qpos, b->qvel, b->warm, b->act, b->ctrl, b->kenv, b->ctrl_row, b->kmask_jnt, b->kmask_ten,
-                  b->flags, b->touch, b->ncon, b->nefc, b->iters};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  for (void* p : b->wbufs)
-    if (p) (void)hipFree(p);
-  for (auto& e : b->ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-  for (auto& e : b->ev_pgs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-  for (auto& e : b->ev_pool) (void)hipEventDestroy(e);
   delete b;
 }
 
@@ -286,62 +265,33 @@ int sg_batch_create(const sg_model* m, int n_envs, int device, sg_batch** out) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SG_ERR_NO_DEVICE, "sg_batch_create: no HIP device (there is no CPU fallback)");
   if (device < 0 || device >= ndev) return fail(SG_ERR_NO_DEVICE, "sg_batch_create: device index out of range");
   HIPCHK(hipSetDevice(device));
-  sg_batch* b = new sg_batch();
-  b->m = m; b->n = n_envs; b->device = device; b->lds_attr_set = false; b->prof = false; b->prof_ms = 0; b->prof_n = 0; b->prof_pgs_ms = 0; b->prof_pgs_n = 0;
-  b->dnbtab = nullptr; b->dsched = nullptr; b->dgpairs = nullptr; b->dtab = nullptr; b->dcpos = nullptr; b->epw_override = 0;
-  b->dTH = nullptr; b->dT = nullptr; b->dtelem = b->tcws = nullptr; b->dtpairs = nullptr; b->touch_words = nullptr; b->tree_ready = false; b->tree_attr_set = false; b->dtsched = nullptr; b->dtnbtab = nullptr;
-  b->kin_d = nullptr; b->kin_i = nullptr; b->kin_ids = nullptr; b->kin_ids_cap = 0; b->rrecs = nullptr; b->rrecs_cap = 0;
-  b->con_pairs = nullptr; b->con_gaux = nullptr; b->con_scratch = nullptr; b->con_scratch_cap = 0; b->con_attr_set = false;
-  b->dH = nullptr; b->delem = b->qpos = b->qvel = b->warm = b->act = b->ctrl = b->kenv = b->ctrl_row = nullptr;
-  b->kmask_jnt = b->kmask_ten = b->flags = b->touch = b->ncon = b->nefc = b->iters = nullptr;
+  std::unique_ptr<sg_batch, void (*)(sg_batch*)> guard(new sg_batch(), sg_batch_destroy);   // every early return below destroys the half-built batch
+  sg_batch* b = guard.get();
+  b->m = m; b->n = n_envs; b->device = device;
+  SgArena& A = b->mem;
   const SgPlanHeader& H = m->plan.h;
-  const size_t n = n_envs, nv = H.nv, nq = H.nq, njnt = H.njnt, nu = H.nu > 0 ? H.nu : 1, nt = H.ntendon;   // nq = nv = njnt unless the model has a free joint
-#define ALLOC(p, bytes)                                   \
-  do {                                                    \
-    hipError_t e_ = hipMalloc((void**)&(p), (bytes));     \
-    if (e_ != hipSuccess) {                               \
-      sg_batch_destroy(b);                                \
-      return fail(SG_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e_)); \
-    }                                                     \
-  } while (0)
-  ALLOC(b->dH, sizeof(SgPlanHeader));
-  ALLOC(b->delem, sizeof(double) * m->plan.elem.size());
-  ALLOC(b->qpos, sizeof(double) * n * nq); ALLOC(b->qvel, sizeof(double) * n * nv); ALLOC(b->warm, sizeof(double) * n * nv);
-  ALLOC(b->act, sizeof(double) * n * nu); ALLOC(b->ctrl, sizeof(double) * n * nu); ALLOC(b->kenv, sizeof(double) * n);
-  ALLOC(b->ctrl_row, sizeof(double) * nu);
-  ALLOC(b->kmask_jnt, sizeof(int) * njnt); ALLOC(b->kmask_ten, sizeof(int) * nt);
-  ALLOC(b->flags, sizeof(int) * n); ALLOC(b->touch, sizeof(int) * n); ALLOC(b->ncon, sizeof(int) * n); ALLOC(b->nefc, sizeof(int) * n);
-  ALLOC(b->iters, sizeof(int) * n);
-  memset(&b->w, 0, sizeof b->w);
-  b->pipeline = 3;
-  if (m->has_fast) {  // workspace of the split pipeline
+  const size_t n = n_envs, nv = H.nv, nq = H.nq, njnt = H.njnt, nu = H.nu, nt = H.ntendon;   // nq = nv = njnt unless the model has a free joint
+  bool ok = A.zeros(&b->dH, 1) && hipMemcpy(b->dH, &H, sizeof H, hipMemcpyHostToDevice) == hipSuccess && A.upload(&b->delem, m->plan.elem) &&
+            A.zeros(&b->qpos, n * nq) && A.zeros(&b->qvel, n * nv) && A.zeros(&b->warm, n * nv) && A.zeros(&b->act, n * nu) &&
+            A.zeros(&b->ctrl, n * nu) && A.zeros(&b->kenv, n) && A.zeros(&b->ctrl_row, nu) && A.zeros(&b->kmask_jnt, njnt) &&
+            A.zeros(&b->kmask_ten, nt) && A.zeros(&b->flags, n) && A.zeros(&b->touch, n) && A.zeros(&b->ncon, n) && A.zeros(&b->nefc, n) &&
+            A.zeros(&b->iters, n) && A.upload(&b->dgpairs, m->plan.gpairs);
+  if (!ok) return devmem_fail(A.nomem, "sg_batch_create (state)");
+  b->kmask_jnt_host.assign(njnt, 0); b->kmask_ten_host.assign(nt, 0);
+  if (m->has_fast) {  // work space of the split pipeline
     const size_t S = 2 * n, N = H.nelem;
-    auto walloc = [&](void** p, size_t bytes) -> bool {
-      if (hipMalloc(p, bytes) != hipSuccess) return false;
-      b->wbufs.push_back(*p);
-      return hipMemset(*p, 0, bytes) == hipSuccess;
-    };
-    bool ok = walloc((void**)&b->w.secprof, sizeof(unsigned long long) * 48) && walloc((void**)&b->w.crec, sizeof(double) * (SG_LEGACY_ON ? SG_CAP * ((n + SG_EPW - 1) / SG_EPW + 1) * SG_RF * SG_SPW : 2)) && walloc((void**)&b->w.ns, sizeof(int) * S) &&
-              walloc((void**)&b->w.crow, sizeof(double) * (SG_CAP + 2) * ((n + 7) / 8 + 2) * SG_RK * 64) &&
-              walloc((void**)&b->w.cdummy, sizeof(double) * ((n + 3) / 4) * SG_RK * 64) &&
-              walloc((void**)&b->w.envh, sizeof(double) * 4 * n) && walloc((void**)&b->w.shared, sizeof(int) * n) &&
-              walloc((void**)&b->w.pending, sizeof(int) * n) && walloc((void**)&b->w.status, sizeof(int) * n) &&
-              walloc((void**)&b->w.iters, sizeof(int) * n) && walloc((void**)&b->w.ncon, sizeof(int) * n) &&
-              walloc((void**)&b->w.nefc, sizeof(int) * n) && walloc((void**)&b->w.touch, sizeof(int) * n) &&
-              walloc((void**)&b->w.sMinv, sizeof(double) * 16 * S) && walloc((void**)&b->w.saF, sizeof(double) * 4 * S) &&
-              walloc((void**)&b->w.lim_active, sizeof(int) * S) && walloc((void**)&b->w.lim, sizeof(double) * 4 * SG_MAXLIM * S) &&
-              walloc((void**)&b->w.as, sizeof(double) * n * N) && walloc((void**)&b->w.eqf, sizeof(double) * n * N) &&
-              walloc((void**)&b->w.eqb, sizeof(double) * n * N) && walloc((void**)&b->w.eqR, sizeof(double) * n * N) &&
-              walloc((void**)&b->w.asme, sizeof(double) * n * N) && walloc((void**)&b->w.fsm, sizeof(double) * n * N) &&
-              walloc((void**)&b->w.chh, sizeof(double) * n * 2 * SG_CHW) &&
-              walloc((void**)&b->w.nbf, sizeof(double) * n * (3 * N + 1)) && walloc((void**)&b->w.nbb, sizeof(double) * n * (3 * N + 1)) &&
-              walloc((void**)&b->w.nbR, sizeof(double) * n * (3 * N + 1)) &&
-              walloc((void**)&b->w.cst, sizeof(double) * ((H.nnb > 0 && SG_ROWS_NB_MODE(H.nelem, H.eq_rounds) == 2) ? SG_CST_INDEX((n + 3) / 4, 0, 0, H.eq_rounds + 8) : 2)) &&
-              walloc((void**)&b->w.gcon, sizeof(double) * n * SG_GEN_MAXCON * SG_GEN_W) && walloc((void**)&b->w.gen, sizeof(int) * n) &&
-              walloc((void**)&b->w.gen_count, sizeof(int) * 4) && walloc((void**)&b->w.gen_list, sizeof(int) * n) &&
-              walloc((void**)&b->w.gpairs16, SG_PHASE_SLIM(m->rounds) ? sizeof(unsigned short) * n * SG_PAIRS_CAP(4) : 16) &&
-              walloc((void**)&b->w.gcval, SG_PHASE_SLIM(m->rounds) ? sizeof(double) * n * SG_MAXCH * 64 : 16);
-    if (!ok) { sg_batch_destroy(b); return fail(SG_ERR_NOMEM, "hipMalloc (split-pipeline workspace)"); }
+    SgWork& w = b->w;
+    ok = A.zeros(&w.secprof, 48) && A.zeros(&w.crec, SG_LEGACY_ON ? SG_CAP * ((n + SG_EPW - 1) / SG_EPW + 1) * SG_RF * SG_SPW : 0) && A.zeros(&w.ns, S) &&
+         A.zeros(&w.crow, (SG_CAP + 2) * ((n + 7) / 8 + 2) * SG_RK * 64) && A.zeros(&w.cdummy, ((n + 3) / 4) * SG_RK * 64) &&
+         A.zeros(&w.envh, 4 * n) && A.zeros(&w.shared, n) && A.zeros(&w.pending, n) && A.zeros(&w.status, n) && A.zeros(&w.iters, n) &&
+         A.zeros(&w.ncon, n) && A.zeros(&w.nefc, n) && A.zeros(&w.touch, n) && A.zeros(&w.sMinv, 16 * S) && A.zeros(&w.saF, 4 * S) &&
+         A.zeros(&w.lim_active, S) && A.zeros(&w.lim, 4 * SG_MAXLIM * S) && A.zeros(&w.as, n * N) && A.zeros(&w.eqf, n * N) &&
+         A.zeros(&w.eqb, n * N) && A.zeros(&w.eqR, n * N) && A.zeros(&w.asme, n * N) && A.zeros(&w.fsm, n * N) &&
+         A.zeros(&w.chh, n * 2 * SG_CHW) && A.zeros(&w.nbf, n * (3 * N + 1)) && A.zeros(&w.nbb, n * (3 * N + 1)) && A.zeros(&w.nbR, n * (3 * N + 1)) &&
+         A.zeros(&w.cst, (H.nnb > 0 && SG_ROWS_NB_MODE(H.nelem, H.eq_rounds) == 2) ? SG_CST_INDEX((n + 3) / 4, 0, 0, H.eq_rounds + 8) : 0) &&
+         A.zeros(&w.gcon, n * SG_GEN_MAXCON * SG_GEN_W) && A.zeros(&w.gen, n) && A.zeros(&w.gen_count, 4) && A.zeros(&w.gen_list, n) &&
+         A.zeros(&w.gpairs16, SG_PHASE_SLIM(m->rounds) ? n * SG_PAIRS_CAP(4) : 0) && A.zeros(&w.gcval, SG_PHASE_SLIM(m->rounds) ? n * SG_MAXCH * 64 : 0);
+    if (!ok) return devmem_fail(A.nomem, "sg_batch_create (split-pipeline work space)");
     const char* pm = getenv("SG_PIPELINE");
     b->pipeline = (pm && strcmp(pm, "tree") == 0 && m->has_tree) ? 3 : 2;
 #ifdef SG_LEGACY_PIPELINES
@@ -355,10 +305,6 @@ int sg_batch_create(const sg_model* m, int n_envs, int device, sg_batch** out) {
     SgEqSlot idle;
     idle.e = idle.p[0] = idle.p[1] = idle.p[2] = H.nelem;
     for (int g = 0; g < 8 * SG_EQ_SLOTS; g++) sch.push_back(idle);  // the kernel fetches slots a few rounds ahead
-    ALLOC(b->dnbtab, sizeof(int) * m->plan.nbtab.size());
-    ALLOC(b->dsched, sizeof(SgEqSlot) * sch.size());
-    HIPCHK(hipMemcpy(b->dnbtab, m->plan.nbtab.data(), sizeof(int) * m->plan.nbtab.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(b->dsched, sch.data(), sizeof(SgEqSlot) * sch.size(), hipMemcpyHostToDevice));
     // the solver's table words (sg_pgs_rows_kernel): lane 2 b + h of a 16-lane group holds, for the block e in slot b of the round,
     // x | y << 11 | (2 e + h) << 22: the byte offsets of two slider words, (x, y) = 8 (e, p0) for h = 0 and 8 (p1, p2) for h = 1, and the
     // lane's pair of row states in 16-byte units
@@ -373,21 +319,14 @@ int sg_batch_create(const sg_model* m, int n_envs, int device, sg_batch** out) {
       if (two_words) { tab[2 * i] = (8u * x) | ((8u * y) << 16); tab[2 * i + 1] = 64u * (unsigned)sl.e + 32u * (unsigned)h; }
       else tab[i] = (8u * x) | ((8u * y) << 11) | ((2u * (unsigned)sl.e + (unsigned)h) << 22);
     }
-    ALLOC(b->dtab, sizeof(unsigned) * tab.size());
-    HIPCHK(hipMemcpy(b->dtab, tab.data(), sizeof(unsigned) * tab.size(), hipMemcpyHostToDevice));
     // where the phase kernel puts a block's four step factors: round r, slot g of the schedule = lanes 2 g, 2 g + 1 of the env's
     // 16-lane group, two doubles each (SG_CST_INDEX)
     std::vector<int> cpos(H.nelem, 0);
     for (size_t i = 0; i < m->plan.sched.size(); i++)
       if (m->plan.sched[i].e < H.nelem) cpos[m->plan.sched[i].e] = (int)(i / SG_EQ_SLOTS) * 128 + 4 * (int)(i % SG_EQ_SLOTS);
-    ALLOC(b->dcpos, sizeof(int) * cpos.size());
-    HIPCHK(hipMemcpy(b->dcpos, cpos.data(), sizeof(int) * cpos.size(), hipMemcpyHostToDevice));
+    if (!(A.upload(&b->dnbtab, m->plan.nbtab) && A.upload(&b->dsched, sch) && A.upload(&b->dtab, tab) && A.upload(&b->dcpos, cpos)))
+      return devmem_fail(A.nomem, "sg_batch_create (solver tables)");
   }
-  ALLOC(b->dgpairs, sizeof(SgGenPair) * (m->plan.gpairs.size() + 1));
-  HIPCHK(hipMemcpy(b->dgpairs, m->plan.gpairs.data(), sizeof(SgGenPair) * m->plan.gpairs.size(), hipMemcpyHostToDevice));
-#undef ALLOC
-  HIPCHK(hipMemcpy(b->dH, &H, sizeof H, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(b->delem, m->plan.elem.data(), sizeof(double) * m->plan.elem.size(), hipMemcpyHostToDevice));
   // state as after mj_resetData
   std::vector<double> q0(nq, 0.0);
   for (int c = 0; c < H.nchain; c++)
@@ -400,16 +339,9 @@ int sg_batch_create(const sg_model* m, int n_envs, int device, sg_batch** out) {
   std::vector<double> qall(n * nq);
   for (size_t i = 0; i < n; i++) memcpy(&qall[i * nq], q0.data(), sizeof(double) * nq);
   HIPCHK(hipMemcpy(b->qpos, qall.data(), sizeof(double) * n * nq, hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(b->qvel, 0, sizeof(double) * n * nv)); HIPCHK(hipMemset(b->warm, 0, sizeof(double) * n * nv));
-  HIPCHK(hipMemset(b->act, 0, sizeof(double) * n * nu)); HIPCHK(hipMemset(b->ctrl, 0, sizeof(double) * n * nu));
-  HIPCHK(hipMemset(b->kenv, 0, sizeof(double) * n));
-  HIPCHK(hipMemset(b->kmask_jnt, 0, sizeof(int) * njnt)); HIPCHK(hipMemset(b->kmask_ten, 0, sizeof(int) * nt));
-  b->kmask_jnt_host.assign(njnt, 0); b->kmask_ten_host.assign(nt, 0);
-  HIPCHK(hipMemset(b->flags, 0, sizeof(int) * n)); HIPCHK(hipMemset(b->touch, 0, sizeof(int) * n));
-  HIPCHK(hipMemset(b->ncon, 0, sizeof(int) * n)); HIPCHK(hipMemset(b->nefc, 0, sizeof(int) * n)); HIPCHK(hipMemset(b->iters, 0, sizeof(int) * n));
   if (b->pipeline == 3)
-    if (int rc = tree_alloc(b)) { sg_batch_destroy(b); return rc; }
-  *out = b;
+    if (int rc = tree_alloc(b)) return rc;
+  *out = guard.release();
   return SG_OK;
 }
 int sg_batch_nenvs(const sg_batch* b) { return b->n; }
@@ -481,6 +413,24 @@ static int begin_event_pair(sg_batch* b, std::vector<std::pair<hipEvent_t, hipEv
   }
   list.emplace_back(e[0], e[1]);
   HIPCHK(hipEventRecord(e[0], s));
+  return SG_OK;
+}
+
+// sg_profile_read*: the finished pairs of `list` into the two accumulators, their events back to the pool
+static int profile_read(sg_batch* b, std::vector<std::pair<hipEvent_t, hipEvent_t>>& list, double& sum_ms, long long& count, int reset, double* avg_ms,
+                        long long* launches) {
+  HIPCHK(hipSetDevice(b->device));
+  for (auto& e : list) {
+    HIPCHK(hipEventSynchronize(e.second));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e.first, e.second));
+    sum_ms += ms; count++;
+    b->ev_pool.push_back(e.first); b->ev_pool.push_back(e.second);
+  }
+  list.clear();
+  if (avg_ms) *avg_ms = count ? sum_ms / count : 0.0;
+  if (launches) *launches = count;
+  if (reset) { sum_ms = 0; count = 0; }
   return SG_OK;
 }
 
@@ -667,7 +617,7 @@ int sg_get_touch_words(sg_batch* b, int32_t* out, int nwords, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(hipMemsetAsync(out, 0, sizeof(int32_t) * (size_t)b->n * nwords, s));
   if (b->pipeline == 3)
-    HIPCHK(hipMemcpy2DAsync(out, sizeof(int32_t) * nwords, b->touch_words, sizeof(int32_t) * 2, sizeof(int32_t) * (nwords < 2 ? nwords : 2), b->n,
+    HIPCHK(hipMemcpy2DAsync(out, sizeof(int32_t) * nwords, b->t.touch_words, sizeof(int32_t) * 2, sizeof(int32_t) * (nwords < 2 ? nwords : 2), b->n,
                             hipMemcpyDeviceToDevice, s));
   else
     HIPCHK(hipMemcpy2DAsync(out, sizeof(int32_t) * nwords, b->pipeline == 0 ? b->touch : b->w.touch, sizeof(int32_t), sizeof(int32_t), b->n,
@@ -696,7 +646,7 @@ int sg_tree_workgroups_per_cu(const sg_batch* b) {
   const sg_model* m = b->m;
   if (hipSetDevice(b->device) != hipSuccess) return fail(SG_ERR_NO_DEVICE, "hipSetDevice");
   if (sg_tree_prepare() != hipSuccess) return fail(SG_ERR_HIP, "sg_tree_prepare");
-  return sg_tree_occupancy(m->tree.CS, sgt::lds_bytes(m->tree, m->tplan.h.nelem, m->tplan.h.has_free, m->tplan.h.nnb));
+  return sg_tree_occupancy(m->tree.CS, m->tree_lds);
 }
 
 #ifdef SG_SECTION_PROF
@@ -716,13 +666,13 @@ int sg_debug_sections(sg_batch* b, unsigned long long* out32) {
 // (sg_tree.h: staged narrowphase records | contact rows | mass-matrix blocks | the arrays lds_carve backs with global memory), to be
 // held word by word against the host emulation's after the same launch.  -> the number of doubles copied (<= cap), or a negative error
 long long sg_debug_tree_work(sg_batch* b, int env, double* out, long long cap) {
-  if (!b || !out || env < 0 || env >= b->n || !b->tcws) return fail(SG_ERR_INVALID, "sg_debug_tree_work: bad argument");
+  if (!b || !out || env < 0 || env >= b->n || !b->t.cws) return fail(SG_ERR_INVALID, "sg_debug_tree_work: bad argument");
   const sg_model* m = b->m;
-  long long n = sgt::cws_doubles(m->tree, m->tplan.h.nelem, m->tplan.h.has_free, m->tplan.h.nnb);
+  long long n = m->tree_cws;
   if (n > cap) n = cap;
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out, b->tcws + (size_t)env * sgt::cws_doubles(m->tree, m->tplan.h.nelem, m->tplan.h.has_free, m->tplan.h.nnb), sizeof(double) * n, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, b->t.cws + (size_t)env * m->tree_cws, sizeof(double) * n, hipMemcpyDeviceToHost));
   return n;
 }
 #endif
@@ -735,36 +685,12 @@ int sg_profile_enable(sg_batch* b, int enable) {
 
 int sg_profile_read_solver(sg_batch* b, int reset, double* avg_ms, long long* launches) {
   if (!b) return fail(SG_ERR_INVALID, "sg_profile_read_solver: bad argument");
-  HIPCHK(hipSetDevice(b->device));
-  for (auto& e : b->ev_pgs) {
-    HIPCHK(hipEventSynchronize(e.second));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e.first, e.second));
-    b->prof_pgs_ms += ms; b->prof_pgs_n++;
-    b->ev_pool.push_back(e.first); b->ev_pool.push_back(e.second);
-  }
-  b->ev_pgs.clear();
-  if (avg_ms) *avg_ms = b->prof_pgs_n ? b->prof_pgs_ms / b->prof_pgs_n : 0.0;
-  if (launches) *launches = b->prof_pgs_n;
-  if (reset) { b->prof_pgs_ms = 0; b->prof_pgs_n = 0; }
-  return SG_OK;
+  return profile_read(b, b->ev_pgs, b->prof_pgs_ms, b->prof_pgs_n, reset, avg_ms, launches);
 }
 
 int sg_profile_read(sg_batch* b, int reset, double* avg_ms, long long* launches) {
   if (!b) return fail(SG_ERR_INVALID, "sg_profile_read: bad argument");
-  HIPCHK(hipSetDevice(b->device));
-  for (auto& e : b->ev) {
-    HIPCHK(hipEventSynchronize(e.second));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e.first, e.second));
-    b->prof_ms += ms; b->prof_n++;
-    b->ev_pool.push_back(e.first); b->ev_pool.push_back(e.second);
-  }
-  b->ev.clear();
-  if (avg_ms) *avg_ms = b->prof_n ? b->prof_ms / b->prof_n : 0.0;
-  if (launches) *launches = b->prof_n;
-  if (reset) { b->prof_ms = 0; b->prof_n = 0; }
-  return SG_OK;
+  return profile_read(b, b->ev, b->prof_ms, b->prof_n, reset, avg_ms, launches);
 }
 
 // ---- pose read-out and renderer (sg_kin.hip) ----
@@ -789,26 +715,19 @@ static int kin_prepare(sg_batch* b, const char* fn, const int32_t* env_ids, int 
       if (env_ids[i] < 0 || env_ids[i] >= b->n)
         return fail(SG_ERR_INVALID, std::string(fn) + ": env id " + std::to_string(env_ids[i]) + " out of range [0, " + std::to_string(b->n) + ")");
   HIPCHK(hipSetDevice(b->device));
-  if (!b->kin_d) {
+  if (!b->kin_d) {   // built on the side: the batch sees the tables only once both are filled
+    SgArena A;
     double* d = nullptr;
     int* ip = nullptr;
-    if (hipMalloc((void**)&d, sizeof(double) * K.dbl.size()) != hipSuccess) return fail(SG_ERR_NOMEM, std::string(fn) + ": hipMalloc");
-    if (hipMalloc((void**)&ip, sizeof(int) * K.ints.size()) != hipSuccess) { (void)hipFree(d); return fail(SG_ERR_NOMEM, std::string(fn) + ": hipMalloc"); }
+    if (!(A.upload(&d, K.dbl) && A.upload(&ip, K.ints))) return devmem_fail(A.nomem, std::string(fn) + " (pose tables)");
+    A.give_to(b->mem);
     b->kin_d = d; b->kin_i = ip;
-    HIPCHK(hipMemcpy(b->kin_d, K.dbl.data(), sizeof(double) * K.dbl.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(b->kin_i, K.ints.data(), sizeof(int) * K.ints.size(), hipMemcpyHostToDevice));
   }
   *dids = nullptr;
   if (env_ids) {
-    if (n_ids > b->kin_ids_cap) {
-      HIPCHK(hipStreamSynchronize(s));   // (the old buffer may still be read by an earlier launch on this stream)
-      if (b->kin_ids) (void)hipFree(b->kin_ids);
-      b->kin_ids = nullptr; b->kin_ids_cap = 0;
-      if (hipMalloc((void**)&b->kin_ids, sizeof(int) * n_ids) != hipSuccess) return fail(SG_ERR_NOMEM, std::string(fn) + ": hipMalloc");
-      b->kin_ids_cap = n_ids;
-    }
-    HIPCHK(hipMemcpyAsync(b->kin_ids, env_ids, sizeof(int) * n_ids, hipMemcpyHostToDevice, s));
-    *dids = b->kin_ids;
+    if (!b->kin_ids.reserve(n_ids, s)) return devmem_fail(b->kin_ids.nomem, std::string(fn) + " (env ids)");
+    HIPCHK(hipMemcpyAsync(b->kin_ids.p, env_ids, sizeof(int) * n_ids, hipMemcpyHostToDevice, s));
+    *dids = b->kin_ids.p;
   }
   return SG_OK;
 }
@@ -848,19 +767,12 @@ int sg_render(sg_batch* b, const double* cam, const int32_t* env_ids, int n_ids,
   hipStream_t s = (hipStream_t)stream;
   const int* dids = nullptr;
   if (int rc = kin_prepare(b, "sg_render", env_ids, n_ids, s, &dids)) return rc;
-  const size_t need = (size_t)n_ids * K.o.ngeom * SGR_REC;
-  if (need > b->rrecs_cap) {
-    HIPCHK(hipStreamSynchronize(s));
-    if (b->rrecs) (void)hipFree(b->rrecs);
-    b->rrecs = nullptr; b->rrecs_cap = 0;
-    if (hipMalloc((void**)&b->rrecs, sizeof(float) * need) != hipSuccess) return fail(SG_ERR_NOMEM, "sg_render: hipMalloc (geom records)");
-    b->rrecs_cap = need;
-  }
+  if (!b->rrecs.reserve((size_t)n_ids * K.o.ngeom * SGR_REC, s)) return devmem_fail(b->rrecs.nomem, "sg_render (geom records)");
   SgRenderArgs a;
   double eye[3];
   sgr_camera(cam, width, height, eye, &a.cam);
-  if (int rc = launch_kin(b, dids, n_ids, nullptr, nullptr, nullptr, nullptr, b->rrecs, eye, s)) return rc;
-  a.recs = b->rrecs; a.ngeom = K.o.ngeom; a.n_ids = n_ids;
+  if (int rc = launch_kin(b, dids, n_ids, nullptr, nullptr, nullptr, nullptr, b->rrecs.p, eye, s)) return rc;
+  a.recs = b->rrecs.p; a.ngeom = K.o.ngeom; a.n_ids = n_ids;
   a.tiles_x = (width + SGR_TILE - 1) / SGR_TILE;
   a.ntiles = a.tiles_x * ((height + SGR_TILE - 1) / SGR_TILE);
   a.rgba = rgba; a.depth = depth; a.segid = segid;
@@ -891,25 +803,18 @@ int sg_get_contacts(sg_batch* b, const int32_t* env_ids, int n_ids, int max_cont
   const int* dids = nullptr;
   if (int rc = kin_prepare(b, "sg_get_contacts", env_ids, n_ids, s, &dids)) return rc;
   if (!ncon && !geom && !dist && !pos && !frame) return SG_OK;
-  if (!b->con_pairs) {
+  if (!b->con_pairs) {   // (on the side, as the pose tables)
+    SgArena A;
     int* dp = nullptr;
     double* dg = nullptr;
-    if (hipMalloc((void**)&dp, sizeof(int) * (Cn.pairs.size() + 2)) != hipSuccess) return fail(SG_ERR_NOMEM, "sg_get_contacts: hipMalloc");
-    if (hipMalloc((void**)&dg, sizeof(double) * (Cn.gaux.size() + 2)) != hipSuccess) { (void)hipFree(dp); return fail(SG_ERR_NOMEM, "sg_get_contacts: hipMalloc"); }
+    if (!(A.upload(&dp, Cn.pairs) && A.upload(&dg, Cn.gaux))) return devmem_fail(A.nomem, "sg_get_contacts (pair tables)");
+    A.give_to(b->mem);
     b->con_pairs = dp; b->con_gaux = dg;
-    HIPCHK(hipMemcpy(b->con_pairs, Cn.pairs.data(), sizeof(int) * Cn.pairs.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(b->con_gaux, Cn.gaux.data(), sizeof(double) * Cn.gaux.size(), hipMemcpyHostToDevice));
   }
   const size_t npose = sgc_pose_doubles(K.o);
   const size_t lds = sizeof(double) * (SGC_FIXED_DBL + npose);
   const bool in_lds = lds <= 159 * 1024;   // (the kernel has 256 B of static LDS besides; the CU has 160 KB)
-  if (!in_lds && (size_t)n_ids * npose > b->con_scratch_cap) {
-    HIPCHK(hipStreamSynchronize(s));   // (the old block may still be in use by an earlier launch on this stream)
-    if (b->con_scratch) (void)hipFree(b->con_scratch);
-    b->con_scratch = nullptr; b->con_scratch_cap = 0;
-    if (hipMalloc((void**)&b->con_scratch, sizeof(double) * n_ids * npose) != hipSuccess) return fail(SG_ERR_NOMEM, "sg_get_contacts: hipMalloc (pose blocks)");
-    b->con_scratch_cap = (size_t)n_ids * npose;
-  }
+  if (!in_lds && !b->con_scratch.reserve((size_t)n_ids * npose, s)) return devmem_fail(b->con_scratch.nomem, "sg_get_contacts (pose blocks)");
   if (in_lds && !b->con_attr_set) {   // per device, as the solver kernels' attribute; what this model's launches ask for (above 64 KB it must be granted)
     HIPCHK(hipFuncSetAttribute((const void*)sg_contacts_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     b->con_attr_set = true;
@@ -917,7 +822,7 @@ int sg_get_contacts(sg_batch* b, const int32_t* env_ids, int n_ids, int max_cont
   SgConArgs a;
   a.D = b->kin_d; a.I = b->kin_i; a.o = K.o; a.gaux = b->con_gaux; a.pairs = b->con_pairs; a.npair = (int)(Cn.pairs.size() / 2); a.cap = Cn.cap;
   a.qpos = b->qpos; a.env_ids = dids; a.n_ids = n_ids; a.max_contacts = max_contacts;
-  a.ncon = ncon; a.geom = geom; a.dist = dist; a.pos = pos; a.frame = frame; a.scratch = in_lds ? nullptr : b->con_scratch;
+  a.ncon = ncon; a.geom = geom; a.dist = dist; a.pos = pos; a.frame = frame; a.scratch = in_lds ? nullptr : b->con_scratch.p;
   if (in_lds) hipLaunchKernelGGL(sg_contacts_kernel<true>, dim3(n_ids), dim3(64), lds, s, a);
   else hipLaunchKernelGGL(sg_contacts_kernel<false>, dim3(n_ids), dim3(64), sizeof(double) * SGC_FIXED_DBL, s, a);
   HIPCHK(hipGetLastError());
