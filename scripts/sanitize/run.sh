@@ -1,7 +1,9 @@
 #!/bin/bash
 # AddressSanitizer + UBSan over the host-side native code (MJCF compiler, plan builder): CPU build only (GPU sanitizers are not
 # available on the pool).  usage: scripts/sanitize/run.sh [more.xml ...]   -- compiles every tests/data/*.xml (+ arguments) in both
-# composite variants and builds the kernel plan; malformed and missing files must come back as messages.
+# composite variants and builds both kernel plans (two-finger and tree); malformed and missing files must come back as messages.  Then
+# the mutation mode: both builders and the blob lookups of csrc/sg_blob.h over damaged copies of every models/*.sgmodel (cut at and
+# around every record boundary, nrec raised, a record's count raised past the end, total_bytes off by one): each must be refused.
 set -e
 HERE=$(cd "$(dirname "$0")" && pwd); ROOT=$(cd "$HERE/../.." && pwd)
 OUT=${TMPDIR:-/tmp}/sg_sanitize_host
@@ -15,4 +17,5 @@ for c in "2000 2000 2000" "1e300 4 4" "20 20 20"; do
   printf "<mujoco><compiler angle='radian'/><option solver='PGS' cone='elliptic'/><worldbody><body pos='0 0 1'><composite type='box' count='%s' spacing='.3'><geom type='capsule' size='.02 .05' mass='.01'/></composite></body></worldbody></mujoco>" "$c" > "$T/sg_count_${c%% *}.xml"
 done
 "$OUT" "$ROOT"/tests/data/*.xml "$T/sg_broken.xml" "$T/sg_missing.xml" "$T/sg_cycle.xml" "$T"/sg_count_*.xml "$@"
+"$OUT" --mutate "$ROOT"/models/*.sgmodel
 echo "sanitize: clean"

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "sg_general.h"
+#include "sg_pairs.h"   // sgc_pair_allowed, sgc_enum_pairs, sgc_build_pairs: the candidate-pair table (shared with sg_plan.cpp)
 #include "../../include/softgrip_model.h"
 
 #define SGC_MAXCON 512        // the oracle's MAXCON: add_contact keeps no more, whatever the model's nconmax says
@@ -30,49 +31,6 @@
 
 // contacts mj_collision keeps at most: the model's nconmax when positive, and the oracle's 512
 inline int sgc_cap(int nconmax) { return nconmax > 0 && nconmax < SGC_MAXCON ? nconmax : SGC_MAXCON; }
-
-// the oracle's pair_allowed
-inline bool sgc_pair_allowed(const int* body_parentid, const int* body_weldid, const int* geom_bodyid, const int* contype, const int* conaffinity,
-                             int g1, int g2) {
-  const int b1 = geom_bodyid[g1], b2 = geom_bodyid[g2];
-  if (!((contype[g1] & conaffinity[g2]) || (contype[g2] & conaffinity[g1]))) return false;
-  const int w1 = body_weldid[b1], w2 = body_weldid[b2];
-  if (w1 == w2) return false;   // same weld group (both static too)
-  const int wp1 = body_weldid[body_parentid[w1]], wp2 = body_weldid[body_parentid[w2]];
-  if (w1 != 0 && w2 != 0 && (w1 == wp2 || w2 == wp1)) return false;   // parent - child
-  return true;
-}
-
-// candidate pairs [npair][2] (geom1, geom2 in mj_collideGeoms' by-type order).  false + err: a pair of types without a narrowphase routine.
-inline bool sgc_build_pairs(int nbody, int ngeom, const int* body_parentid, const int* body_weldid, const int* body_geomadr, const int* body_geomnum,
-                            const int* geom_bodyid, const int* geom_type, const int* contype, const int* conaffinity, std::vector<int>* pairs,
-                            std::string* err) {
-  pairs->clear();
-  for (int b = 0; b < nbody; b++) {
-    if (body_parentid[b] < 0 || body_parentid[b] >= nbody || body_weldid[b] < 0 || body_weldid[b] >= nbody || body_geomnum[b] < 0 ||
-        (body_geomnum[b] > 0 && (body_geomadr[b] < 0 || body_geomadr[b] + body_geomnum[b] > ngeom))) {
-      *err = "body tables out of range";
-      return false;
-    }
-  }
-  for (int g = 0; g < ngeom; g++)
-    if (geom_bodyid[g] < 0 || geom_bodyid[g] >= nbody) { *err = "geom body out of range"; return false; }
-  for (int b1 = 0; b1 < nbody; b1++)
-    for (int b2 = b1 + 1; b2 < nbody; b2++)
-      for (int i = 0; i < body_geomnum[b1]; i++)
-        for (int j = 0; j < body_geomnum[b2]; j++) {
-          int g1 = body_geomadr[b1] + i, g2 = body_geomadr[b2] + j;
-          if (!sgc_pair_allowed(body_parentid, body_weldid, geom_bodyid, contype, conaffinity, g1, g2)) continue;
-          int t1 = geom_type[g1], t2 = geom_type[g2];
-          if (t1 > t2) { int t = g1; g1 = g2; g2 = t; t = t1; t1 = t2; t2 = t; }
-          const bool ok = (t1 == SG_GEOM_PLANE && (t2 == SG_GEOM_SPHERE || t2 == SG_GEOM_CAPSULE || t2 == SG_GEOM_BOX)) ||
-                          ((t1 == SG_GEOM_SPHERE || t1 == SG_GEOM_CAPSULE || t1 == SG_GEOM_BOX) && t2 == SG_GEOM_BOX);
-          if (!ok) { *err = "unsupported collision pair types " + std::to_string(t1) + "-" + std::to_string(t2); return false; }
-          pairs->push_back(g1);
-          pairs->push_back(g2);
-        }
-  return true;
-}
 
 // bounding tests of collision(): true = the pair goes on to its narrowphase routine.  M1: geom1's orientation (row-major).
 SG_HD bool sgc_broad(int t1, const double* p1, const double* M1, const double* p2, double rb1, double rb2, double margin) {

@@ -33,7 +33,7 @@ static void sgc_from_blob(const void* blob, size_t nbytes, const SgKinHost& K, S
   long long c = 0;
   const long long nb = K.o.nbody, ng = K.o.ngeom;
 #define CF(var, name, dt, want)                                                                                          \
-  const auto* var = (const std::conditional<dt == SG_DT_F64, double, int>::type*)sgk_find(blob, nbytes, name, dt, &c); \
+  const auto* var = (const std::conditional<dt == SG_DT_F64, double, int>::type*)sg_blob_find(blob, nbytes, name, dt, &c); \
   if (!var || c != want) { C->err = std::string("model blob lacks ") + name; return; }
   CF(par, "body_parentid", SG_DT_I32, nb);
   CF(weld, "body_weldid", SG_DT_I32, nb);
@@ -46,7 +46,7 @@ static void sgc_from_blob(const void* blob, size_t nbytes, const SgKinHost& K, S
   CF(gmargin, "geom_margin", SG_DT_F64, ng);
   CF(grb, "geom_rbound", SG_DT_F64, ng);
 #undef CF
-  const int* oi = (const int*)sgk_find(blob, nbytes, "opt_i", SG_DT_I32, &c);
+  const int* oi = (const int*)sg_blob_find(blob, nbytes, "opt_i", SG_DT_I32, &c);
   if (!oi || c < 2) { C->err = "model blob lacks opt_i"; return; }
   C->cap = sgc_cap(oi[1]);
   if (!sgc_build_pairs((int)nb, (int)ng, par, weld, gadr, gnum, gbody, gtype, ctype, caff, &C->pairs, &C->err)) return;

@@ -18,6 +18,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "sg_blob.h"   // sg_blob_find: the one (bounds-checked) reader of the model blob
 #include "sg_plan.h"
 #include "sg_render.h"
 #include "../../include/softgrip_model.h"
@@ -120,33 +121,12 @@ __host__ __device__ inline void sgk_geom(const double* D, const int* I, const Sg
 }
 
 // ---- host: the table from the blob and the plan ----
-static const void* sgk_find(const void* blob, size_t nbytes, const char* name, int dtype, long long* cnt) {
-  const char* base = (const char*)blob;
-  if (nbytes < sizeof(sg_blob_header)) return nullptr;
-  const sg_blob_header* h = (const sg_blob_header*)base;
-  size_t off = sizeof(sg_blob_header);
-  for (uint32_t r = 0; r < h->nrec; r++) {
-    if (off + sizeof(sg_blob_record) > nbytes) return nullptr;
-    const sg_blob_record* rec = (const sg_blob_record*)(base + off);
-    const size_t es = rec->dtype == SG_DT_F64 ? 8 : rec->dtype == SG_DT_I32 ? 4 : 1;
-    size_t nb = (size_t)rec->count * es;
-    nb += (8 - nb % 8) % 8;
-    if (off + sizeof(sg_blob_record) + nb > nbytes) return nullptr;
-    if (strncmp(rec->name, name, 24) == 0 && (int)rec->dtype == dtype) {
-      *cnt = rec->count;
-      return base + off + sizeof(sg_blob_record);
-    }
-    off += sizeof(sg_blob_record) + nb;
-  }
-  return nullptr;
-}
-
 // per body: parent, body_pos, body_quat, its joints; per joint: type, jnt_pos, jnt_axis, qposadr, qpos0; per geom: body, geom_pos, geom_quat
 // (as a matrix), geom_size, geom_type, geom_rbound and a category from the plan; the bodies' depth-level schedule
 static void sgk_build(const void* blob, size_t nbytes, const SgPlan& plan, const SgTreeDev* tree, bool fast, SgKinHost* K) {
   long long nb = 0, nj = 0, ng = 0, nq = 0, c = 0;
 #define KF(var, name, dt, want)                                                               \
-  const auto* var = (const std::conditional<dt == SG_DT_F64, double, int>::type*)sgk_find(blob, nbytes, name, dt, &c); \
+  const auto* var = (const std::conditional<dt == SG_DT_F64, double, int>::type*)sg_blob_find(blob, nbytes, name, dt, &c); \
   if (!var || (want >= 0 && c != want)) { K->err = std::string("model blob lacks ") + name; return; }
   KF(par, "body_parentid", SG_DT_I32, -1);
   nb = c;
@@ -169,7 +149,7 @@ static void sgk_build(const void* blob, size_t nbytes, const SgPlan& plan, const
   KF(grb, "geom_rbound", SG_DT_F64, ng);
 #undef KF
   long long ca = 0;
-  const int* qadr = (const int*)sgk_find(blob, nbytes, "jnt_qposadr", SG_DT_I32, &ca);   // (only blobs with a free joint carry it)
+  const int* qadr = (const int*)sg_blob_find(blob, nbytes, "jnt_qposadr", SG_DT_I32, &ca);   // (only blobs with a free joint carry it)
   if (qadr && ca != nj) qadr = nullptr;
   if (nb < 1 || nb > 1024) { K->err = "the kinematic tree has more than 1024 bodies"; return; }
   // checks: parents before children, joint / position addresses in range
