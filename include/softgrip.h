@@ -174,6 +174,30 @@ int sg_model_default_camera(const sg_model* m, double cam[7]);
 int sg_render(sg_batch* b, const double* cam, const int32_t* env_ids, int n_ids, int width, int height,
               uint8_t* rgba, float* depth, int32_t* segid, void* stream);
 
+/* ---- the soft object's skin: what a camera sees of a <composite> with a <skin> child is a surface, not its collision capsules.
+ * A skin is triangles bound to bodies, held by the model next to its kinematics table and NOT part of the blob: nvert <= 256 vertices,
+ * each with a body id vert_body[v] and a position vert_pos[v][3] in that body's frame; nface <= 512 triangles face[f][3] of vertex
+ * indices, front side counter-clockwise; one rgba[4] (alpha is ignored: output alpha stays 255).  Host pointers, no device needed.
+ * The model of a scene compiled from MJCF carries the composite's skin (one vertex per shell element at (0, 0, inflate), the six sides'
+ * quads split in two; built as at subgrid = 0, textures and materials are not drawn); a model made from a blob has none until it is set.
+ * Setting a skin validates before it stores anything: SG_ERR_INVALID for NULL arrays with positive counts, a body id outside
+ * [0, nbody), a face index outside [0, nvert), a face that repeats an index, non-finite positions or rgba; SG_ERR_MODEL beyond the
+ * limits; a rejected call leaves the old skin in place.  nvert == 0 removes the skin.  Batches of the model pick a new skin up at
+ * their next render.  Reading a skin: the sizes always, the arrays where the pointer is not NULL. */
+int sg_model_set_skin(sg_model* m, int nvert, const int32_t* vert_body, const double* vert_pos,
+                      int nface, const int32_t* face, const float rgba[4]);
+int sg_model_skin(const sg_model* m, int* nvert, int* nface, int32_t* vert_body, double* vert_pos,
+                  int32_t* face, float* rgba);
+
+/* The renderer with flags.  flags == 0: exactly what the plain call does (same kernels, same bits).  SG_RENDER_SKIN on a model with a skin:
+ * the skin is drawn and the geoms of the bodies its vertices are bound to are not; everything else is drawn as before (the
+ * composite's centre sphere too).  Skin pixels report segid == ngeom.  Front faces only; a ray through a shared edge or vertex of two
+ * triangles hits one of them; of equal distances the smaller face index wins and a geom wins against a triangle.  The shading normal
+ * is interpolated from area-weighted vertex normals.  With the flag and no skin: the plain call.  Unknown flag bits: SG_ERR_INVALID. */
+enum { SG_RENDER_SKIN = 1 };
+int sg_render_ex(sg_batch* b, const double* cam, const int32_t* env_ids, int n_ids, int width, int height,
+                 int flags, uint8_t* rgba, float* depth, int32_t* segid, void* stream);
+
 /* ---- contact read-out: replaces the loop `for i in range(data.ncon): data.contact[i]` (manenv.py:65-85).
  * mj_collision for the listed envs at the batch's CURRENT qpos -- what sim.forward(); sim.data.contact[:ncon] would hold: the oracle's
  * candidate pairs, order, bounding tests, narrowphase and cap.  Geometry only (no forces, no solver parameters).  Device pointers, any

@@ -96,7 +96,7 @@ def log_into_file(args):
     name = args.data_name if world == 1 else "%s.rank%d" % (args.data_name, rank)
     if getattr(args, "render_dir", None):   # frames of the squeeze steps (the reference's env.render(), :49); no part of the data
         env_spec.update(render_dir=os.path.join(args.render_dir, name), render_envs=range(max(0, min(args.render_envs, getattr(args, "n_envs", 1)))),
-                        render_size=tuple(args.render_size), render_every=args.render_every)
+                        render_size=tuple(args.render_size), render_every=args.render_every, render_skin=bool(getattr(args, "render_skin", False)))
     env = ManEnv(**env_spec)
     n = env.n_envs
     lo, hi = stiffness_bin(rank, world) if world > 1 else (300, 1400)   # stiffness sweep sharded by bin (BASELINE.json configs[3])
@@ -247,6 +247,8 @@ def make_parser():
                         help="write PNG frames of the squeeze steps to DIR/<data-name>[.rankR]/s<scene>_b<batch>_e<env>_t<step>.png (headless renderer)")
     parser.add_argument('--render-envs', type=int, default=1, help="with --render-dir: frames of the first N envs of a batch")
     parser.add_argument('--render-size', type=int, nargs=2, default=[320, 240], metavar=("W", "H"), help="with --render-dir: frame size")
+    parser.add_argument('--render-skin', action='store_true',
+                        help="with --render-dir: draw the soft object as its skin (a surface) and not as its element capsules")
     parser.add_argument('--render-every', type=int, default=1, help="with --render-dir: a frame every K-th squeeze step")
     parser.add_argument('--force-device', type=int, default=-1, help="testing only: put every rank on this GPU")
     return parser

@@ -68,6 +68,7 @@ struct sg_model {
   long long tree_cws = 0;    // sgt::cws_doubles: each walks lds_carve, so once per model)
   SgKinHost kin;    // kinematics table of sg_get_poses / sg_render (sg_kin.hip)
   SgConHost con;    // candidate pairs, margins and bounding radii of sg_get_contacts (sg_contacts.hip)
+  SgSkinHost skin;  // the composite's skin (sg_skin.h; nvert == 0: none): sg_model_set_skin, drawn by sg_render_ex
 };
 
 // device tables and work space of the tree pipeline (sg_tree.h), allocated when the pipeline is first selected
@@ -116,6 +117,12 @@ struct sg_batch {
   int* kin_i = nullptr;
   SgScratch<int> kin_ids;    // the listed env ids on the device
   SgScratch<float> rrecs;    // [n_ids][ngeom][SGR_REC] fp32 geom records of the last sg_render
+  // the skin (sg_render_ex): tables uploaded at first use and again when the model's skin version has moved
+  SgArena skin_mem;
+  SgSkinDev skin_dev = {};
+  unsigned skin_version = 0;   // the version skin_dev holds (0: none; versions start at 1)
+  SgScratch<double> skin_xpos, skin_xquat;   // [n_ids][nbody][3 | 4] body poses of the last skin render
+  SgScratch<float> skin_vrec;                // [n_ids][nvert][SGR_VREC] vertex records of the last skin render
   // contact read-out (sg_contacts.hip), allocated at first use
   int* con_pairs = nullptr;
   double* con_gaux = nullptr;
@@ -237,13 +244,27 @@ int sg_mjcf_compile(const char* xml_path, int flags, void** blob, size_t* nbytes
 void sg_blob_free(void* blob) { free(blob); }
 
 int sg_model_compile(const char* xml_path, int flags, sg_model** out) {
-  void* blob = nullptr;
-  size_t nbytes = 0;
-  int rc = sg_mjcf_compile(xml_path, flags, &blob, &nbytes);
-  if (rc != SG_OK) return rc;
-  rc = sg_model_create(blob, nbytes, out);
-  free(blob);
-  return rc;
+  if (!xml_path || !out) return fail(SG_ERR_INVALID, "sg_model_compile: null argument");
+  std::string blob, err;
+  SgSkinSpec spec;
+  if (!sg_mjcf_compile_file(xml_path, !(flags & SG_COMPILE_NO_NEIGHBORS), (flags & SG_COMPILE_IMPLICIT_TENDON_DAMPER) != 0, &blob, &err, &spec))
+    return fail(SG_ERR_MODEL, "sg_mjcf_compile: " + err);
+  int rc = sg_model_create(blob.data(), blob.size(), out);
+  if (rc != SG_OK || !spec.present) return rc;
+  // the composite's <skin>: built from the body names of the blob, as mjcf.py Model.composite_skin() does
+  long long c = 0;
+  const char* names = (const char*)sg_blob_find(blob.data(), blob.size(), "names", SG_DT_U8, &c);
+  std::vector<std::string> body_names(1);
+  for (long long i = 0; names && i < c && names[i] != '\n'; i++) {
+    if (names[i] == '|') body_names.emplace_back();
+    else body_names.back().push_back(names[i]);
+  }
+  SgSkinHost S;
+  // (names that do not form a shell within the limits: the model has no skin, as mjcf.py's Model.skin = None -- the scene still compiles)
+  if (sg_composite_skin(body_names, &spec.prefix, spec.inflate, spec.rgba, &S) &&
+      sg_model_set_skin(*out, S.nvert, S.vert_body.data(), S.vert_pos.data(), S.nface, S.face.data(), S.rgba) != SG_OK)
+    (void)sg_model_set_skin(*out, 0, nullptr, nullptr, 0, nullptr, nullptr);
+  return SG_OK;
 }
 int sg_model_nq(const sg_model* m) { return m->plan.h.nq; }
 int sg_model_nv(const sg_model* m) { return m->plan.h.nv; }
@@ -753,17 +774,25 @@ int sg_get_poses(sg_batch* b, const int32_t* env_ids, int n_ids, double* xpos, d
   return launch_kin(b, dids, n_ids, xpos, xquat, geom_xpos, geom_xmat, nullptr, nullptr, s);
 }
 
-int sg_render(sg_batch* b, const double* cam, const int32_t* env_ids, int n_ids, int width, int height, uint8_t* rgba, float* depth, int32_t* segid,
-              void* stream) {
-  if (!b || !cam) return fail(SG_ERR_INVALID, "sg_render: null batch or camera");
-  if (width <= 0 || height <= 0 || width > 16384 || height > 16384) return fail(SG_ERR_INVALID, "sg_render: image size out of range (1 .. 16384)");
+// the argument and model checks both render entry points share (before anything touches the device)
+static int render_check(const char* fn, const sg_batch* b, const double* cam, int width, int height) {
+  const std::string f = std::string(fn) + ": ";
+  if (!b || !cam) return fail(SG_ERR_INVALID, f + "null batch or camera");
+  if (width <= 0 || height <= 0 || width > 16384 || height > 16384) return fail(SG_ERR_INVALID, f + "image size out of range (1 .. 16384)");
   for (int c = 0; c < 7; c++)
-    if (!std::isfinite(cam[c])) return fail(SG_ERR_INVALID, "sg_render: camera values must be finite");
-  if (!(cam[3] > 0) || !(cam[6] > 0 && cam[6] < 180)) return fail(SG_ERR_INVALID, "sg_render: camera distance must be > 0 and fovy in (0, 180)");
+    if (!std::isfinite(cam[c])) return fail(SG_ERR_INVALID, f + "camera values must be finite");
+  if (!(cam[3] > 0) || !(cam[6] > 0 && cam[6] < 180)) return fail(SG_ERR_INVALID, f + "camera distance must be > 0 and fovy in (0, 180)");
   const SgKinHost& K = b->m->kin;
   if (K.ok && K.bad_type >= 0)
-    return fail(SG_ERR_MODEL, "sg_render: geom type " + std::to_string(K.bad_type) + " has no ray intersection (plane, sphere, capsule and box only)");
-  if (K.ok && K.o.ngeom > SGR_MAXGEOM) return fail(SG_ERR_MODEL, "sg_render: more than " + std::to_string(SGR_MAXGEOM) + " geoms");
+    return fail(SG_ERR_MODEL, f + "geom type " + std::to_string(K.bad_type) + " has no ray intersection (plane, sphere, capsule and box only)");
+  if (K.ok && K.o.ngeom > SGR_MAXGEOM) return fail(SG_ERR_MODEL, f + "more than " + std::to_string(SGR_MAXGEOM) + " geoms");
+  return SG_OK;
+}
+
+int sg_render(sg_batch* b, const double* cam, const int32_t* env_ids, int n_ids, int width, int height, uint8_t* rgba, float* depth, int32_t* segid,
+              void* stream) {
+  if (int rc = render_check("sg_render", b, cam, width, height)) return rc;
+  const SgKinHost& K = b->m->kin;
   hipStream_t s = (hipStream_t)stream;
   const int* dids = nullptr;
   if (int rc = kin_prepare(b, "sg_render", env_ids, n_ids, s, &dids)) return rc;
@@ -779,6 +808,125 @@ int sg_render(sg_batch* b, const double* cam, const int32_t* env_ids, int n_ids,
   if (!rgba && !depth && !segid) return SG_OK;
   if ((long long)a.ntiles * n_ids > 0x7fffffffll) return fail(SG_ERR_INVALID, "sg_render: too many tiles x envs for one launch");
   hipLaunchKernelGGL(sg_render_kernel, dim3((unsigned)(a.ntiles * n_ids)), dim3(256), 0, s, a);
+  HIPCHK(hipGetLastError());
+  return SG_OK;
+}
+
+// ---- the skin (sg_skin.h, sg_kin.hip) ----
+int sg_model_set_skin(sg_model* m, int nvert, const int32_t* vert_body, const double* vert_pos, int nface, const int32_t* face, const float* rgba) {
+  if (!m) return fail(SG_ERR_INVALID, "sg_model_set_skin: null model");
+  if (nvert < 0 || nface < 0) return fail(SG_ERR_INVALID, "sg_model_set_skin: negative count");
+  if (nvert == 0) {   // removes the skin
+    m->skin.nvert = m->skin.nface = 0;
+    m->skin.vert_body.clear(); m->skin.vert_pos.clear(); m->skin.face.clear();
+    m->skin.version++;
+    return SG_OK;
+  }
+  if (!m->kin.ok) return fail(SG_ERR_MODEL, "sg_model_set_skin: " + m->kin.err);
+  if (nvert > SGR_MAXVERT || nface > SGR_MAXFACE)
+    return fail(SG_ERR_MODEL, "sg_model_set_skin: more than " + std::to_string(SGR_MAXVERT) + " vertices or " + std::to_string(SGR_MAXFACE) + " faces");
+  if (!vert_body || !vert_pos || !rgba || (nface > 0 && !face)) return fail(SG_ERR_INVALID, "sg_model_set_skin: null array with a positive count");
+  for (int v = 0; v < nvert; v++) {
+    if (vert_body[v] < 0 || vert_body[v] >= m->kin.o.nbody)
+      return fail(SG_ERR_INVALID, "sg_model_set_skin: vertex " + std::to_string(v) + " is bound to body " + std::to_string(vert_body[v]) + ", outside [0, nbody)");
+    for (int c = 0; c < 3; c++)
+      if (!std::isfinite(vert_pos[3 * v + c])) return fail(SG_ERR_INVALID, "sg_model_set_skin: vertex positions must be finite");
+  }
+  for (int f = 0; f < nface; f++) {
+    const int32_t* q = face + 3 * f;
+    for (int c = 0; c < 3; c++)
+      if (q[c] < 0 || q[c] >= nvert) return fail(SG_ERR_INVALID, "sg_model_set_skin: face " + std::to_string(f) + " has a vertex index outside [0, nvert)");
+    if (q[0] == q[1] || q[1] == q[2] || q[0] == q[2]) return fail(SG_ERR_INVALID, "sg_model_set_skin: face " + std::to_string(f) + " repeats a vertex");
+  }
+  for (int c = 0; c < 4; c++)
+    if (!std::isfinite(rgba[c])) return fail(SG_ERR_INVALID, "sg_model_set_skin: rgba must be finite");
+  SgSkinHost& S = m->skin;
+  S.nvert = nvert; S.nface = nface;
+  S.vert_body.assign(vert_body, vert_body + nvert);
+  S.vert_pos.assign(vert_pos, vert_pos + 3 * (size_t)nvert);
+  S.face.assign(face, face + 3 * (size_t)nface);
+  for (int c = 0; c < 4; c++) S.rgba[c] = rgba[c];
+  S.version++;
+  return SG_OK;
+}
+
+int sg_model_skin(const sg_model* m, int* nvert, int* nface, int32_t* vert_body, double* vert_pos, int32_t* face, float* rgba) {
+  if (!m) return fail(SG_ERR_INVALID, "sg_model_skin: null model");
+  const SgSkinHost& S = m->skin;
+  if (nvert) *nvert = S.nvert;
+  if (nface) *nface = S.nface;
+  if (vert_body) std::copy(S.vert_body.begin(), S.vert_body.end(), vert_body);
+  if (vert_pos) std::copy(S.vert_pos.begin(), S.vert_pos.end(), vert_pos);
+  if (face) std::copy(S.face.begin(), S.face.end(), face);
+  if (rgba)
+    for (int c = 0; c < 4; c++) rgba[c] = S.rgba[c];
+  return SG_OK;
+}
+
+// the skin's tables on the batch's device, uploaded again when the model's skin has changed since (an earlier skin render, on whatever
+// stream it went out, may still read the old ones: the device is waited for first -- once per sg_model_set_skin, not per render)
+static int skin_prepare(sg_batch* b) {
+  const SgSkinHost& S = b->m->skin;
+  if (b->skin_version == S.version) return SG_OK;
+  const SgKinHost& K = b->m->kin;
+  SgSkinTables T;
+  sg_skin_tables(S, K.ints.data() + K.o.gbody, K.o.ngeom, K.o.nbody, &T);
+  HIPCHK(hipDeviceSynchronize());
+  b->skin_version = 0;
+  b->skin_mem.release();
+  SgArena& A = b->skin_mem;
+  int *vb = nullptr, *as = nullptr, *ad = nullptr, *hid = nullptr;
+  double* vp = nullptr;
+  uint32_t* fc = nullptr;
+  if (!(A.upload(&vb, S.vert_body) && A.upload(&vp, S.vert_pos) && A.upload(&fc, T.faces) && A.upload(&as, T.adj_start) && A.upload(&ad, T.adj) &&
+        A.upload(&hid, T.hidden))) {
+    const bool nomem = A.nomem;
+    A.release();
+    return devmem_fail(nomem, "sg_render_ex (skin tables)");
+  }
+  SgSkinDev& d = b->skin_dev;
+  d.vert_body = vb; d.vert_pos = vp; d.faces = fc; d.adj_start = as; d.adj = ad; d.hidden = hid;
+  d.nvert = S.nvert; d.nface = S.nface;
+  for (int c = 0; c < 3; c++) d.rgb[c] = S.rgba[c];
+  b->skin_version = S.version;
+  return SG_OK;
+}
+
+int sg_render_ex(sg_batch* b, const double* cam, const int32_t* env_ids, int n_ids, int width, int height, int flags, uint8_t* rgba, float* depth,
+                 int32_t* segid, void* stream) {
+  if (flags & ~SG_RENDER_SKIN) return fail(SG_ERR_INVALID, "sg_render_ex: unknown flag bits");
+  if (!b || !cam) return fail(SG_ERR_INVALID, "sg_render_ex: null batch or camera");
+  if (!(flags & SG_RENDER_SKIN) || b->m->skin.nvert == 0) return sg_render(b, cam, env_ids, n_ids, width, height, rgba, depth, segid, stream);
+  if (int rc = render_check("sg_render_ex", b, cam, width, height)) return rc;
+  const SgKinHost& K = b->m->kin;
+  const SgSkinHost& S = b->m->skin;
+  hipStream_t s = (hipStream_t)stream;
+  const int* dids = nullptr;
+  if (int rc = kin_prepare(b, "sg_render_ex", env_ids, n_ids, s, &dids)) return rc;
+  if (int rc = skin_prepare(b)) return rc;
+  const size_t nb = K.o.nbody;
+  if (!b->rrecs.reserve((size_t)n_ids * K.o.ngeom * SGR_REC, s)) return devmem_fail(b->rrecs.nomem, "sg_render_ex (geom records)");
+  if (!b->skin_xpos.reserve((size_t)n_ids * nb * 3, s)) return devmem_fail(b->skin_xpos.nomem, "sg_render_ex (body poses)");
+  if (!b->skin_xquat.reserve((size_t)n_ids * nb * 4, s)) return devmem_fail(b->skin_xquat.nomem, "sg_render_ex (body poses)");
+  if (!b->skin_vrec.reserve((size_t)n_ids * S.nvert * SGR_VREC, s)) return devmem_fail(b->skin_vrec.nomem, "sg_render_ex (vertex records)");
+  SgSkinRenderArgs A;
+  SgRenderArgs& a = A.r;
+  double eye[3];
+  sgr_camera(cam, width, height, eye, &a.cam);
+  if (int rc = launch_kin(b, dids, n_ids, b->skin_xpos.p, b->skin_xquat.p, nullptr, nullptr, b->rrecs.p, eye, s)) return rc;
+  SgSkinVertArgs V;
+  V.s = b->skin_dev; V.xpos = b->skin_xpos.p; V.xquat = b->skin_xquat.p; V.nbody = K.o.nbody; V.vrec = b->skin_vrec.p;
+  for (int c = 0; c < 3; c++) V.eye[c] = eye[c];
+  hipLaunchKernelGGL(sg_skin_vert_kernel, dim3(n_ids), dim3(256), 0, s, V);
+  HIPCHK(hipGetLastError());
+  a.recs = b->rrecs.p; a.ngeom = K.o.ngeom; a.n_ids = n_ids;
+  a.tiles_x = (width + SGR_TILE - 1) / SGR_TILE;
+  a.ntiles = a.tiles_x * ((height + SGR_TILE - 1) / SGR_TILE);
+  a.rgba = rgba; a.depth = depth; a.segid = segid;
+  A.s = b->skin_dev; A.vrec = b->skin_vrec.p;
+  if (!rgba && !depth && !segid) return SG_OK;
+  if ((long long)a.ntiles * n_ids > 0x7fffffffll) return fail(SG_ERR_INVALID, "sg_render_ex: too many tiles x envs for one launch");
+  hipLaunchKernelGGL(sg_rskin_kernel, dim3((unsigned)(a.ntiles * n_ids)), dim3(256), 0, s, A);
   HIPCHK(hipGetLastError());
   return SG_OK;
 }

@@ -21,6 +21,7 @@
 #include "sg_blob.h"   // sg_blob_find: the one (bounds-checked) reader of the model blob
 #include "sg_plan.h"
 #include "sg_render.h"
+#include "sg_skin.h"
 #include "../../include/softgrip_model.h"
 
 // ---- the kinematics table: one double and one int array, sections at the offsets below ----
@@ -379,6 +380,148 @@ __global__ __launch_bounds__(256) void sg_render_kernel(SgRenderArgs a) {
     float d[3];
     sgr_ray(a.cam, i, j, d);
     h = sgr_trace(recs, slist, n, a.cam, d);
+  }
+  const size_t px = ((size_t)k * H + j) * W + i;
+  if (a.rgba) ((uchar4*)a.rgba)[px] = make_uchar4(h.rgba[0], h.rgba[1], h.rgba[2], h.rgba[3]);
+  if (a.depth) a.depth[px] = h.depth;
+  if (a.segid) a.segid[px] = h.geom;
+}
+
+// ---- the skin (sg_render_ex with SG_RENDER_SKIN): triangles bound to bodies, sg_skin.h ----
+//   sg_skin_vert_kernel  256 lanes = one listed env, a lane per vertex: world position from the body poses sg_kin_kernel wrote (fp64, the
+//                        eye subtracted before the cast), positions into LDS, then the vertex normal over the host-built vertex -> face
+//                        adjacency list.  Writes [n_ids][nvert] records of 2 x float4.  Once per env and not per tile: a 640 x 480 image
+//                        has 1 200 tiles per env.  A NaN env writes NaN.
+//   sg_rskin_kernel      sg_render_kernel's sibling (that kernel keeps its code, LDS and registers): additionally stages the env's vertex
+//                        positions (4 KB) and the faces (2 KB) in LDS, leaves the geoms the skin replaces out of the culled list, culls the
+//                        triangles' bounding spheres against the tile cone into a second LDS list (1 KB; 432 faces = two passes of 256
+//                        lanes), traces geoms then triangles and reads the normals of the hit's three vertices only.
+struct SgSkinDev {
+  const int* vert_body;      // [nvert]
+  const double* vert_pos;    // [nvert][3]
+  const uint32_t* faces;     // [nface] sgr_pack_face
+  const int* adj_start;      // [nvert + 1]
+  const int* adj;            // [3 nface]
+  const int* hidden;         // [ngeom] 1: a geom the skin replaces
+  int nvert, nface;
+  float rgb[3];
+};
+
+struct SgSkinVertArgs {
+  SgSkinDev s;
+  const double *xpos, *xquat;   // [n_ids][nbody][3 | 4]
+  int nbody;
+  double eye[3];
+  float* vrec;                  // [n_ids][nvert][SGR_VREC]
+};
+
+__global__ __launch_bounds__(256) void sg_skin_vert_kernel(SgSkinVertArgs a) {
+  __shared__ float4 spos[SGR_MAXVERT];
+  const int k = blockIdx.x, v = threadIdx.x;
+  if (v < a.s.nvert) {
+    const size_t kb = (size_t)k * a.nbody + a.s.vert_body[v];
+    double R[9], t[3];
+    sgk_quat_mat(R, a.xquat + kb * 4);
+    sgk_mv(t, R, a.s.vert_pos + 3 * v);
+    const double* bp = a.xpos + kb * 3;
+    spos[v] = make_float4((float)(bp[0] + t[0] - a.eye[0]), (float)(bp[1] + t[1] - a.eye[1]), (float)(bp[2] + t[2] - a.eye[2]), 0.0f);
+  }
+  __syncthreads();
+  if (v < a.s.nvert) {
+    float n[3];
+    sgr_vertex_normal(v, (const float*)spos, a.s.faces, a.s.adj_start, a.s.adj, n);
+    float4* dst = (float4*)(a.vrec + ((size_t)k * a.s.nvert + v) * SGR_VREC);
+    dst[0] = spos[v];
+    dst[1] = make_float4(n[0], n[1], n[2], 0.0f);
+  }
+}
+
+struct SgSkinRenderArgs {
+  SgRenderArgs r;
+  SgSkinDev s;
+  const float* vrec;   // [n_ids][nvert][SGR_VREC]
+};
+
+__global__ __launch_bounds__(256) void sg_rskin_kernel(SgSkinRenderArgs A) {
+  __shared__ float4 srec[SGR_MAXGEOM * SGR_REC / 4];
+  __shared__ float4 svert[SGR_MAXVERT];
+  __shared__ uint32_t sface[SGR_MAXFACE];
+  __shared__ unsigned short slist[SGR_MAXGEOM];
+  __shared__ unsigned short sflist[SGR_MAXFACE];
+  __shared__ int swc[4];
+  const SgRenderArgs& a = A.r;
+  const int tid = threadIdx.x;
+  const int k = blockIdx.x / a.ntiles, tile = blockIdx.x - k * a.ntiles;
+  const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+  const int W = a.cam.width, H = a.cam.height;
+  const int nvert = A.s.nvert, nface = A.s.nface;
+  // 1. stage the env's records, its vertex positions and the faces (a NaN / inf: the env renders as background)
+  const float4* src = (const float4*)(a.recs + (size_t)k * a.ngeom * SGR_REC);
+  bool bad = false;
+  for (int i = tid; i < a.ngeom * (SGR_REC / 4); i += 256) {
+    const float4 v = src[i];
+    bad |= !isfinite(v.x) || !isfinite(v.y) || !isfinite(v.z) || ((i & 3) != 3 && !isfinite(v.w));
+    srec[i] = v;
+  }
+  const float* vrec = A.vrec + (size_t)k * nvert * SGR_VREC;
+  if (tid < nvert) {
+    const float4 v = ((const float4*)vrec)[2 * tid];
+    bad |= !isfinite(v.x) || !isfinite(v.y) || !isfinite(v.z);
+    svert[tid] = v;
+  }
+  for (int i = tid; i < nface; i += 256) sface[i] = A.s.faces[i];
+  bad = __syncthreads_or(bad);
+  const float* recs = (const float*)srec;
+  const float* vpos = (const float*)svert;
+  // 2. cull against the tile's ray cone: the geoms the skin does not replace, then the triangles
+  int n = 0, nf = 0;
+  if (!bad) {
+    const int i0 = tx * SGR_TILE, j0 = ty * SGR_TILE, i1 = min(i0 + SGR_TILE - 1, W - 1), j1 = min(j0 + SGR_TILE - 1, H - 1);
+    float d0[3], d1[3], d2[3], d3[3], axis[3], cs, sn;
+    sgr_ray(a.cam, i0, j0, d0); sgr_ray(a.cam, i1, j0, d1); sgr_ray(a.cam, i0, j1, d2); sgr_ray(a.cam, i1, j1, d3);
+    sgr_tile_cone(d0, d1, d2, d3, axis, &cs, &sn);
+    const int w = tid >> 6, lane = tid & 63;
+    for (int base = 0; base < a.ngeom; base += 256) {
+      const int g = base + tid;
+      const bool keep = g < a.ngeom && !A.s.hidden[g] && sgr_cone_keep(recs + SGR_REC * g, axis, cs, sn);
+      const unsigned long long m = __ballot(keep);
+      if (lane == 0) swc[w] = __popcll(m);
+      __syncthreads();
+      int off = n, tot = 0;
+      for (int q = 0; q < 4; q++) { off += q < w ? swc[q] : 0; tot += swc[q]; }
+      if (keep) slist[off + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)g;
+      n += tot;
+      __syncthreads();
+    }
+    for (int base = 0; base < nface; base += 256) {
+      const int f = base + tid;
+      bool keep = false;
+      if (f < nface) {
+        const uint32_t fw = sface[f];
+        keep = sgr_tri_cone_keep(vpos + 4 * (fw & 0xFF), vpos + 4 * ((fw >> 8) & 0xFF), vpos + 4 * ((fw >> 16) & 0xFF), axis, cs, sn);
+      }
+      const unsigned long long m = __ballot(keep);
+      if (lane == 0) swc[w] = __popcll(m);
+      __syncthreads();
+      int off = nf, tot = 0;
+      for (int q = 0; q < 4; q++) { off += q < w ? swc[q] : 0; tot += swc[q]; }
+      if (keep) sflist[off + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)f;   // (ascending face index: ties go to the smaller one)
+      nf += tot;
+      __syncthreads();
+    }
+  }
+  // 3. a lane per pixel
+  const int i = tx * SGR_TILE + (tid & (SGR_TILE - 1)), j = ty * SGR_TILE + (tid >> 4);
+  if (i >= W || j >= H) return;
+  SgrHit h;
+  if (bad) {
+    h.depth = INFINITY; h.geom = -1;
+    sgr_background(h.rgba);
+  } else {
+    float d[3];
+    int face;
+    sgr_ray(a.cam, i, j, d);
+    h = sgr_trace_skin(recs, slist, n, vpos, sface, sflist, nf, vrec, A.s.rgb, a.ngeom, a.cam, d, &face);
   }
   const size_t px = ((size_t)k * H + j) * W + i;
   if (a.rgba) ((uchar4*)a.rgba)[px] = make_uchar4(h.rgba[0], h.rgba[1], h.rgba[2], h.rgba[3]);

@@ -366,6 +366,7 @@ struct Compiler {
   double timestep = 0.002, gravity[3] = {0, 0, -9.81}, tolerance = 1e-8, impratio = 1;
   int iterations = 100, nconmax = -1, njmax = -1;
   std::string solver = "Newton", cone = "pyramidal";
+  SgSkinSpec skin;
 
   Geom make_geom(const AttrMap& at, const std::string& name) {
     Geom g;
@@ -514,7 +515,17 @@ struct Compiler {
             (isj ? jattr : tattr)[a.first] = a.second;
           }
         }
-      } else if (c.tag == "skin") {  // render-only
+      } else if (c.tag == "skin") {  // render-only: no part of the blob (sg_skin.h); the first skinned composite's is kept
+        if (!skin.present) {
+          skin.present = true;
+          skin.prefix = prefix;
+          if (const std::string* s = c.get("inflate")) skin.inflate = parse_vec(*s)[0];
+          if (const std::string* s = c.get("rgba")) {
+            auto v = parse_vec(*s);
+            if (v.size() != 4) fail("skin rgba needs 4 numbers");
+            for (int k = 0; k < 4; k++) skin.rgba[k] = (float)v[k];
+          }
+        }
       } else {
         fail("unsupported composite child <" + c.tag + ">");
       }
@@ -1160,11 +1171,13 @@ std::string finalize(Compiler& C, bool implicit_tendon_damping) {
 
 }  // namespace
 
-bool sg_mjcf_compile_file(const char* xml_path, bool composite_neighbors, bool implicit_tendon_damping, std::string* blob, std::string* err) {
+bool sg_mjcf_compile_file(const char* xml_path, bool composite_neighbors, bool implicit_tendon_damping, std::string* blob, std::string* err,
+                          SgSkinSpec* skin) {
   try {
     Compiler C;
     C.run(xml_path, composite_neighbors);
     *blob = finalize(C, implicit_tendon_damping);
+    if (skin) *skin = C.skin;
     return true;
   } catch (const Fail& f) {
     *err = f.msg;

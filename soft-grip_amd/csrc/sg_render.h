@@ -259,3 +259,174 @@ SGR_HD SgrHit sgr_trace(const float* recs, const IdxT* ids, int nids, const SgrC
   }
   return r;
 }
+
+// ---- the skin: triangles bound to bodies (sg_render_ex with SG_RENDER_SKIN) ----
+// Vertices are positions relative to the eye in fp32 (the eye is subtracted in fp64 first, as sgr_make_record does), one float4 each; a face
+// is three vertex indices in one 32-bit word (nvert <= 256: a byte each), front side counter-clockwise.  Rules both casters share:
+//   * the ray starts at 0, so the edge value of edge (p, q) is d . (p x q).  It is computed with the endpoint of SMALLER VERTEX INDEX
+//     first and with an exact sign (sgr_edge): two triangles that share an edge get bit-identical magnitudes.  Per triangle
+//     (a, b, c) it is oriented as E_ab = d . (b x a); the ray hits when all three are >= 0 -- zero counts as inside, so no ray slips
+//     between two triangles that share an edge;
+//   * front faces only: t = (n . a) / (n . d) with the face normal n = (b - a) x (c - a), and n . d < 0, t > 0;
+//   * of equal t the smaller face index wins; against a geom at equal t the geom wins;
+//   * shading: the fixed formula with the skin's rgb as albedo and the normal = the barycentric blend (weights E_bc, E_ca, E_ab) of the
+//     vertex normals, normalised.  A vertex normal is the normalised sum of the unnormalised n of its faces (area weighting); where that
+//     sum is zero the hit face's normal stands in for it, and so it does for a blend that comes out zero.
+#define SGR_MAXVERT 256
+#define SGR_MAXFACE 512
+#define SGR_VREC 8        // floats per vertex record: position - eye (xyz, 0), normal (xyz, 0)
+
+SGR_HD uint32_t sgr_pack_face(int a, int b, int c) { return (uint32_t)a | ((uint32_t)b << 8) | ((uint32_t)c << 16); }
+
+// The edge value is taken in the ray's own frame: with u, w orthonormal and u x w = d, d . (p x q) = (p.u)(q.w) - (p.w)(q.u).  The two
+// coordinates of a vertex are fp32 numbers that depend on the ray and the vertex alone (explicit fmaf in a fixed order: every triangle
+// that uses the vertex gets the same bits); the two products of such numbers are exact in fp64 and their difference is rounded once,
+// whether or not the compiler contracts it.  So the sign of every edge value is the exact sign for the projected points: two triangles
+// that share an edge get bit-identical magnitudes, and the fan of triangles around a vertex leaves no gap for a ray aimed at it either
+// (with d . (p x q) taken in fp32 from the 3-D coordinates, rounding noise of the size of the value itself decides the signs there).
+struct SgrRayFrame { float u[3], w[3]; };
+
+SGR_HD void sgr_ray_frame(const float* d, SgrRayFrame* fr) {
+  const float ax = fabsf(d[0]), ay = fabsf(d[1]), az = fabsf(d[2]);
+  float e[3] = {0.0f, 0.0f, 0.0f};
+  e[ax <= ay && ax <= az ? 0 : (ay <= az ? 1 : 2)] = 1.0f;   // the axis d leans on least
+  float u[3] = {d[1] * e[2] - d[2] * e[1], d[2] * e[0] - d[0] * e[2], d[0] * e[1] - d[1] * e[0]};
+  const float il = 1.0f / sqrtf(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+  for (int k = 0; k < 3; k++) fr->u[k] = u[k] * il;
+  fr->w[0] = d[1] * fr->u[2] - d[2] * fr->u[1]; fr->w[1] = d[2] * fr->u[0] - d[0] * fr->u[2]; fr->w[2] = d[0] * fr->u[1] - d[1] * fr->u[0];
+}
+
+SGR_HD float sgr_dot_fixed(const float* p, const float* a) { return fmaf(p[0], a[0], fmaf(p[1], a[1], p[2] * a[2])); }
+
+// d . (p x q)
+SGR_HD double sgr_edge(const SgrRayFrame& fr, const float* p, const float* q) {
+  const double pu = sgr_dot_fixed(p, fr.u), pw = sgr_dot_fixed(p, fr.w), qu = sgr_dot_fixed(q, fr.u), qw = sgr_dot_fixed(q, fr.w);
+  return pu * qw - pw * qu;
+}
+
+// oriented edge value E_pq = d . (q x p) of the triangle's edge p -> q (vertex indices ip, iq): the endpoint of smaller index first
+SGR_HD double sgr_edge_oriented(const SgrRayFrame& fr, const float* p, int ip, const float* q, int iq) {
+  return ip < iq ? -sgr_edge(fr, p, q) : sgr_edge(fr, q, p);
+}
+
+// unnormalised face normal (b - a) x (c - a)
+SGR_HD void sgr_face_normal(const float* a, const float* b, const float* c, float* n) {
+  const float u[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, v[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+  n[0] = u[1] * v[2] - u[2] * v[1]; n[1] = u[2] * v[0] - u[0] * v[2]; n[2] = u[0] * v[1] - u[1] * v[0];
+}
+
+// ray (origin 0, unit d) against the triangle: distance (INFINITY: no hit) and the weights w = (E_bc, E_ca, E_ab) of a, b, c
+SGR_HD float sgr_tri(const float* d, const SgrRayFrame& fr, const float* a, int ia, const float* b, int ib, const float* c, int ic, float* w) {
+  const double eab = sgr_edge_oriented(fr, a, ia, b, ib);
+  const double ebc = sgr_edge_oriented(fr, b, ib, c, ic);
+  const double eca = sgr_edge_oriented(fr, c, ic, a, ia);
+  if (!(eab >= 0.0 && ebc >= 0.0 && eca >= 0.0)) return INFINITY;
+  float n[3];
+  sgr_face_normal(a, b, c, n);
+  const float den = n[0] * d[0] + n[1] * d[1] + n[2] * d[2];
+  if (!(den < 0.0f)) return INFINITY;
+  const float t = (n[0] * a[0] + n[1] * a[1] + n[2] * a[2]) / den;
+  if (!(t > 0.0f && t < INFINITY)) return INFINITY;
+  w[0] = (float)ebc; w[1] = (float)eca; w[2] = (float)eab;
+  return t;
+}
+
+// bounding sphere of a triangle about its centroid against the tile cone (the test of sgr_cone_keep)
+SGR_HD bool sgr_tri_cone_keep(const float* a, const float* b, const float* c, const float* axis, float cs, float sn) {
+  const float third = 1.0f / 3.0f;
+  const float p[3] = {(a[0] + b[0] + c[0]) * third, (a[1] + b[1] + c[1]) * third, (a[2] + b[2] + c[2]) * third};
+  float r2 = 0.0f;
+  const float* vs[3] = {a, b, c};
+  for (int q = 0; q < 3; q++) {
+    const float x = vs[q][0] - p[0], y = vs[q][1] - p[1], z = vs[q][2] - p[2];
+    r2 = fmaxf(r2, x * x + y * y + z * z);
+  }
+  const float R = sqrtf(r2);
+  const float al = p[0] * axis[0] + p[1] * axis[1] + p[2] * axis[2];
+  const float q0 = p[0] - al * axis[0], q1 = p[1] - al * axis[1], q2 = p[2] - al * axis[2];
+  const float perp = sqrtf(q0 * q0 + q1 * q1 + q2 * q2);
+  return perp * cs - al * sn <= R * 1.001f + 1e-5f;
+}
+
+// normal of vertex v: normalised sum of the face normals of its faces adj[adj_start[v] .. adj_start[v + 1]) (ascending face index);
+// (0, 0, 0) when the sum has no length.  vpos: float4 per vertex
+SGR_HD void sgr_vertex_normal(int v, const float* vpos, const uint32_t* faces, const int* adj_start, const int* adj, float* n) {
+  float s[3] = {0.0f, 0.0f, 0.0f};
+  for (int q = adj_start[v]; q < adj_start[v + 1]; q++) {
+    const uint32_t f = faces[adj[q]];
+    float fn[3];
+    sgr_face_normal(vpos + 4 * (f & 0xFF), vpos + 4 * ((f >> 8) & 0xFF), vpos + 4 * ((f >> 16) & 0xFF), fn);
+    s[0] += fn[0]; s[1] += fn[1]; s[2] += fn[2];
+  }
+  const float l2 = s[0] * s[0] + s[1] * s[1] + s[2] * s[2];
+  const float il = l2 > 0.0f ? 1.0f / sqrtf(l2) : 0.0f;
+  n[0] = s[0] * il; n[1] = s[1] * il; n[2] = s[2] * il;
+}
+
+// one pixel against the listed geoms (ids ascending, the hidden ones left out) and then the listed faces (ascending).  vpos: float4 per
+// vertex (position - eye); vrec: the env's vertex records (SGR_VREC floats each; only the hit's normals are read); skin_id: what a skin
+// pixel reports as its geom (ngeom).  *face: the hit face (-1: none)
+template <typename IdxT, typename FIdxT>
+SGR_HD SgrHit sgr_trace_skin(const float* recs, const IdxT* ids, int nids, const float* vpos, const uint32_t* faces, const FIdxT* flist, int nf,
+                             const float* vrec, const float* albedo, int skin_id, const SgrCam& c, const float* d, int* face) {
+  float best = INFINITY, bh[3] = {0, 0, 0}, bn[3] = {0, 0, 1};
+  int bg = -1;
+  for (int q = 0; q < nids; q++) {
+    const int g = (int)ids[q];
+    float h[3], nl[3];
+    const float t = sgr_intersect(recs + SGR_REC * g, d, h, nl);
+    if (t < best) {
+      best = t; bg = g;
+      bh[0] = h[0]; bh[1] = h[1]; bh[2] = h[2]; bn[0] = nl[0]; bn[1] = nl[1]; bn[2] = nl[2];
+    }
+  }
+  int bf = -1;
+  float bw[3] = {0, 0, 0};
+  SgrRayFrame fr;
+  sgr_ray_frame(d, &fr);
+  for (int q = 0; q < nf; q++) {
+    const int f = (int)flist[q];
+    const uint32_t w = faces[f];
+    const int ia = w & 0xFF, ib = (w >> 8) & 0xFF, ic = (w >> 16) & 0xFF;
+    float wt[3];
+    const float t = sgr_tri(d, fr, vpos + 4 * ia, ia, vpos + 4 * ib, ib, vpos + 4 * ic, ic, wt);
+    if (t < best) { best = t; bf = f; bw[0] = wt[0]; bw[1] = wt[1]; bw[2] = wt[2]; }
+  }
+  *face = bf;
+  SgrHit r;
+  if (bf >= 0) {
+    const uint32_t w = faces[bf];
+    const int iv[3] = {(int)(w & 0xFF), (int)((w >> 8) & 0xFF), (int)((w >> 16) & 0xFF)};
+    float fn[3];
+    sgr_face_normal(vpos + 4 * iv[0], vpos + 4 * iv[1], vpos + 4 * iv[2], fn);
+    const float fl = 1.0f / sqrtf(fn[0] * fn[0] + fn[1] * fn[1] + fn[2] * fn[2]);
+    fn[0] *= fl; fn[1] *= fl; fn[2] *= fl;
+    float n[3] = {0.0f, 0.0f, 0.0f};
+    for (int k = 0; k < 3; k++) {
+      const float* vn = vrec + SGR_VREC * iv[k] + 4;
+      const bool zero = vn[0] == 0.0f && vn[1] == 0.0f && vn[2] == 0.0f;
+      for (int x = 0; x < 3; x++) n[x] += bw[k] * (zero ? fn[x] : vn[x]);
+    }
+    const float l2 = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
+    if (l2 > 0.0f) {
+      const float il = 1.0f / sqrtf(l2);
+      n[0] *= il; n[1] *= il; n[2] *= il;
+    } else {
+      n[0] = fn[0]; n[1] = fn[1]; n[2] = fn[2];
+    }
+    const float f = 0.25f + 0.45f * fmaxf(0.0f, -(n[0] * c.fwd[0] + n[1] * c.fwd[1] + n[2] * c.fwd[2])) + 0.30f * fmaxf(0.0f, n[2]);
+    r.geom = skin_id;
+    r.depth = best * (d[0] * c.fwd[0] + d[1] * c.fwd[1] + d[2] * c.fwd[2]);
+    r.rgba[0] = sgr_u8(albedo[0] * f); r.rgba[1] = sgr_u8(albedo[1] * f); r.rgba[2] = sgr_u8(albedo[2] * f); r.rgba[3] = 255;
+    return r;
+  }
+  r.geom = bg;
+  if (bg < 0) {
+    r.depth = INFINITY;
+    sgr_background(r.rgba);
+  } else {
+    r.depth = best * (d[0] * c.fwd[0] + d[1] * c.fwd[1] + d[2] * c.fwd[2]);
+    sgr_shade(recs + SGR_REC * bg, bh, bn, c, r.rgba);
+  }
+  return r;
+}

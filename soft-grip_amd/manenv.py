@@ -43,7 +43,7 @@ class ManEnv(Env):
 
     def __init__(self, sim_start, sim_step, env_paths, is_vis=True, n_envs=1, device=0, contact_flag_mode="intent", check_scene=True,
                  tendon_damper="auto", joint_ids=None, tendon_ids=None, finger_names=None, n_actuated=None, max_cached_scenes=4,
-                 render_dir=None, render_envs=(0,), render_size=(320, 240), render_every=1, camera=None):
+                 render_dir=None, render_envs=(0,), render_size=(320, 240), render_every=1, camera=None, render_skin=False):
         """``joint_ids`` / ``tendon_ids``: which model entries ``set_new_stiffness`` writes; default = the reference's class attributes
         (joints 11..63 and tendon 0: manenv.py:12-13), to be overridden for a scene with another layout (e.g. a smaller shell).
         ``tendon_damper``: how the damper of the composite's volume tendon is integrated (mjcf.load_model).
@@ -53,7 +53,8 @@ class ManEnv(Env):
         ``render_dir``: when set, every ``render_every``-th call of ``render()`` writes PNGs of the envs ``render_envs`` at
         ``render_size`` (width, height) seen through ``camera`` (7 numbers of MuJoCo's free camera; None = the scene's default camera)
         as <render_dir>/<render_prefix>_e<env>_t<call>.png; ``render_prefix`` defaults to s<scene>_b<episode>.  Without it
-        ``render()`` stays the no-op it is (``is_vis`` starts nothing)."""
+        ``render()`` stays the no-op it is (``is_vis`` starts nothing).  ``render_skin``: those frames show the soft object as its skin
+        (``render_frames(skin=True)``) and not as its element capsules."""
         super().__init__(sim_start, sim_step)
         assert len(env_paths) > 0
         assert contact_flag_mode in ("intent", "reference")
@@ -81,6 +82,7 @@ class ManEnv(Env):
                                      # would have carried on.  Counted apart so that a dataset job can refuse to paper over it (create_dataset)
         self.render_dir, self.render_envs, self.render_every, self.camera = render_dir, [int(e) for e in render_envs], int(render_every), camera
         self.render_size = (int(render_size[0]), int(render_size[1]))
+        self.render_skin = bool(render_skin)
         self.render_prefix = None     # file-name prefix of the frames (None: s<scene>_b<episode>)
         self.current_scene, self._episode, self._render_calls = 0, -1, 0
         self._scenes = {}     # path -> the loaded scene (model, batch, buffers, the damper it runs with): load_env() of a scene seen before
@@ -325,16 +327,17 @@ class ManEnv(Env):
         if t % max(1, self.render_every):
             return
         from .pngio import write_png
-        rgb = self.render_frames(envs=self.render_envs, camera=self.camera, size=self.render_size, depth=False, seg=False)["rgb"].cpu().numpy()
+        rgb = self.render_frames(envs=self.render_envs, camera=self.camera, size=self.render_size, depth=False, seg=False, skin=self.render_skin)["rgb"].cpu().numpy()
         os.makedirs(self.render_dir, exist_ok=True)
         prefix = self.render_prefix or "s%d_b%d" % (self.current_scene, max(self._episode, 0))
         for k, e in enumerate(self.render_envs):
             write_png(os.path.join(self.render_dir, "%s_e%d_t%d.png" % (prefix, e, t)), rgb[k])
 
-    def render_frames(self, envs=None, camera=None, size=(320, 240), rgb=True, depth=True, seg=True):
+    def render_frames(self, envs=None, camera=None, size=(320, 240), rgb=True, depth=True, seg=True, skin=False):
         """images of the listed envs (None: all) on the current state: NativeBatch.render's dict of device tensors (rgba / rgb
-        [k, H, W, 4|3] uint8, depth [k, H, W] float32, seg [k, H, W] int32); size = (width, height)"""
-        return self.env.render(camera=camera, env_ids=envs, width=int(size[0]), height=int(size[1]), rgb=rgb, depth=depth, seg=seg)
+        [k, H, W, 4|3] uint8, depth [k, H, W] float32, seg [k, H, W] int32); size = (width, height).  skin=True: the soft object as
+        its skin (the scene's <skin>, else the one built from the composite's body names; seg = ngeom there)"""
+        return self.env.render(camera=camera, env_ids=envs, width=int(size[0]), height=int(size[1]), rgb=rgb, depth=depth, seg=seg, skin=skin)
 
     def get_contacts(self, env_ids=None, max_contacts=256):
         """the contact list of the listed envs (None: all) at the current state -- what `sim.forward(); sim.data.contact[:ncon]` holds

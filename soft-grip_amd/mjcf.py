@@ -265,6 +265,7 @@ class _Compiler:
     def __init__(self, path: str, composite_neighbors: bool = True):
         self.root = _load_xml(path)
         self.composite_neighbors = composite_neighbors
+        self.skin_spec = None     # <composite><skin>: prefix, inflate, rgba
         self.defaults = _Defaults()
         self.bodies: List[_Body] = [_Body("world", np.zeros(3), np.array([1.0, 0, 0, 0]), -1)]
         self.tendons: List[_Tendon] = []
@@ -452,8 +453,10 @@ class _Compiler:
                     eq_t["solimp"] = _parse_solimp(a.pop("solimpfix"))
                 a.pop("kind", None)
                 tattr.update(a)
-            elif c.tag == "skin":
-                pass  # render-only
+            elif c.tag == "skin":   # render-only: no part of the blob (Model.composite_skin); the first skinned composite's is kept
+                if self.skin_spec is None:      # material / texcoord / subgrid: accepted and ignored
+                    rgba = _vec(c.attrib["rgba"], 4) if "rgba" in c.attrib else None
+                    self.skin_spec = dict(prefix=prefix, inflate=float(c.attrib.get("inflate", 0.0)), rgba=rgba)
             else:
                 raise ValueError("unsupported composite child <%s>" % c.tag)
 
@@ -554,6 +557,7 @@ class _Compiler:
         m.njmax = self.size["njmax"]
 
         m.body_names = [b.name for b in B]
+        m.skin = m.composite_skin(**self.skin_spec) if self.skin_spec else None
         m.body_parentid = np.array([max(b.parent, 0) for b in B], dtype=np.int32)
         m.body_pos = np.array([b.pos for b in B])
         m.body_quat = np.array([b.quat for b in B])
@@ -973,6 +977,63 @@ class Model:
         "site_bodyid", "tendon_adr", "tendon_num", "wrap_type", "wrap_objid",
         "eq_type", "eq_obj1id", "eq_obj2id", "actuator_trnid", "sensor_type", "sensor_objid", "sensor_adr",
     ]
+
+    skin = None    # the composite's <skin> (compile_mjcf) as composite_skin() returns it; no part of the blob
+
+    def composite_skin(self, inflate=0.0, rgba=None, prefix=None):
+        """The skin of the composite whose element bodies are named ``<prefix>B<ix>_<iy>_<iz>`` (prefix None: that of the first such
+        body), from the body names alone -- so a blob-loaded model gets one too: dict of ``vert_body`` [nvert] int32, ``vert_pos``
+        [nvert, 3] float64 (body frame), ``face`` [nface, 3] int32 (front side counter-clockwise), ``rgba`` [4] float32; None when no
+        such bodies exist.  One vertex per shell element in the order the elements are generated (ix outer, iy, iz inner), at
+        (0, 0, inflate): the element bodies' z axis points outward, so inflate = 0 puts the vertices on the outermost points of the
+        collision geoms.  Faces per axis x, y, z and per side low then high, in-face axes (b, c) the cyclic successors, quads over b
+        (outer) and c (inner) split along P00 - P11 and wound outward.  count = the largest index + 1; built as at subgrid = 0.
+        rgba None: (0.8, 0.2, 0.1, 1), the renderer's element albedo.  csrc/sg_skin.h is the same routine in the library."""
+        import re
+        body, count, pre = {}, [0, 0, 0], prefix
+        for i, name in enumerate(self.body_names):
+            mt = re.match(r"^(.*)B(\d{1,6})_(\d{1,6})_(\d{1,6})$", name, re.S)
+            if not mt:
+                continue
+            if pre is None:
+                pre = mt.group(1)
+            if mt.group(1) != pre:
+                continue
+            idx = tuple(int(mt.group(k)) for k in (2, 3, 4))
+            body[idx] = i
+            count = [max(count[k], idx[k] + 1) for k in range(3)]
+        if not body or min(count) < 2:
+            return None
+        vert, vert_body = {}, []
+        for ix in range(count[0]):
+            for iy in range(count[1]):
+                for iz in range(count[2]):
+                    if not (ix in (0, count[0] - 1) or iy in (0, count[1] - 1) or iz in (0, count[2] - 1)):
+                        continue
+                    if (ix, iy, iz) not in body:
+                        return None
+                    vert[(ix, iy, iz)] = len(vert_body)
+                    vert_body.append(body[(ix, iy, iz)])
+        if len(vert_body) != len(body) or len(vert_body) > 256:
+            return None
+        face = []
+        for a in range(3):
+            b, c = (a + 1) % 3, (a + 2) % 3
+            for side in (0, 1):
+                for i in range(count[b] - 1):
+                    for j in range(count[c] - 1):
+                        def at(di, dj):
+                            q = [0, 0, 0]
+                            q[a], q[b], q[c] = (count[a] - 1 if side else 0), i + di, j + dj
+                            return vert[tuple(q)]
+                        p00, p10, p11, p01 = at(0, 0), at(1, 0), at(1, 1), at(0, 1)
+                        face += [(p00, p10, p11), (p00, p11, p01)] if side else [(p00, p11, p10), (p00, p01, p11)]
+        if len(face) > 512:
+            return None
+        vert_pos = np.zeros((len(vert_body), 3))
+        vert_pos[:, 2] = inflate
+        return dict(vert_body=np.array(vert_body, dtype=np.int32), vert_pos=vert_pos, face=np.array(face, dtype=np.int32).reshape(-1, 3),
+                    rgba=np.array((0.8, 0.2, 0.1, 1.0) if rgba is None else rgba, dtype=np.float32))
 
     def to_blob(self) -> bytes:
         recs = []

@@ -23,8 +23,9 @@ SYMBOLS = [
     "sg_model_compile", "sg_mjcf_compile", "sg_blob_free", "sg_set_solver_envs_per_wavefront", "sg_solver_envs_per_wavefront",
     "sg_get_touch_words", "sg_model_nboxes", "sg_model_nv", "sg_model_njnt", "sg_tree_workgroups_per_cu",
     "sg_get_poses", "sg_model_nbody", "sg_model_ngeom", "sg_model_default_camera", "sg_render",
-    "sg_get_contacts", "sg_model_ncollision_pairs",
+    "sg_get_contacts", "sg_model_ncollision_pairs", "sg_model_set_skin", "sg_model_skin", "sg_render_ex",
 ]
+SG_RENDER_SKIN = 1
 SG_COMPILE_NO_NEIGHBORS, SG_COMPILE_IMPLICIT_TENDON_DAMPER = 1, 2
 
 
@@ -86,6 +87,9 @@ def load_library(path):
     L.sg_model_default_camera.argtypes = [vp, C.POINTER(C.c_double)]
     L.sg_get_poses.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, dp, dp, dp, vp]
     L.sg_render.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.sg_model_set_skin.argtypes = [vp, C.c_int, ip, dp, C.c_int, ip, C.POINTER(C.c_float)]
+    L.sg_model_skin.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), ip, dp, ip, C.POINTER(C.c_float)]
+    L.sg_render_ex.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.sg_get_contacts.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, ip, ip, dp, dp, dp, vp]
     L.sg_model_ncollision_pairs.argtypes = [vp]
     L.sg_profile_enable.argtypes = [vp, C.c_int]
@@ -130,6 +134,35 @@ class NativeModel:
         self.nbody = L.sg_model_nbody(self.ptr)
         self.ngeom = L.sg_model_ngeom(self.ptr)
         self.ncollision_pairs = L.sg_model_ncollision_pairs(self.ptr)   # candidate geom pairs of the contact read-out
+        if getattr(model, "skin", None) is not None:     # the composite's <skin> (mjcf.py; no part of the blob)
+            self.set_skin(model.skin)
+
+    def set_skin(self, skin):
+        """attach a skin (sg_model_set_skin): dict of vert_body [nvert] int, vert_pos [nvert, 3] float, face [nface, 3] int, rgba [4];
+        None removes it.  Batches of this model show it from their next render(skin=True) on."""
+        if skin is None:
+            check(self.L.sg_model_set_skin(self.ptr, 0, None, None, 0, None, None), self.L)
+            return
+        vb = np.ascontiguousarray(skin["vert_body"], dtype=np.int32).reshape(-1)
+        vp = np.ascontiguousarray(skin["vert_pos"], dtype=np.float64).reshape(-1, 3)
+        fc = np.ascontiguousarray(skin["face"], dtype=np.int32).reshape(-1, 3)
+        rgba = np.ascontiguousarray(skin["rgba"], dtype=np.float32).reshape(4)
+        if len(vp) != len(vb):
+            raise ValueError("skin: vert_pos needs one row per vertex")
+        check(self.L.sg_model_set_skin(self.ptr, len(vb), vb.ctypes.data_as(C.c_void_p), vp.ctypes.data_as(C.c_void_p), len(fc),
+                                       fc.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.POINTER(C.c_float))), self.L)
+
+    def skin(self):
+        """the attached skin as set_skin's dict (sg_model_skin); None without one"""
+        nv, nf = C.c_int(), C.c_int()
+        check(self.L.sg_model_skin(self.ptr, C.byref(nv), C.byref(nf), None, None, None, None), self.L)
+        if nv.value == 0:
+            return None
+        vb, vp = np.empty(nv.value, np.int32), np.empty((nv.value, 3), np.float64)
+        fc, rgba = np.empty((nf.value, 3), np.int32), np.empty(4, np.float32)
+        check(self.L.sg_model_skin(self.ptr, None, None, vb.ctypes.data_as(C.c_void_p), vp.ctypes.data_as(C.c_void_p),
+                                   fc.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.POINTER(C.c_float))), self.L)
+        return dict(vert_body=vb, vert_pos=vp, face=fc, rgba=rgba)
 
     def default_camera(self):
         """MuJoCo free camera [lookat xyz, distance, azimuth, elevation, fovy] that frames the scene at qpos0 (sg_model_default_camera)"""
@@ -271,11 +304,17 @@ class NativeBatch:
         self._check(self.L.sg_get_contacts(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, mc, _ptr(out.get("ncon")),
                                            _ptr(out.get("geom")), _ptr(out.get("dist")), _ptr(out.get("pos")), _ptr(out.get("frame")), self._stream()))
 
-    def render(self, camera=None, env_ids=None, width=320, height=240, rgb=True, depth=True, seg=True):
+    def render(self, camera=None, env_ids=None, width=320, height=240, rgb=True, depth=True, seg=True, skin=False):
         """ray-cast images of the listed envs (None: all) on the current state (sg_render): dict of device tensors rgba [k, H, W, 4]
         uint8 with its view rgb [..., :3], depth [k, H, W] float32 (+inf = background), seg [k, H, W] int32 (geom id, -1 = background).
-        camera: 7 numbers (lookat xyz, distance, azimuth, elevation, fovy); None = the model's default camera."""
+        camera: 7 numbers (lookat xyz, distance, azimuth, elevation, fovy); None = the model's default camera.
+        skin=True (sg_render_ex, SG_RENDER_SKIN): the soft object is drawn as its skin -- seg reports ngeom there -- and not as its
+        element geoms; a model without one gets ``model.composite_skin()`` attached first, and renders as before when there is none."""
         t = self.torch
+        if skin and self.nmodel.skin() is None and hasattr(self.nmodel.model, "composite_skin"):
+            made = self.nmodel.model.composite_skin()
+            if made is not None:
+                self.nmodel.set_skin(made)
         cam = np.ascontiguousarray(self.nmodel.default_camera() if camera is None else camera, dtype=np.float64).reshape(7)
         ids, k = self._ids(env_ids)
         out = {}
@@ -286,9 +325,13 @@ class NativeBatch:
             out["depth"] = t.empty(k, height, width, dtype=t.float32, device=self.device)
         if seg:
             out["seg"] = t.empty(k, height, width, dtype=t.int32, device=self.device)
-        self._check(self.L.sg_render(self.ptr, cam.ctypes.data_as(C.POINTER(C.c_double)),
-                                     None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, int(width), int(height),
-                                     _ptr(out.get("rgba")), _ptr(out.get("depth")), _ptr(out.get("seg")), self._stream()))
+        args = (_ptr(out.get("rgba")), _ptr(out.get("depth")), _ptr(out.get("seg")), self._stream())
+        head = (self.ptr, cam.ctypes.data_as(C.POINTER(C.c_double)), None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k,
+                int(width), int(height))
+        if skin:
+            self._check(self.L.sg_render_ex(*head, SG_RENDER_SKIN, *args))
+        else:
+            self._check(self.L.sg_render(*head, *args))
         return out
 
     def set_solver_envs_per_wavefront(self, epw):
