@@ -1,0 +1,61 @@
+#!/usr/bin/env python3
+"""Did a change of the source move the generated code?  Two device assembly files (build_native keeps them: build/<variant>/*.device.s) go
+in; per function SAME or DIFF of its instruction stream -- comments and directives stripped, the block labels (.LBB..) kept -- and per
+kernel the resource metadata.  Exit status 1 on any DIFF.
+usage: asm_same.py OLD.s NEW.s [OLDNAME=NEWNAME ...]     a rename is a regular expression and its replacement, applied to OLD's text:
+       '10tree_stageILi(\\d+)ELi1E=19tree_stage_dynamicsILi\\1E'"""
+import re
+import sys
+
+META = (".vgpr_count", ".agpr_count", ".sgpr_spill_count", ".vgpr_spill_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
+
+
+def parse(text):
+    funcs, cur = {}, None
+    isfunc = set(re.findall(r"^\s*\.type\s+([^\s,]+),@function", text, re.M))
+    for line in text.split("\n"):
+        line = line.split(";", 1)[0].strip()
+        m = re.match(r"^([A-Za-z_][\w$.]*):$", line)
+        if m and m.group(1) in isfunc:
+            cur = funcs.setdefault(m.group(1), [])
+        elif line.startswith(".Lfunc_end"):
+            cur = None
+        elif cur is not None and line and (not line.startswith(".") or re.match(r"^\.LBB\w+:$", line)):
+            cur.append(line)
+    kernels = {}
+    for block in text.split("  - .agpr_count:")[1:]:          # one metadata entry per kernel (its keys are sorted: this one is first)
+        block = "  - .agpr_count:" + block
+        name = re.search(r"\.name:\s+(\S+)", block)
+        kernels[name.group(1)] = tuple(re.search(r"\%s:\s+(\d+)" % k, block).group(1) for k in META)
+    return funcs, kernels
+
+
+def main(argv):
+    old, new = open(argv[1]).read(), open(argv[2]).read()
+    for r in argv[3:]:
+        a, b = r.split("=", 1)
+        old = re.sub(a, b, old)
+    (fo, ko), (fn, kn) = parse(old), parse(new)
+    bad = 0
+    for name in sorted(set(fo) | set(fn)):
+        a, b = fo.get(name), fn.get(name)
+        if a == b:
+            print("SAME %6d instructions  %s" % (sum(1 for s in a if not s.endswith(":")), name))
+            continue
+        bad += 1
+        if a is None or b is None:
+            print("DIFF only in %s  %s" % ("NEW" if a is None else "OLD", name))
+        else:
+            first = next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
+            print("DIFF %d -> %d lines, first at line %d of the stream  %s" % (len(a), len(b), first, name))
+    for name in sorted(set(ko) | set(kn)):
+        same = ko.get(name) == kn.get(name)
+        bad += not same
+        print("%s metadata %s  %s" % ("SAME" if same else "DIFF", " ".join("%s=%s" % (k[1:], v) for k, v in zip(META, kn.get(name) or ko.get(name))) if same
+                                       else "%s -> %s" % (ko.get(name), kn.get(name)), name))
+    print("%d functions, %d kernels: %s" % (len(set(fo) | set(fn)), len(set(ko) | set(kn)), "all SAME" if not bad else "%d DIFF" % bad))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv))

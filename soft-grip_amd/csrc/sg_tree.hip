@@ -20,7 +20,7 @@ __global__ __launch_bounds__(64) void sg_tree_kernel(sgt::TreeArgs a) {
   extern __shared__ double sg_tree_lds[];
   const int env = blockIdx.x;
   if (env >= a.nenv) return;
-  // the step's stages are called functions (sg_tree.h tree_stage); they find the launch arguments through this word
+  // the step's stages are called functions (sg_tree_stage_*.h over sg_tree_frame.inc); they find the launch arguments through this word
   if (threadIdx.x == 0) *(unsigned long long*)sg_tree_lds = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
   __syncthreads();
   sgt::tree_env<CHD>(a, env, sg_tree_lds);

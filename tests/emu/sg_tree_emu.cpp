@@ -69,9 +69,9 @@ int temu_layout(TreeEmu* E, char* buf, int cap) {
   sgt::Lds S;
   double* const cw = E->cws.data();
   const long long CW = sgt::cws_row_doubles(E->T.CS);
-  double* const g0 = cw + (size_t)SGT_MAXHIT * SGT_HITREC * SGT_RECW + (size_t)SGT_MAXCON * CW + E->T.NMAT;
+  double* const g0 = SGT_CWS_CARVE(cw, CW, E->T.NMAT);
   sgt::lds_carve(S, E->lds.data(), E->T, H.nelem, H.has_free, g0, nullptr, H.nnb);
-  int n = snprintf(buf, cap, "stage 0\ncrow %lld\nMg %lld\n", (long long)SGT_MAXHIT * SGT_HITREC * SGT_RECW, (long long)SGT_MAXHIT * SGT_HITREC * SGT_RECW + (long long)SGT_MAXCON * CW);
+  int n = snprintf(buf, cap, "stage 0\ncrow %lld\nMg %lld\n", (long long)(SGT_CWS_ROWS(cw) - cw), (long long)(SGT_CWS_MASS(SGT_CWS_ROWS(cw), CW) - cw));
 #define LAY(f) do { const long long o = (long long)(S.f - cw); if (o >= 0 && o < (long long)E->cws.size()) n += snprintf(buf + n, cap - n, #f " %lld\n", o); } while (0)
   LAY(fs); LAY(fc); LAY(bias); LAY(tenJ); LAY(kd); LAY(qacc); LAY(xpos); LAY(xmat); LAY(xipos); LAY(ximat); LAY(bw); LAY(bal); LAY(ba); LAY(bf); LAY(bn);
   LAY(anchor); LAY(axis); LAY(spos); LAY(L); LAY(Minv); LAY(tmpP); LAY(qe); LAY(ve); LAY(we); LAY(asme); LAY(fse); LAY(bfix); LAY(Rfix); LAY(blim); LAY(Rlim);
