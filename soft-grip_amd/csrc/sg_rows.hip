@@ -224,9 +224,10 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
     }
   }
   __syncthreads();
-  int nsmax = ns;
+  int nsmax_v = ns;
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { int t = __shfl_xor(nsmax, o); nsmax = t > nsmax ? t : nsmax; }
+  for (int o = 32; o > 0; o >>= 1) { int t = __shfl_xor(nsmax_v, o); nsmax_v = t > nsmax_v ? t : nsmax_v; }
+  const int nsmax = __builtin_amdgcn_readfirstlane(nsmax_v);   // in a scalar register: the contact pass's loop control and look-ahead tests are scalar branches
   const unsigned long long any_lim = __ballot(lim_active != 0);
 
   bool running = valid;
@@ -657,17 +658,32 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
 #ifdef SG_SECTION_PROF
       if (lane == 0) { atomicAdd(&a.w.secprof[28], (unsigned long long)nsmax); atomicAdd(&a.w.secprof[29], 1ull); }
 #endif
-      // slots 0 .. SG_CAP+1 exist in memory (two spare slots), so the look-ahead never needs a bound check
+      // Two register sets: while slot i is updated the rows of slot i + 1 are on their way.  Nothing is requested past slot nsmax - 1
+      // (sg_work.h: sg_rows_load_slot; nsmax is in a scalar register, so the tests are scalar branches): until r06 every pass ended with
+      // the loads of the two spare slots nsmax, nsmax + 1 -- 16 loads of 16 bytes per lane that nobody used, ~9 % of a pass's fetch
+      // traffic at the box's mean of 20.6 slots and more where the streams are short.  The trips whose look-ahead stays inside the stream
+      // run in a loop without any test on it; the last one or two slots are peeled off, so no wait in the loop has to cover a path
+      // that skipped its loads.  (Touching lines two or four slots further ahead, to have them in L2 when the loads come, was built
+      // and measured as a loss -- 1.6 % and 6.4 % of an episode, profiles/r06_rows_lookahead_ab.txt -- and is not here.)
       Row ra, rb;
       const double2* pa = row0;
       load_row(ra, pa);
-      for (int i = 0; i < nsmax; i += 2) {
+      int i = 0;
+      for (; sg_rows_load_slot(i, 2, nsmax) >= 0; i += 2) {
         const double2* pb = pa + slot_stride;
         load_row(rb, pb);
         update_row(ra, i, pa);
         pa = pb + slot_stride;
         load_row(ra, pa);
         update_row(rb, i + 1, pb);
+      }
+      if (sg_rows_load_slot(i, 1, nsmax) >= 0) {
+        const double2* pb = pa + slot_stride;
+        load_row(rb, pb);
+        update_row(ra, i, pa);
+        update_row(rb, i + 1, pb);
+      } else {
+        update_row(ra, i, pa);
       }
       __syncthreads();
       SG_T(14);

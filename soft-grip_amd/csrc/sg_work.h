@@ -98,6 +98,11 @@ struct SgPhaseArgs {
 #define SG_ROW_INDEX(slot, wave, k, lane, nwb) \
   ((((((size_t)(slot)) * ((nwb) + 2) + (wave)) * (SG_RK / 2) + (k) / 2) * 64 + (lane)) * 2 + ((k) & 1))
 
+// The solver's look-ahead over a wavefront's contact slots 0 .. nsmax - 1 (sg_rows.hip, the contact pass): while slot i is updated the rows
+// of slot i + ahead are loaded into registers -- or nothing is (-1) where that slot is past the end of the wavefront's longest stream.
+// Whatever (i, ahead) a caller passes, a slot that comes back lies in [0, nsmax - 1] (tests/test_rows_touch_index.py).
+__host__ __device__ constexpr int sg_rows_load_slot(int i, int ahead, int nsmax) { return i + ahead < nsmax ? i + ahead : -1; }
+
 enum { SGH_QSM = 0, SGH_QFRC = 4, SGH_ACTDOT = 8, SGH_M = 9, SGH_K = 25, SGH_MINV = 73, SGH_V = 89, SGH_W = 93, SGH_BOX = 97,
        SGH_LIMACT = 121, SGH_LIMSIGN = 122, SGH_LIMR = 130, SGH_LIMB = 138, SGH_LIMF = 146 };
 
