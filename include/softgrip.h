@@ -219,6 +219,40 @@ int sg_get_contacts(sg_batch* b, const int32_t* env_ids, int n_ids, int max_cont
                     int32_t* ncon, int32_t* geom, double* dist, double* pos, double* frame, void* stream);
 int sg_model_ncollision_pairs(const sg_model* m);
 
+/* ---- ray queries: replaces mj_ray / the rangefinder sensor -- "what lies along this line, and how far away".
+ * mj_ray for the listed envs at the batch's CURRENT qpos, n_rays rays per env, in fp64.
+ *   origin, dir  device: [n_rays][3], the same rays for every listed env, or [n_ids][n_rays][3] with SG_RAY_PER_ENV in `flags`.
+ *                Directions are normalised by the call.
+ *   ray_body     HOST, [n_rays], NULL = all -1.  ray_body[r] >= 0: origin and direction of ray r are given in that body's frame and
+ *                follow the body's pose in each env; -1: the world frame.
+ *   ray_exclude  HOST, [n_rays], NULL = all -1.  ray_exclude[r] >= 0: the geoms of that body are no candidates (mj_ray's bodyexclude:
+ *                what a rangefinder does with its own body).
+ *   cat_mask     bit c set: the geoms of category c are candidates (mj_ray's geomgroup).  The categories are those of the kinematics
+ *                table: the ground plane, static geoms, moving finger boxes, the soft object's shell elements, its centre sphere.
+ *   max_dist     <= 0: unlimited; otherwise a hit farther away is a miss.
+ * Per-ray rules (the renderer's): only ENTRY hits count -- the smallest t > 0 at which the ray enters a geom from outside.  An origin
+ * inside a geom therefore does not see that geom: THIS DEPARTS FROM mj_ray, which reports the exit; a depth probe that starts inside
+ * its own (excluded) body and crosses it sees what lies in front, and a surface that has pushed past the origin is not reported from
+ * behind.  Planes are one-sided (seen from their +z side).  Of equal distances the smaller geom id wins.  Primitives: plane, sphere,
+ * capsule, box; a model with another geom type fails with SG_ERR_MODEL, as sg_render does (and beyond its 320 geoms).
+ * Outputs, device pointers, any may be NULL:
+ *   dist   [n_ids][n_rays] f64, metres along the unit direction; -1 for a miss;
+ *   geomid [n_ids][n_rays] int32; -1 for a miss;
+ *   normal [n_ids][n_rays][3] f64: the outward unit normal at the hit, world axes; zeros for a miss.
+ * A ray whose direction has zero length or a non-finite component is a miss.  An env whose qpos holds a NaN or inf gets dist = NaN,
+ * normal = NaN and geomid = -1.  env_ids as in sg_get_poses.  Reads the batch and changes nothing in it; does not synchronise the host
+ * (the two host id arrays are read before the call returns and uploaded with a copy on `stream`).  As for sg_get_contacts: after
+ * sg_step the batch's qpos is one Euler integration PAST the collision pass behind touch_out.
+ * SG_ERR_INVALID (checked before anything touches the device): NULL batch, origin or dir; n_ids <= 0 or n_rays <= 0; an env id out of
+ * range; a body id outside [-1, nbody); cat_mask outside [1, 31]; unknown flag bits; a max_dist that is not finite.
+ * Two kernel layouts serve the call (a lane per ray; the lanes of a wavefront over the geoms of one ray), chosen from n_rays; the env
+ * var SG_RAY_LAYOUT=rays|geoms, read per call, forces one.  Both give the same bits. */
+enum { SG_RAY_GROUND = 1, SG_RAY_STATIC = 2, SG_RAY_FINGER = 4, SG_RAY_ELEM = 8, SG_RAY_CENTER = 16, SG_RAY_ALL = 31 };   /* cat_mask */
+enum { SG_RAY_PER_ENV = 1 };   /* flags */
+int sg_ray(sg_batch* b, const int32_t* env_ids, int n_ids, int n_rays, const double* origin, const double* dir,
+           const int32_t* ray_body, const int32_t* ray_exclude, int cat_mask, double max_dist, int flags,
+           double* dist, int32_t* geomid, double* normal, void* stream);
+
 /* kernel timing hook for bench.py: average device time (ms) of one sg_step/sg_reset call's kernels over the
  * calls since the last call with reset != 0, measured with HIP events on the launch
  * stream.  Synchronises the host. */

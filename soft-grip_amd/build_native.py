@@ -36,7 +36,7 @@ SOURCE_FLAGS = {"sg_tree.hip": ["-fno-optimize-sibling-calls"]}
 
 def _headers():
     # (this file too: the flags are in it)
-    return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(_HERE, "..", "include", "*.h")) + [os.path.join(CSRC, "sg_kernels.hip"), os.path.join(CSRC, "sg_kin.hip"), os.path.join(CSRC, "sg_contacts.hip"), os.path.abspath(__file__)])
+    return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(_HERE, "..", "include", "*.h")) + [os.path.join(CSRC, "sg_kernels.hip"), os.path.join(CSRC, "sg_kin.hip"), os.path.join(CSRC, "sg_contacts.hip"), os.path.join(CSRC, "sg_ray.hip"), os.path.abspath(__file__)])
 
 
 def _stale(target, deps):

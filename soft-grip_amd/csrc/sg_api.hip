@@ -12,6 +12,7 @@
 #include "sg_work.h"
 #include "sg_kin.hip"   // pose read-out and renderer kernels (compiled in this translation unit)
 #include "sg_contacts.hip"   // contact-list read-out kernel (compiled in this translation unit, after sg_kin.hip)
+#include "sg_ray.hip"   // ray-query kernels (compiled in this translation unit, after sg_contacts.hip)
 #include "sg_devmem.h"   // SgArena, SgScratch: the owners of every device buffer below (after the HIP runtime's declarations)
 #ifdef SG_LEGACY_PIPELINES
 #include "sg_kernels_args.h"
@@ -128,6 +129,9 @@ struct sg_batch {
   double* con_gaux = nullptr;
   SgScratch<double> con_scratch;   // per-env pose blocks of a model whose poses do not fit LDS
   bool con_attr_set = false;
+  // ray queries (sg_ray.hip): the poses of the last call's envs and its rays' body / exclude ids
+  SgScratch<double> ray_xpos, ray_xquat, ray_gxpos, ray_gxmat;   // [n_ids][nbody][3 | 4], [n_ids][ngeom][3 | 9]
+  SgScratch<int> ray_ids;                                         // [2][n_rays]
   ~sg_batch() {   // (on the batch's device: sg_batch_destroy.  The arenas and scratch buffers free themselves)
     for (auto& e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (auto& e : ev_pgs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -973,6 +977,66 @@ int sg_get_contacts(sg_batch* b, const int32_t* env_ids, int n_ids, int max_cont
   a.ncon = ncon; a.geom = geom; a.dist = dist; a.pos = pos; a.frame = frame; a.scratch = in_lds ? nullptr : b->con_scratch.p;
   if (in_lds) hipLaunchKernelGGL(sg_contacts_kernel<true>, dim3(n_ids), dim3(64), lds, s, a);
   else hipLaunchKernelGGL(sg_contacts_kernel<false>, dim3(n_ids), dim3(64), sizeof(double) * SGC_FIXED_DBL, s, a);
+  HIPCHK(hipGetLastError());
+  return SG_OK;
+}
+
+// ---- ray queries (sg_ray.hip) ----
+// Which layout a call gets: lanes over geoms below SG_RAY_CROSSOVER rays per env, lane per ray from there on.  Measured (DESIGN.md 8.3,
+// profiles/r08_ray_bench.json; 4096 envs, softbox): lanes over geoms wins at 16 rays per env (0.18 against 0.33 ms) and loses at 64 (0.55
+// against 0.40 ms); the two lines cross near 34.  SG_RAY_LAYOUT=rays|geoms, read per call, forces one (the tests run both at every shape).
+#define SG_RAY_CROSSOVER 32
+int sg_ray(sg_batch* b, const int32_t* env_ids, int n_ids, int n_rays, const double* origin, const double* dir, const int32_t* ray_body,
+           const int32_t* ray_exclude, int cat_mask, double max_dist, int flags, double* dist, int32_t* geomid, double* normal, void* stream) {
+  // (argument checks first, in an order that lets most be reached without a device)
+  if (n_ids <= 0 || n_rays <= 0) return fail(SG_ERR_INVALID, "sg_ray: n_ids and n_rays must be positive");
+  if (cat_mask < 1 || cat_mask > SG_RAY_ALL) return fail(SG_ERR_INVALID, "sg_ray: cat_mask outside [1, 31]");
+  if (flags & ~SG_RAY_PER_ENV) return fail(SG_ERR_INVALID, "sg_ray: unknown flag bits");
+  if (!std::isfinite(max_dist)) return fail(SG_ERR_INVALID, "sg_ray: max_dist must be finite (<= 0: unlimited)");
+  if (!b || !origin || !dir) return fail(SG_ERR_INVALID, "sg_ray: null batch, origin or dir");
+  const SgKinHost& K = b->m->kin;
+  if (K.ok)
+    for (const int32_t* ids : {ray_body, ray_exclude})
+      for (int r = 0; ids && r < n_rays; r++)
+        if (ids[r] < -1 || ids[r] >= K.o.nbody)
+          return fail(SG_ERR_INVALID, "sg_ray: body id " + std::to_string(ids[r]) + " of ray " + std::to_string(r) + " outside [-1, " + std::to_string(K.o.nbody) + ")");
+  if (K.ok && K.bad_type >= 0)
+    return fail(SG_ERR_MODEL, "sg_ray: geom type " + std::to_string(K.bad_type) + " has no ray intersection (plane, sphere, capsule and box only)");
+  if (K.ok && K.o.ngeom > SGY_MAXGEOM) return fail(SG_ERR_MODEL, "sg_ray: more than " + std::to_string(SGY_MAXGEOM) + " geoms");
+  if ((long long)n_ids * n_rays > 0x7fffffffll) return fail(SG_ERR_INVALID, "sg_ray: too many envs x rays for one launch");
+  hipStream_t s = (hipStream_t)stream;
+  const int* dids = nullptr;
+  if (int rc = kin_prepare(b, "sg_ray", env_ids, n_ids, s, &dids)) return rc;
+  if (!dist && !geomid && !normal) return SG_OK;
+  const size_t nb = K.o.nbody, ng = K.o.ngeom;
+  if (!b->ray_xpos.reserve((size_t)n_ids * nb * 3, s)) return devmem_fail(b->ray_xpos.nomem, "sg_ray (body poses)");
+  if (!b->ray_xquat.reserve((size_t)n_ids * nb * 4, s)) return devmem_fail(b->ray_xquat.nomem, "sg_ray (body poses)");
+  if (!b->ray_gxpos.reserve((size_t)n_ids * (ng ? ng : 1) * 3, s)) return devmem_fail(b->ray_gxpos.nomem, "sg_ray (geom poses)");
+  if (!b->ray_gxmat.reserve((size_t)n_ids * (ng ? ng : 1) * 9, s)) return devmem_fail(b->ray_gxmat.nomem, "sg_ray (geom poses)");
+  if (!b->ray_ids.reserve(2 * (size_t)n_rays, s)) return devmem_fail(b->ray_ids.nomem, "sg_ray (ray body ids)");
+  if (ray_body) HIPCHK(hipMemcpyAsync(b->ray_ids.p, ray_body, sizeof(int) * n_rays, hipMemcpyHostToDevice, s));
+  if (ray_exclude) HIPCHK(hipMemcpyAsync(b->ray_ids.p + n_rays, ray_exclude, sizeof(int) * n_rays, hipMemcpyHostToDevice, s));
+  if (int rc = launch_kin(b, dids, n_ids, b->ray_xpos.p, b->ray_xquat.p, b->ray_gxpos.p, b->ray_gxmat.p, nullptr, nullptr, s)) return rc;
+  SgRayArgs a;
+  a.D = b->kin_d; a.I = b->kin_i; a.gsize = K.o.gsize; a.gmeta = K.o.gmeta; a.gbody = K.o.gbody; a.ngeom = K.o.ngeom; a.nbody = K.o.nbody;
+  a.xpos = b->ray_xpos.p; a.xquat = b->ray_xquat.p; a.gxpos = b->ray_gxpos.p; a.gxmat = b->ray_gxmat.p;
+  a.origin = origin; a.dir = dir;
+  a.ray_body = ray_body ? b->ray_ids.p : nullptr; a.ray_exclude = ray_exclude ? b->ray_ids.p + n_rays : nullptr;
+  a.n_ids = n_ids; a.n_rays = n_rays; a.per_env = (flags & SG_RAY_PER_ENV) ? 1 : 0; a.cat_mask = cat_mask;
+  a.limit = max_dist > 0 ? max_dist : INFINITY;
+  a.dist = dist; a.geomid = geomid; a.normal = normal;
+  bool by_geoms = n_rays < SG_RAY_CROSSOVER;
+  if (const char* forced = getenv("SG_RAY_LAYOUT")) {
+    if (!strcmp(forced, "rays")) by_geoms = false;
+    else if (!strcmp(forced, "geoms")) by_geoms = true;
+    else if (*forced) return fail(SG_ERR_INVALID, "sg_ray: SG_RAY_LAYOUT must be rays or geoms");
+  }
+  if (by_geoms) {
+    hipLaunchKernelGGL(sg_ray_geoms_kernel, dim3((unsigned)((long long)n_ids * n_rays)), dim3(64), 0, s, a);
+  } else {
+    const int nblk = (n_rays + 255) / 256;
+    hipLaunchKernelGGL(sg_ray_rays_kernel, dim3((unsigned)((long long)n_ids * nblk)), dim3(256), sizeof(double) * SGY_REC * (ng ? ng : 1), s, a, nblk);
+  }
   HIPCHK(hipGetLastError());
   return SG_OK;
 }

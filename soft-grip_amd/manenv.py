@@ -15,6 +15,59 @@ from . import native
 from .mjcf import load_model
 
 
+def tactile_rays(model, res=(8, 8), faces=None):
+    """The rays of ``ManEnv.tactile_depth``: per moving finger box (those of sg_model_nboxes, in geom-id order) a W x H grid of rays that
+    cross the box from the face OPPOSITE its pad and leave through the pad.  res = (W, H).  Body-frame rays, the same for every env.
+
+    A box has half extents s and a pad face (a, sigma): axis a in {0, 1, 2} of the geom's frame, sigma = +-1.  By default the face whose
+    outward normal at qpos0 has the largest dot product with (centre-sphere geom position - box centre); ``faces`` = one (axis, sign)
+    per box overrides it (a model without a centre sphere needs it: ValueError otherwise).  With u = (a + 1) % 3, v = (a + 2) % 3,
+    cell (i, j), i < W, j < H, in the geom's frame:
+        p[u] = s[u] (2 (i + .5) / W - 1),  p[v] = s[v] (2 (j + .5) / H - 1),  p[a] = -sigma s[a],  direction = sigma e_a
+    both mapped by the geom's local pose (geom_pos, geom_quat) into its body's frame; ray_body = ray_exclude = the geom's body.
+    Returns dict(origin [B, H, W, 3], direction [B, H, W, 3], body [B, H, W] int32, thickness [B] = 2 s[a], geoms [B], faces [B, 2])."""
+    from .mjcf import quat_to_mat
+    m = model
+    W, H = int(res[0]), int(res[1])
+    if W < 1 or H < 1:
+        raise ValueError("tactile_rays: res must be (W, H) with both >= 1")
+    boxes = [g for g in range(m.ngeom) if m.body_weldid[m.geom_bodyid[g]] != 0 and m.geom_type[g] == 6]
+    if faces is None:
+        centre = [g for g in range(m.ngeom) if m.geom_type[g] == 2]
+        if len(centre) != 1:
+            raise ValueError("tactile_rays: the model has no centre sphere to aim the pads at -- pass faces=[(axis, sign), ...], one per finger box")
+        kin = m.kinematics(np.asarray(m.qpos0, dtype=np.float64))
+        world = lambda g: (kin["xpos"][m.geom_bodyid[g]] + kin["xmat"][m.geom_bodyid[g]] @ m.geom_pos[g],  # noqa: E731
+                           kin["xmat"][m.geom_bodyid[g]] @ quat_to_mat(m.geom_quat[g]))
+        target = world(centre[0])[0]
+        faces = []
+        for g in boxes:
+            x, R = world(g)
+            dots = [(sg_ * float(R[:, a] @ (target - x)), -a, a, sg_) for a in range(3) for sg_ in (1, -1)]
+            faces.append(max(dots)[2:])      # (of equal dot products the smaller axis, then the + side)
+    faces = [(int(a), int(sg_)) for a, sg_ in faces]
+    if len(faces) != len(boxes) or any(a not in (0, 1, 2) or sg_ not in (1, -1) for a, sg_ in faces):
+        raise ValueError("tactile_rays: faces needs one (axis in 0..2, sign +-1) per finger box (%d)" % len(boxes))
+    B = len(boxes)
+    origin, direction = np.zeros((B, H, W, 3)), np.zeros((B, H, W, 3))
+    body, thick = np.zeros((B, H, W), dtype=np.int32), np.zeros(B)
+    ci = 2.0 * (np.arange(W) + 0.5) / W - 1.0
+    cj = 2.0 * (np.arange(H) + 0.5) / H - 1.0
+    for k, (g, (a, sg_)) in enumerate(zip(boxes, faces)):
+        s = np.asarray(m.geom_size[g], dtype=np.float64)
+        u, v = (a + 1) % 3, (a + 2) % 3
+        p = np.zeros((H, W, 3))
+        p[..., u] = s[u] * ci[None, :]
+        p[..., v] = s[v] * cj[:, None]
+        p[..., a] = -sg_ * s[a]
+        R = quat_to_mat(m.geom_quat[g])
+        origin[k] = np.asarray(m.geom_pos[g]) + p @ R.T
+        direction[k] = sg_ * R[:, a]
+        body[k] = m.geom_bodyid[g]
+        thick[k] = 2.0 * s[a]
+    return dict(origin=origin, direction=direction, body=body, thickness=thick, geoms=np.array(boxes, dtype=np.int32), faces=np.array(faces, dtype=np.int32).reshape(B, 2))
+
+
 class Env(object):
     """reference environment/interface/environment.py:1-10"""
 
@@ -348,6 +401,47 @@ class ManEnv(Env):
         out = self.env.contacts(env_ids=env_ids, max_contacts=max_contacts)
         out["geom_names"] = [n or "" for n in self.model.geom_names]
         return out
+
+    def raycast(self, origin, direction, body=None, exclude=None, env_ids=None, cat_mask=native.SG_RAY_ALL, max_dist=0.0, normals=False):
+        """ray queries on the current state (mj_ray; sg_ray): NativeBatch.raycast's arguments and dict of device tensors (dist [k, R],
+        geom [k, R], normal [k, R, 3] with normals=True)"""
+        return self.env.raycast(origin, direction, body=body, exclude=exclude, env_ids=env_ids, cat_mask=cat_mask, max_dist=max_dist, normals=normals)
+
+    def tactile_depth(self, res=(8, 8), max_gap=0.05, env_ids=None, faces=None, cat_mask=native.SG_RAY_ELEM | native.SG_RAY_CENTER):
+        """A tactile depth map of the finger pads: for every moving finger box (sg_model_nboxes, its order) a res = (W, H) grid of
+        distances from the pad's face to the object surface in front of it.  Returns dict(gap [k, nboxes, H, W] float64 device tensor:
+        metres, NEGATIVE where the object has pushed into the pad (the penetration depth), +inf where nothing lies within max_gap;
+        geom [k, nboxes, H, W] int32: the geom seen, -1 for none).
+
+        The rays are ``tactile_rays(model, res, faces)`` -- built once per scene and cached; the formula is in that function's
+        docstring so that a C caller can build the same -- cast with ray_body = ray_exclude = the box's body, cat_mask (default: the
+        soft object's elements and centre) and max_dist = max over boxes of 2 s[a] + max_gap.  A ray starts on the face opposite the
+        pad and crosses the box from inside (an origin inside a geom does not see it, and the box's body is excluded), so
+        gap = dist - 2 s[a]."""
+        import torch
+        key = (tuple(int(r) for r in res), None if faces is None else tuple((int(a), int(s)) for a, s in faces))
+        cache = self.__dict__.setdefault("_tactile_cache", {})
+        ent = cache.get((id(self.model), key))
+        if ent is None:
+            rays = tactile_rays(self.model, res, faces)
+            dev = self.env.device
+            ent = dict(origin=torch.from_numpy(rays["origin"].reshape(-1, 3).copy()).to(dev), direction=torch.from_numpy(rays["direction"].reshape(-1, 3).copy()).to(dev),
+                       body=rays["body"].reshape(-1), thickness=rays["thickness"], thick_t=torch.from_numpy(rays["thickness"]).to(dev),
+                       shape=rays["body"].shape, model=self.model)
+            cache[(id(self.model), key)] = ent
+        B, H, W = ent["shape"]
+        max_gap = float(max_gap)
+        if B == 0:
+            k = self.n_envs if env_ids is None else len(env_ids)
+            return dict(gap=torch.empty(k, 0, H, W, dtype=torch.float64, device=self.env.device), geom=torch.empty(k, 0, H, W, dtype=torch.int32, device=self.env.device))
+        out = self.env.raycast(ent["origin"], ent["direction"], body=ent["body"], exclude=ent["body"], env_ids=env_ids, cat_mask=cat_mask,
+                               max_dist=float(ent["thickness"].max()) + max_gap)
+        dist = out["dist"].view(-1, B, H, W)
+        geom = out["geom"].view(-1, B, H, W)
+        gap = dist - ent["thick_t"].view(1, B, 1, 1)
+        seen = (dist >= 0) & (gap <= max_gap)
+        inf = torch.full_like(gap, float("inf"))
+        return dict(gap=torch.where(seen | torch.isnan(dist), gap, inf), geom=torch.where(seen, geom, torch.full_like(geom, -1)))
 
     # ---- fused episode: the create_dataset.py schedule without a host round trip per step ----
     def rollout(self, schedule, out=None, reset=True):

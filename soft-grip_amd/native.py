@@ -23,9 +23,12 @@ SYMBOLS = [
     "sg_model_compile", "sg_mjcf_compile", "sg_blob_free", "sg_set_solver_envs_per_wavefront", "sg_solver_envs_per_wavefront",
     "sg_get_touch_words", "sg_model_nboxes", "sg_model_nv", "sg_model_njnt", "sg_tree_workgroups_per_cu",
     "sg_get_poses", "sg_model_nbody", "sg_model_ngeom", "sg_model_default_camera", "sg_render",
-    "sg_get_contacts", "sg_model_ncollision_pairs", "sg_model_set_skin", "sg_model_skin", "sg_render_ex",
+    "sg_get_contacts", "sg_model_ncollision_pairs", "sg_model_set_skin", "sg_model_skin", "sg_render_ex", "sg_ray",
 ]
 SG_RENDER_SKIN = 1
+# sg_ray: category bits of cat_mask (ground plane, static, moving finger box, shell element, centre sphere) and flags
+SG_RAY_GROUND, SG_RAY_STATIC, SG_RAY_FINGER, SG_RAY_ELEM, SG_RAY_CENTER, SG_RAY_ALL = 1, 2, 4, 8, 16, 31
+SG_RAY_PER_ENV = 1
 SG_COMPILE_NO_NEIGHBORS, SG_COMPILE_IMPLICIT_TENDON_DAMPER = 1, 2
 
 
@@ -92,6 +95,8 @@ def load_library(path):
     L.sg_render_ex.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.sg_get_contacts.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, ip, ip, dp, dp, dp, vp]
     L.sg_model_ncollision_pairs.argtypes = [vp]
+    L.sg_ray.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, dp, dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_double, C.c_int,
+                         dp, ip, dp, vp]
     L.sg_profile_enable.argtypes = [vp, C.c_int]
     L.sg_profile_read.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
     L.sg_profile_read_solver.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
@@ -303,6 +308,33 @@ class NativeBatch:
                 mc = x.shape[1]
         self._check(self.L.sg_get_contacts(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, mc, _ptr(out.get("ncon")),
                                            _ptr(out.get("geom")), _ptr(out.get("dist")), _ptr(out.get("pos")), _ptr(out.get("frame")), self._stream()))
+
+    def raycast(self, origin, direction, body=None, exclude=None, env_ids=None, cat_mask=SG_RAY_ALL, max_dist=0.0, normals=False):
+        """mj_ray for the listed envs (None: all) on the current state (sg_ray).  origin / direction: float64 device tensors [R, 3] --
+        the same rays for every env -- or [k, R, 3], rays of their own per listed env; directions need not be unit.  body / exclude:
+        R ints (host) or None: the body whose frame ray r is given in and follows (-1: world) and the body whose geoms it does not see
+        (-1: none).  cat_mask: SG_RAY_* bits of the geom categories that are candidates; max_dist <= 0: unlimited.  Returns a dict of
+        device tensors dist [k, R] float64 (metres, -1: miss), geom [k, R] int32 (-1: miss) and, with normals=True, normal [k, R, 3]
+        (outward, world axes, zeros for a miss).  Entry hits only: an origin inside a geom does not see that geom.  An env whose qpos
+        is not finite gets NaN / -1."""
+        t = self.torch
+        ids, k = self._ids(env_ids)
+        assert origin.is_cuda and direction.is_cuda and origin.dtype == t.float64 and direction.dtype == t.float64
+        assert origin.shape == direction.shape and origin.shape[-1] == 3 and origin.dim() in (2, 3), origin.shape
+        per_env = origin.dim() == 3
+        assert not per_env or origin.shape[0] == k, (origin.shape, k)
+        origin, direction = origin.contiguous(), direction.contiguous()
+        nr = origin.shape[-2]
+        hb = None if body is None else np.ascontiguousarray(body, dtype=np.int32).reshape(-1)
+        hx = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.int32).reshape(-1)
+        assert (hb is None or len(hb) == nr) and (hx is None or len(hx) == nr)
+        out = dict(dist=t.empty(k, nr, dtype=t.float64, device=self.device), geom=t.empty(k, nr, dtype=t.int32, device=self.device))
+        if normals:
+            out["normal"] = t.empty(k, nr, 3, dtype=t.float64, device=self.device)
+        i32 = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+        self._check(self.L.sg_ray(self.ptr, i32(ids), k, nr, _ptr(origin), _ptr(direction), i32(hb), i32(hx), int(cat_mask), float(max_dist),
+                                  SG_RAY_PER_ENV if per_env else 0, _ptr(out["dist"]), _ptr(out["geom"]), _ptr(out.get("normal")), self._stream()))
+        return out
 
     def render(self, camera=None, env_ids=None, width=320, height=240, rgb=True, depth=True, seg=True, skin=False):
         """ray-cast images of the listed envs (None: all) on the current state (sg_render): dict of device tensors rgba [k, H, W, 4]

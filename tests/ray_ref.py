@@ -1,0 +1,242 @@
+"""Independent NumPy (fp64) ray caster for sg_ray (include/softgrip.h, soft-grip_amd/csrc/sg_ray.h): written from the rules the header
+states, not from the header's code.  World frame throughout: body-frame rays are mapped first (map_rays) with the body poses the caller
+has -- NativeBatch.poses() on the GPU, mjcf.Model.kinematics() on the CPU.  Geom poses and categories are render_ref's.
+
+Rules: entry hits only (the smallest t > 0 at which the ray enters the primitive from outside; an origin inside sees nothing of it),
+planes one-sided, of equal distances the smaller geom id, a hit beyond max_dist (> 0) is a miss; a direction without length or with a
+non-finite component is a miss.  Results: dist (-1 miss), geom (-1), outward unit normal in world axes (zeros)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+from render_ref import BOX, CAPSULE, PLANE, SPHERE, categories, geom_poses  # noqa: F401
+from softgrip_amd.mjcf import quat_to_mat
+
+GROUND_BIT, STATIC_BIT, FINGER_BIT, ELEM_BIT, CENTER_BIT, ALL_BITS = 1, 2, 4, 8, 16, 31
+
+
+def _sphere_entry(o, d, r):
+    """entry root of |o + t d| = r per ray (unit d), inf where there is none or it is not positive"""
+    tl = -np.sum(o * d, -1)
+    q = o + tl[:, None] * d
+    h2 = r * r - np.sum(q * q, -1)
+    with np.errstate(invalid="ignore"):
+        t = tl - np.sqrt(h2)
+    return np.where((h2 >= 0) & (t > 0), t, np.inf)
+
+
+def _primitive(type_, size, o, d):
+    """rays o + t d [N, 3] in the primitive's own frame -> entry distance [N] (inf: none) and local outward normal [N, 3]"""
+    n = len(d)
+    nl = np.zeros((n, 3))
+    nl[:, 2] = 1.0
+    t = np.full(n, np.inf)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if type_ == PLANE:
+            tt = -o[:, 2] / d[:, 2]
+            ok = (d[:, 2] < 0) & (o[:, 2] > 0)
+            if size[0] > 0 and size[1] > 0:
+                ok &= (np.abs(o[:, 0] + tt * d[:, 0]) <= size[0]) & (np.abs(o[:, 1] + tt * d[:, 1]) <= size[1])
+            t = np.where(ok, tt, np.inf)
+        elif type_ == SPHERE:
+            t = _sphere_entry(o, d, size[0])
+            nl = (o + np.where(np.isfinite(t), t, 0.0)[:, None] * d) / size[0]
+        elif type_ == CAPSULE:
+            r, hl = size[0], size[1]
+            a = d[:, 0] ** 2 + d[:, 1] ** 2
+            tl = -(o[:, 0] * d[:, 0] + o[:, 1] * d[:, 1]) / a
+            q0, q1 = o[:, 0] + tl * d[:, 0], o[:, 1] + tl * d[:, 1]
+            h2 = r * r - (q0 * q0 + q1 * q1)
+            ts = tl - np.sqrt(h2 / a)
+            side = (a > 1e-24) & (h2 >= 0) & (ts > 0) & (np.abs(o[:, 2] + ts * d[:, 2]) <= hl)
+            t = np.where(side, ts, np.inf)
+            for zc, sgn in ((hl, 1.0), (-hl, -1.0)):       # a cap is surface on its outer hemisphere only
+                tc = _sphere_entry(o - np.array([0.0, 0.0, zc]), d, r)
+                z = o[:, 2] + np.where(np.isfinite(tc), tc, 0.0) * d[:, 2]
+                tc = np.where(sgn * (z - zc) >= 0, tc, np.inf)
+                t = np.minimum(t, tc)
+            h = o + np.where(np.isfinite(t), t, 0.0)[:, None] * d
+            nl = (h - np.stack([np.zeros(n), np.zeros(n), np.clip(h[:, 2], -hl, hl)], -1)) / r
+        elif type_ == BOX:
+            t1 = (-size - o) / d
+            t2 = (size - o) / d
+            lo, hi = np.minimum(t1, t2), np.maximum(t1, t2)
+            par = d == 0
+            lo = np.where(par, -np.inf, lo)
+            hi = np.where(par, np.inf, hi)
+            miss = np.any(par & (np.abs(o) > size), -1)
+            tn, tf = lo.max(-1), hi.min(-1)
+            ax = lo.argmax(-1)
+            t = np.where(~miss & (tn <= tf) & (tn > 0), tn, np.inf)
+            nl = np.zeros((n, 3))
+            nl[np.arange(n), ax] = -np.sign(d[np.arange(n), ax])
+    return t, nl
+
+
+def candidates(cats, geom_body, cat_mask=ALL_BITS, exclude=None, nrays=1):
+    """[ngeom, nrays] bool: geom g is a candidate of ray r (its category's bit in cat_mask, not on the ray's excluded body)"""
+    keep = ((int(cat_mask) >> np.asarray(cats)) & 1).astype(bool)[:, None] & np.ones((1, nrays), bool)
+    if exclude is not None:
+        ex = np.asarray(exclude).reshape(-1)
+        keep = keep & ~((ex[None, :] >= 0) & (np.asarray(geom_body)[:, None] == ex[None, :]))
+    return keep
+
+
+def map_rays(xpos, xquat, origin, direction, body=None):
+    """rays given in body frames (body [N], -1 / None: world) -> world origins and (unnormalised) directions"""
+    o, d = np.array(origin, dtype=np.float64), np.array(direction, dtype=np.float64)
+    if body is None:
+        return o, d
+    for r, b in enumerate(np.asarray(body).reshape(-1)):
+        if b >= 0:
+            R = quat_to_mat(xquat[b])
+            o[r] = xpos[b] + R @ o[r]
+            d[r] = R @ d[r]
+    return o, d
+
+
+def cast(gx, gm, types, sizes, origin, direction, keep=None, max_dist=0.0):
+    """world rays against the geoms -> dist [N] (-1), geom [N] int32 (-1), normal [N, 3] (zeros)"""
+    o = np.asarray(origin, dtype=np.float64).reshape(-1, 3)
+    d = np.asarray(direction, dtype=np.float64).reshape(-1, 3)
+    n, ng = len(o), len(types)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ln = np.sqrt(np.sum(d * d, -1))
+    live = np.isfinite(ln) & (ln > 0) & np.isfinite(d).all(-1)
+    u = np.where(live[:, None], d / np.where(live, ln, 1.0)[:, None], np.array([0.0, 0.0, 1.0]))
+    T = np.full((ng, n), np.inf)
+    NL = np.zeros((ng, n, 3))
+    for g in range(ng):
+        R = np.asarray(gm[g], dtype=np.float64).reshape(3, 3)
+        T[g], NL[g] = _primitive(int(types[g]), np.asarray(sizes[g], dtype=np.float64), (o - gx[g]) @ R, u @ R)
+    if keep is not None:
+        T = np.where(keep, T, np.inf)
+    T[:, ~live] = np.inf
+    if ng == 0:
+        return np.full(n, -1.0), np.full(n, -1, np.int32), np.zeros((n, 3))
+    gid = np.argmin(T, 0)                    # (first = smallest id among equal distances)
+    t = T[gid, np.arange(n)]
+    hit = np.isfinite(t) & ((t <= max_dist) if max_dist > 0 else True)
+    nw = np.einsum("nij,nj->ni", np.asarray(gm, dtype=np.float64).reshape(ng, 3, 3)[gid], NL[gid, np.arange(n)])
+    return np.where(hit, t, -1.0), np.where(hit, gid, -1).astype(np.int32), np.where(hit[:, None], nw, 0.0)
+
+
+def unstable(gx, gm, types, sizes, origin, direction, keep, max_dist, ref, shift=1e-7, tol=1e-5):
+    """[N] bool: the reference's OWN answer changes (another geom, or the distance by more than tol) when the ray's origin is moved by
+    +-shift along a world axis -- a ray that grazes a silhouette; only such rays may be left out of a comparison"""
+    o = np.asarray(origin, dtype=np.float64).reshape(-1, 3)
+    bad = np.zeros(len(o), bool)
+    for ax in range(3):
+        for sg_ in (-shift, shift):
+            e = np.zeros(3)
+            e[ax] = sg_
+            dist, gid, _ = cast(gx, gm, types, sizes, o + e, direction, keep, max_dist)
+            bad |= (gid != ref[1]) | (np.abs(dist - ref[0]) > tol)
+    return bad
+
+
+def compare(got, ref, edge, what="", tol=1e-9, cap=0.02):
+    """geom ids exact, dist and normals within tol, off the rays of `edge` (at most `cap` of them); -> number left out"""
+    gd, gg, gn = got
+    rd, rg, rn = ref
+    wrong = (gg != rg) | ~(np.abs(gd - rd) <= tol)
+    if gn is not None:
+        wrong |= ~(np.abs(gn - rn).max(-1) <= tol)
+    assert not (wrong & ~edge).any(), "%s: rays %s differ off the knife edges: got %s / %s, want %s / %s" % (
+        what, np.flatnonzero(wrong & ~edge)[:5].tolist(), gg[wrong & ~edge][:5], gd[wrong & ~edge][:5], rg[wrong & ~edge][:5], rd[wrong & ~edge][:5])
+    left = int((wrong & edge).sum())
+    assert left <= cap * len(rd), "%s: %d of %d rays left out" % (what, left, len(rd))
+    return left
+
+
+def scene_rays(gx, types, n, seed):
+    """the test recipe: c, half = centre and half-diagonal of the non-plane geom centres; origins c + 1.5 half u + (0, 0, 0.2) with u
+    uniform on the upper unit hemisphere, aimed at targets c + U(-0.6, 0.6)^3 half"""
+    rs = np.random.RandomState(seed)
+    p = np.asarray(gx)[np.asarray(types) != PLANE]
+    lo, hi = p.min(0), p.max(0)
+    c, half = 0.5 * (lo + hi), 0.5 * np.linalg.norm(hi - lo)
+    u = rs.normal(size=(n, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    u[:, 2] = np.abs(u[:, 2])
+    o = c + 1.5 * half * u + np.array([0.0, 0.0, 0.2])
+    tgt = c + rs.uniform(-0.6, 0.6, (n, 3)) * half
+    return o, tgt - o
+
+
+# ---- the g++ build of sg_ray.h: records, the ray map, the walk and the reduction as the two kernel layouts do them ----
+HOST_DRIVER = r"""
+#include <vector>
+#include "sg_ray.h"
+// layout 0: one walker over the geoms in id order (the lane-per-ray kernel); 1: 64 walkers striding over the geoms, reduced by
+// sgy_better in the butterfly order of the wave reduction (the lanes-over-geoms kernel)
+extern "C" void ray_host(int layout, int ng, const double* gx, const double* gm, const double* gs, const int* type, const int* cat, const int* gbody,
+                         const double* xpos, const double* xquat, int nr, const double* o_in, const double* d_in, const int* rbody, const int* rexcl,
+                         int cat_mask, double max_dist, double* dist, int* geom, double* normal) {
+  std::vector<double> recs((size_t)ng * SGY_REC + SGY_REC);
+  for (int g = 0; g < ng; g++) {
+    double* r = &recs[(size_t)SGY_REC * g];
+    for (int c = 0; c < 3; c++) r[c] = gx[3 * g + c];
+    for (int c = 0; c < 9; c++) r[3 + c] = gm[9 * g + c];
+    for (int c = 0; c < 3; c++) r[12 + c] = gs[3 * g + c];
+    r[15] = sgy_meta_word(sgy_meta(type[g], cat[g], gbody[g]));
+  }
+  const double limit = max_dist > 0 ? max_dist : INFINITY;
+  for (int q = 0; q < nr; q++) {
+    const int body = rbody ? rbody[q] : -1, excl = rexcl ? rexcl[q] : -1;
+    double o[3], d[3];
+    const bool live = sgy_map_ray(body >= 0 ? xpos + 3 * body : nullptr, xquat + 4 * (body >= 0 ? body : 0), o_in + 3 * q, d_in + 3 * q, o, d);
+    SgyBest best = {INFINITY, -1, 0};
+    if (live && layout == 0) {
+      for (int g = 0; g < ng; g++) sgy_visit(g, &recs[(size_t)SGY_REC * g], o, d, cat_mask, excl, limit, &best);
+    } else if (live) {
+      SgyBest w[64];
+      for (int l = 0; l < 64; l++) {
+        w[l] = SgyBest{INFINITY, -1, 0};
+        for (int g = l; g < ng; g += 64) sgy_visit(g, &recs[(size_t)SGY_REC * g], o, d, cat_mask, excl, limit, &w[l]);
+      }
+      for (int m = 32; m >= 1; m >>= 1) {
+        SgyBest nx[64];
+        for (int l = 0; l < 64; l++) nx[l] = sgy_better(w[l ^ m].t, w[l ^ m].geom, w[l].t, w[l].geom) ? w[l ^ m] : w[l];
+        for (int l = 0; l < 64; l++) w[l] = nx[l];
+      }
+      best = w[0];
+    }
+    sgy_finish(best, &recs[(size_t)SGY_REC * (best.geom >= 0 ? best.geom : 0)], o, d, limit, dist + q, geom + q, normal + 3 * q);
+  }
+}
+"""
+
+
+def build_host(tmpdir):
+    """compiles sg_ray.h with g++ into tmpdir -> ctypes function ray_host"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = os.path.join(tmpdir, "ray_host.cpp")
+    so = os.path.join(tmpdir, "libray_host.so")
+    with open(src, "w") as f:
+        f.write(HOST_DRIVER)
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(root, "soft-grip_amd", "csrc"), "-o", so, src])
+    L = C.CDLL(so)
+    L.ray_host.restype = None
+    return L.ray_host
+
+
+def cast_with(fn, gx, gm, types, sizes, cats, geom_body, origin, direction, xpos=None, xquat=None, body=None, exclude=None, cat_mask=ALL_BITS,
+              max_dist=0.0, layout=0):
+    """the host build on the same inputs (body-frame rays mapped by the header's own code) -> dist, geom, normal"""
+    a = lambda x, dt: np.ascontiguousarray(x, dtype=dt)  # noqa: E731
+    p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
+    gx, gm, gs = a(gx, np.float64), a(np.reshape(gm, (-1, 9)), np.float64), a(sizes, np.float64)
+    ty, ct, gb = a(types, np.int32), a(cats, np.int32), a(geom_body, np.int32)
+    o, d = a(np.reshape(origin, (-1, 3)), np.float64), a(np.reshape(direction, (-1, 3)), np.float64)
+    xp = a(np.zeros((1, 3)) if xpos is None else xpos, np.float64)
+    xq = a(np.array([[1.0, 0, 0, 0]]) if xquat is None else xquat, np.float64)
+    rb = None if body is None else a(body, np.int32)
+    rx = None if exclude is None else a(exclude, np.int32)
+    n = len(o)
+    dist, geom, normal = np.empty(n), np.empty(n, np.int32), np.empty((n, 3))
+    fn(C.c_int(layout), C.c_int(len(ty)), p(gx), p(gm), p(gs), p(ty), p(ct), p(gb), p(xp), p(xq), C.c_int(n), p(o), p(d), p(rb), p(rx),
+       C.c_int(int(cat_mask)), C.c_double(float(max_dist)), p(dist), p(geom), p(normal))
+    return dist, geom, normal
