@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Did a change of the source move the generated code?  Two device assembly files (build_native keeps them: build/<variant>/*.device.s) go
-in; per function SAME or DIFF of its instruction stream -- comments and directives stripped, the block labels (.LBB..) kept -- and per
-kernel the resource metadata.  Exit status 1 on any DIFF.
+in; per function SAME or DIFF of its instruction stream -- comments and directives stripped, the block labels (.LBB..) kept without the
+function's ordinal in its file (.LBB7_3 -> .LBB_3: a function that moved to another translation unit keeps its stream) -- and per kernel
+the resource metadata.  Exit status 1 on any DIFF.  A translation unit split in two: hold the old file against the two new ones concatenated.
 usage: asm_same.py OLD.s NEW.s [OLDNAME=NEWNAME ...]     a rename is a regular expression and its replacement, applied to OLD's text:
        '10tree_stageILi(\\d+)ELi1E=19tree_stage_dynamicsILi\\1E'"""
 import re
@@ -21,7 +22,7 @@ def parse(text):
         elif line.startswith(".Lfunc_end"):
             cur = None
         elif cur is not None and line and (not line.startswith(".") or re.match(r"^\.LBB\w+:$", line)):
-            cur.append(line)
+            cur.append(re.sub(r"\.LBB\d+_", ".LBB_", line))
     kernels = {}
     for block in text.split("  - .agpr_count:")[1:]:          # one metadata entry per kernel (its keys are sorted: this one is first)
         block = "  - .agpr_count:" + block

@@ -15,5 +15,5 @@ PY
 )
 mkdir -p /tmp/variants
 hipcc $BASE "$@" -c -o /tmp/variants/sg_tree_$NAME.o soft-grip_amd/csrc/sg_tree.hip
-hipcc --offload-arch=gfx950 -shared -fPIC -o soft-grip_amd/libsoftgrip_$NAME.so $OBJDIR/sg_api.o $OBJDIR/sg_phase.o $OBJDIR/sg_rows.o /tmp/variants/sg_tree_$NAME.o $OBJDIR/sg_plan.o $OBJDIR/sg_mjcf.o
+hipcc --offload-arch=gfx950 -shared -fPIC -o soft-grip_amd/libsoftgrip_$NAME.so $OBJDIR/sg_api.o $OBJDIR/sg_readout.o $OBJDIR/sg_phase.o $OBJDIR/sg_rows.o /tmp/variants/sg_tree_$NAME.o $OBJDIR/sg_plan.o $OBJDIR/sg_mjcf.o
 echo soft-grip_amd/libsoftgrip_$NAME.so

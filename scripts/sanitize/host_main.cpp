@@ -1,6 +1,6 @@
 // Host program of scripts/sanitize/run.sh (ASan + UBSan, CPU only).
 //   host_main FILE.xml ...            compiles each scene in both composite variants and builds both plans (two-finger and tree)
-//   host_main --mutate FILE.sgmodel.. feeds both plan builders, and the blob lookups sg_kin.hip / sg_contacts.hip use, damaged copies of each
+//   host_main --mutate FILE.sgmodel.. feeds both plan builders, and the blob lookups sg_readout.hip's builders use, damaged copies of each
 //                                     blob: every one must be refused with a message, and none may make a reader leave its buffer
 #include <cstdint>
 #include <cstdio>
@@ -33,7 +33,7 @@ static void mutant(const char* what, long long at, const std::string& bytes) {
     printf("ACCEPTED: %s at %lld (%zu bytes): '%s' / '%s'\n", what, at, bytes.size(), msg[0].c_str(), msg[1].c_str());
     n_bad++;
   }
-  // the lookups of sg_kin.hip and sg_contacts.hip: whatever they return must lie inside the buffer (read it all)
+  // the lookups of sgk_build and sgc_from_blob (sg_readout.hip): whatever they return must lie inside the buffer (read it all)
   static const struct { const char* name; int dt; } look[] = {{"body_parentid", SG_DT_I32}, {"body_pos", SG_DT_F64}, {"jnt_type", SG_DT_I32},
       {"qpos0", SG_DT_F64}, {"geom_rbound", SG_DT_F64}, {"geom_margin", SG_DT_F64}, {"jnt_qposadr", SG_DT_I32}, {"opt_i", SG_DT_I32},
       {"sensor_adr", SG_DT_I32}, {"names", SG_DT_U8}, {"no_such_array", SG_DT_F64}};

@@ -17,7 +17,7 @@ if _HERE not in sys.path:
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(_HERE, "libsoftgrip.so")
 LEGACY_LIB = os.path.join(_HERE, "libsoftgrip_legacy.so")
-SOURCES = ["sg_api.hip", "sg_phase.hip", "sg_rows.hip", "sg_tree.hip", "sg_plan.cpp", "sg_mjcf.cpp"]   # what the product runs
+SOURCES = ["sg_api.hip", "sg_readout.hip", "sg_phase.hip", "sg_rows.hip", "sg_tree.hip", "sg_plan.cpp", "sg_mjcf.cpp"]   # what the product runs
 LEGACY_SOURCES = ["sg_legacy.hip"]   # r01's fused / split pipelines: test builds only (-DSG_LEGACY_PIPELINES)
 # -amdgpu-sched-strategy=iterative-ilp: LLVM's iterative ILP machine scheduler instead of the default max-occupancy one.  The
 # kernels run at one or two wavefronts per SIMD whatever their register count (the solver by design, the phase kernel by its
@@ -36,7 +36,7 @@ SOURCE_FLAGS = {"sg_tree.hip": ["-fno-optimize-sibling-calls"]}
 
 def _headers():
     # (this file too: the flags are in it)
-    return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(_HERE, "..", "include", "*.h")) + [os.path.join(CSRC, "sg_kernels.hip"), os.path.join(CSRC, "sg_kin.hip"), os.path.join(CSRC, "sg_contacts.hip"), os.path.join(CSRC, "sg_ray.hip"), os.path.abspath(__file__)])
+    return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(_HERE, "..", "include", "*.h")) + [os.path.join(CSRC, "sg_kernels.hip"), os.path.abspath(__file__)])
 
 
 def _stale(target, deps):

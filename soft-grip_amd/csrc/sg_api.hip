@@ -1,46 +1,31 @@
-// sg_api.hip -- C ABI (include/softgrip.h) over the gfx950 kernels.  No CPU fallback.
-#include <hip/hip_runtime.h>
-
+// sg_api.hip -- C ABI (include/softgrip.h) over the gfx950 kernels: models, batches and the step path (the read-outs: sg_readout.hip).
+// No CPU fallback.
 #include <cstdio>
 #include <cstring>
 #include <memory>
-#include <string>
-#include <vector>
 
+#include "sg_batch.h"   // sg_model, sg_batch, fail, HIPCHK, devmem_fail: shared with the read-outs (sg_readout.hip)
+#include "sg_blob.h"
 #include "sg_mjcf.h"
 #include "sg_tree.h"
-#include "sg_work.h"
-#include "sg_kin.hip"   // pose read-out and renderer kernels (compiled in this translation unit)
-#include "sg_contacts.hip"   // contact-list read-out kernel (compiled in this translation unit, after sg_kin.hip)
-#include "sg_ray.hip"   // ray-query kernels (compiled in this translation unit, after sg_contacts.hip)
-#include "sg_devmem.h"   // SgArena, SgScratch: the owners of every device buffer below (after the HIP runtime's declarations)
 #ifdef SG_LEGACY_PIPELINES
 #include "sg_kernels_args.h"
-#endif
-
-#ifdef SG_LEGACY_PIPELINES
 #define SG_LEGACY_ON 1
 #else
 #define SG_LEGACY_ON 0   // (the split pipeline's contact records, 126 MB at 4096 envs, are then not allocated)
 #endif
 
-namespace {
-thread_local std::string g_err;
+static thread_local std::string g_err;
 int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-#define HIPCHK(x)                                                                              \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess) return fail(SG_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-// a failed sg_devmem.h call on the buffers of `what`: SG_ERR_NOMEM for the allocation, SG_ERR_HIP for a memset, a copy or the synchronise
 int devmem_fail(bool nomem, const std::string& what) {
   (void)hipGetLastError();   // (the failed call's error must not stay behind as the thread's last one: the next launch check, ours or the caller's, would report it)
   return fail(nomem ? SG_ERR_NOMEM : SG_ERR_HIP, what + (nomem ? ": out of device memory" : ": a HIP memset, copy or synchronise failed"));
 }
 
+namespace {
 __global__ void sg_fill_rows_kernel(double* dst, const double* row, int n, int w) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n * w) dst[i] = row[i % w];
@@ -57,87 +42,6 @@ __global__ void sg_masked_copy_kernel(const unsigned char* mask, int n, const in
   if (i < n && (!mask || mask[i])) { d0[i] = s0[i]; d1[i] = s1[i]; d2[i] = s2[i]; d3[i] = s3[i]; d4[i] = s4[i]; }
 }
 }  // namespace
-
-struct sg_model {
-  SgPlan plan;      // the fast kernels' plan (has_fast), else a copy of tplan: header, elements and sizes serve every entry point
-  int rounds;       // ceil(nelem / 64)
-  bool has_fast;    // the model is in the two-finger class of sg_plan.h
-  bool has_tree;    // the tree pipeline (sg_tree.h) runs it
-  SgPlan tplan;     // the tree pipeline's plan: same elements / equalities / statics, chains in `tree`, flat box references
-  SgTreeDev tree;
-  size_t tree_lds = 0;       // the tree kernel's LDS block in bytes and an env's slice of its work space in doubles (sgt::lds_bytes,
-  long long tree_cws = 0;    // sgt::cws_doubles: each walks lds_carve, so once per model)
-  SgKinHost kin;    // kinematics table of sg_get_poses / sg_render (sg_kin.hip)
-  SgConHost con;    // candidate pairs, margins and bounding radii of sg_get_contacts (sg_contacts.hip)
-  SgSkinHost skin;  // the composite's skin (sg_skin.h; nvert == 0: none): sg_model_set_skin, drawn by sg_render_ex
-};
-
-// device tables and work space of the tree pipeline (sg_tree.h), allocated when the pipeline is first selected
-struct SgTreeBufs {
-  SgPlanHeader* H = nullptr;
-  SgTreeDev* T = nullptr;
-  double *elem = nullptr, *cws = nullptr;
-  SgGenPair* pairs = nullptr;
-  SgEqSlot* sched = nullptr;  // neighbour-row models: the tree plan's block schedule and neighbour tables
-  int* nbtab = nullptr;
-  int* touch_words = nullptr;   // [n][2]
-};
-
-struct sg_batch {
-  const sg_model* m = nullptr;
-  int n = 0, device = 0;
-  SgArena mem;       // every buffer that lives as long as the batch: state, tables, the rows work space, the read-outs' tables
-  SgArena tree_mem;  // the buffers of `t`: all of them or none (tree_alloc)
-  SgPlanHeader* dH = nullptr;
-  double *delem = nullptr, *qpos = nullptr, *qvel = nullptr, *warm = nullptr, *act = nullptr, *ctrl = nullptr, *kenv = nullptr, *ctrl_row = nullptr;
-  SgGenPair* dgpairs = nullptr;  // SgPlan::gpairs on the device (the general contact path's candidate pairs)
-  int* dnbtab = nullptr;       // SgPlan::nbtab on the device (neighbour-row models)
-  SgEqSlot* dsched = nullptr;  // SgPlan::sched + eight spare rounds of idle slots
-  unsigned* dtab = nullptr;    // the same schedule as the solver's LDS table words
-  int* dcpos = nullptr;        // per element: where its equality block's step factors sit in a solver wavefront's stream (SgWork::cst)
-  int *kmask_jnt = nullptr, *kmask_ten = nullptr, *flags = nullptr, *touch = nullptr, *ncon = nullptr, *nefc = nullptr, *iters = nullptr;
-  std::vector<int> kmask_jnt_host, kmask_ten_host;   // what the device masks hold (sg_set_stiffness copies them only when they change)
-  int epw_override = 0;  // sg_set_solver_envs_per_wavefront: 0 = automatic
-  int pipeline = 3;  // 0 fused (one kernel per call), 1 split (chain / phase / pgs kernel chain), 2 split with the row-parallel PGS kernel, 3 tree
-  SgTreeBufs t;
-  bool tree_ready = false;    // every table and the work space of the tree pipeline allocated and filled (tree_alloc)
-  bool tree_attr_set = false;
-  SgWork w = {};
-  bool lds_attr_set = false;  // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done on this batch's device
-  // profiling
-  bool prof = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-  double prof_ms = 0;
-  long long prof_n = 0;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pgs;  // around every solver-kernel launch (the dominant kernel)
-  std::vector<hipEvent_t> ev_pool;  // events handed back by sg_profile_read*: a profiled call creates none once the pool is warm
-  double prof_pgs_ms = 0;
-  long long prof_pgs_n = 0;
-  // pose read-out / renderer (sg_kin.hip), allocated at first use
-  double* kin_d = nullptr;
-  int* kin_i = nullptr;
-  SgScratch<int> kin_ids;    // the listed env ids on the device
-  SgScratch<float> rrecs;    // [n_ids][ngeom][SGR_REC] fp32 geom records of the last sg_render
-  // the skin (sg_render_ex): tables uploaded at first use and again when the model's skin version has moved
-  SgArena skin_mem;
-  SgSkinDev skin_dev = {};
-  unsigned skin_version = 0;   // the version skin_dev holds (0: none; versions start at 1)
-  SgScratch<double> skin_xpos, skin_xquat;   // [n_ids][nbody][3 | 4] body poses of the last skin render
-  SgScratch<float> skin_vrec;                // [n_ids][nvert][SGR_VREC] vertex records of the last skin render
-  // contact read-out (sg_contacts.hip), allocated at first use
-  int* con_pairs = nullptr;
-  double* con_gaux = nullptr;
-  SgScratch<double> con_scratch;   // per-env pose blocks of a model whose poses do not fit LDS
-  bool con_attr_set = false;
-  // ray queries (sg_ray.hip): the poses of the last call's envs and its rays' body / exclude ids
-  SgScratch<double> ray_xpos, ray_xquat, ray_gxpos, ray_gxmat;   // [n_ids][nbody][3 | 4], [n_ids][ngeom][3 | 9]
-  SgScratch<int> ray_ids;                                         // [2][n_rays]
-  ~sg_batch() {   // (on the batch's device: sg_batch_destroy.  The arenas and scratch buffers free themselves)
-    for (auto& e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    for (auto& e : ev_pgs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    for (auto& e : ev_pool) (void)hipEventDestroy(e);
-  }
-};
 
 static int begin_event_pair(sg_batch* b, std::vector<std::pair<hipEvent_t, hipEvent_t>>& list, hipStream_t s);
 
@@ -718,327 +622,7 @@ int sg_profile_read(sg_batch* b, int reset, double* avg_ms, long long* launches)
   return profile_read(b, b->ev, b->prof_ms, b->prof_n, reset, avg_ms, launches);
 }
 
-// ---- pose read-out and renderer (sg_kin.hip) ----
 int sg_model_nbody(const sg_model* m) { return m ? m->kin.o.nbody : 0; }
 int sg_model_ngeom(const sg_model* m) { return m ? m->kin.o.ngeom : 0; }
-
-int sg_model_default_camera(const sg_model* m, double* cam) {
-  if (!m || !cam) return fail(SG_ERR_INVALID, "sg_model_default_camera: null argument");
-  if (!m->kin.ok) return fail(SG_ERR_MODEL, "sg_model_default_camera: " + m->kin.err);
-  sgk_default_camera(m->kin, cam);
-  return SG_OK;
-}
-
-// the kinematics table on the batch's device and the listed env ids (host array, range-checked here) in a device buffer
-static int kin_prepare(sg_batch* b, const char* fn, const int32_t* env_ids, int n_ids, hipStream_t s, const int** dids) {
-  const SgKinHost& K = b->m->kin;
-  if (!K.ok) return fail(SG_ERR_MODEL, std::string(fn) + ": " + K.err);
-  if (n_ids <= 0) return fail(SG_ERR_INVALID, std::string(fn) + ": n_ids must be positive");
-  if (!env_ids && n_ids != b->n) return fail(SG_ERR_INVALID, std::string(fn) + ": env_ids == NULL needs n_ids == the batch's env count");
-  if (env_ids)
-    for (int i = 0; i < n_ids; i++)
-      if (env_ids[i] < 0 || env_ids[i] >= b->n)
-        return fail(SG_ERR_INVALID, std::string(fn) + ": env id " + std::to_string(env_ids[i]) + " out of range [0, " + std::to_string(b->n) + ")");
-  HIPCHK(hipSetDevice(b->device));
-  if (!b->kin_d) {   // built on the side: the batch sees the tables only once both are filled
-    SgArena A;
-    double* d = nullptr;
-    int* ip = nullptr;
-    if (!(A.upload(&d, K.dbl) && A.upload(&ip, K.ints))) return devmem_fail(A.nomem, std::string(fn) + " (pose tables)");
-    A.give_to(b->mem);
-    b->kin_d = d; b->kin_i = ip;
-  }
-  *dids = nullptr;
-  if (env_ids) {
-    if (!b->kin_ids.reserve(n_ids, s)) return devmem_fail(b->kin_ids.nomem, std::string(fn) + " (env ids)");
-    HIPCHK(hipMemcpyAsync(b->kin_ids.p, env_ids, sizeof(int) * n_ids, hipMemcpyHostToDevice, s));
-    *dids = b->kin_ids.p;
-  }
-  return SG_OK;
-}
-
-static int launch_kin(sg_batch* b, const int* dids, int n_ids, double* xpos, double* xquat, double* gxpos, double* gxmat, float* recs,
-                      const double* eye, hipStream_t s) {
-  const SgKinHost& K = b->m->kin;
-  SgKinArgs a;
-  a.D = b->kin_d; a.I = b->kin_i; a.o = K.o; a.qpos = b->qpos; a.env_ids = dids; a.n_ids = n_ids;
-  a.xpos = xpos; a.xquat = xquat; a.gxpos = gxpos; a.gxmat = gxmat; a.recs = recs;
-  for (int c = 0; c < 3; c++) a.eye[c] = eye ? eye[c] : 0.0;
-  hipLaunchKernelGGL(sg_kin_kernel, dim3(n_ids), dim3(64), sizeof(double) * 7 * K.o.nbody, s, a);
-  HIPCHK(hipGetLastError());
-  return SG_OK;
-}
-
-int sg_get_poses(sg_batch* b, const int32_t* env_ids, int n_ids, double* xpos, double* xquat, double* geom_xpos, double* geom_xmat, void* stream) {
-  if (!b) return fail(SG_ERR_INVALID, "sg_get_poses: null batch");
-  hipStream_t s = (hipStream_t)stream;
-  const int* dids = nullptr;
-  if (int rc = kin_prepare(b, "sg_get_poses", env_ids, n_ids, s, &dids)) return rc;
-  if (!xpos && !xquat && !geom_xpos && !geom_xmat) return SG_OK;
-  return launch_kin(b, dids, n_ids, xpos, xquat, geom_xpos, geom_xmat, nullptr, nullptr, s);
-}
-
-// the argument and model checks both render entry points share (before anything touches the device)
-static int render_check(const char* fn, const sg_batch* b, const double* cam, int width, int height) {
-  const std::string f = std::string(fn) + ": ";
-  if (!b || !cam) return fail(SG_ERR_INVALID, f + "null batch or camera");
-  if (width <= 0 || height <= 0 || width > 16384 || height > 16384) return fail(SG_ERR_INVALID, f + "image size out of range (1 .. 16384)");
-  for (int c = 0; c < 7; c++)
-    if (!std::isfinite(cam[c])) return fail(SG_ERR_INVALID, f + "camera values must be finite");
-  if (!(cam[3] > 0) || !(cam[6] > 0 && cam[6] < 180)) return fail(SG_ERR_INVALID, f + "camera distance must be > 0 and fovy in (0, 180)");
-  const SgKinHost& K = b->m->kin;
-  if (K.ok && K.bad_type >= 0)
-    return fail(SG_ERR_MODEL, f + "geom type " + std::to_string(K.bad_type) + " has no ray intersection (plane, sphere, capsule and box only)");
-  if (K.ok && K.o.ngeom > SGR_MAXGEOM) return fail(SG_ERR_MODEL, f + "more than " + std::to_string(SGR_MAXGEOM) + " geoms");
-  return SG_OK;
-}
-
-int sg_render(sg_batch* b, const double* cam, const int32_t* env_ids, int n_ids, int width, int height, uint8_t* rgba, float* depth, int32_t* segid,
-              void* stream) {
-  if (int rc = render_check("sg_render", b, cam, width, height)) return rc;
-  const SgKinHost& K = b->m->kin;
-  hipStream_t s = (hipStream_t)stream;
-  const int* dids = nullptr;
-  if (int rc = kin_prepare(b, "sg_render", env_ids, n_ids, s, &dids)) return rc;
-  if (!b->rrecs.reserve((size_t)n_ids * K.o.ngeom * SGR_REC, s)) return devmem_fail(b->rrecs.nomem, "sg_render (geom records)");
-  SgRenderArgs a;
-  double eye[3];
-  sgr_camera(cam, width, height, eye, &a.cam);
-  if (int rc = launch_kin(b, dids, n_ids, nullptr, nullptr, nullptr, nullptr, b->rrecs.p, eye, s)) return rc;
-  a.recs = b->rrecs.p; a.ngeom = K.o.ngeom; a.n_ids = n_ids;
-  a.tiles_x = (width + SGR_TILE - 1) / SGR_TILE;
-  a.ntiles = a.tiles_x * ((height + SGR_TILE - 1) / SGR_TILE);
-  a.rgba = rgba; a.depth = depth; a.segid = segid;
-  if (!rgba && !depth && !segid) return SG_OK;
-  if ((long long)a.ntiles * n_ids > 0x7fffffffll) return fail(SG_ERR_INVALID, "sg_render: too many tiles x envs for one launch");
-  hipLaunchKernelGGL(sg_render_kernel, dim3((unsigned)(a.ntiles * n_ids)), dim3(256), 0, s, a);
-  HIPCHK(hipGetLastError());
-  return SG_OK;
-}
-
-// ---- the skin (sg_skin.h, sg_kin.hip) ----
-int sg_model_set_skin(sg_model* m, int nvert, const int32_t* vert_body, const double* vert_pos, int nface, const int32_t* face, const float* rgba) {
-  if (!m) return fail(SG_ERR_INVALID, "sg_model_set_skin: null model");
-  if (nvert < 0 || nface < 0) return fail(SG_ERR_INVALID, "sg_model_set_skin: negative count");
-  if (nvert == 0) {   // removes the skin
-    m->skin.nvert = m->skin.nface = 0;
-    m->skin.vert_body.clear(); m->skin.vert_pos.clear(); m->skin.face.clear();
-    m->skin.version++;
-    return SG_OK;
-  }
-  if (!m->kin.ok) return fail(SG_ERR_MODEL, "sg_model_set_skin: " + m->kin.err);
-  if (nvert > SGR_MAXVERT || nface > SGR_MAXFACE)
-    return fail(SG_ERR_MODEL, "sg_model_set_skin: more than " + std::to_string(SGR_MAXVERT) + " vertices or " + std::to_string(SGR_MAXFACE) + " faces");
-  if (!vert_body || !vert_pos || !rgba || (nface > 0 && !face)) return fail(SG_ERR_INVALID, "sg_model_set_skin: null array with a positive count");
-  for (int v = 0; v < nvert; v++) {
-    if (vert_body[v] < 0 || vert_body[v] >= m->kin.o.nbody)
-      return fail(SG_ERR_INVALID, "sg_model_set_skin: vertex " + std::to_string(v) + " is bound to body " + std::to_string(vert_body[v]) + ", outside [0, nbody)");
-    for (int c = 0; c < 3; c++)
-      if (!std::isfinite(vert_pos[3 * v + c])) return fail(SG_ERR_INVALID, "sg_model_set_skin: vertex positions must be finite");
-  }
-  for (int f = 0; f < nface; f++) {
-    const int32_t* q = face + 3 * f;
-    for (int c = 0; c < 3; c++)
-      if (q[c] < 0 || q[c] >= nvert) return fail(SG_ERR_INVALID, "sg_model_set_skin: face " + std::to_string(f) + " has a vertex index outside [0, nvert)");
-    if (q[0] == q[1] || q[1] == q[2] || q[0] == q[2]) return fail(SG_ERR_INVALID, "sg_model_set_skin: face " + std::to_string(f) + " repeats a vertex");
-  }
-  for (int c = 0; c < 4; c++)
-    if (!std::isfinite(rgba[c])) return fail(SG_ERR_INVALID, "sg_model_set_skin: rgba must be finite");
-  SgSkinHost& S = m->skin;
-  S.nvert = nvert; S.nface = nface;
-  S.vert_body.assign(vert_body, vert_body + nvert);
-  S.vert_pos.assign(vert_pos, vert_pos + 3 * (size_t)nvert);
-  S.face.assign(face, face + 3 * (size_t)nface);
-  for (int c = 0; c < 4; c++) S.rgba[c] = rgba[c];
-  S.version++;
-  return SG_OK;
-}
-
-int sg_model_skin(const sg_model* m, int* nvert, int* nface, int32_t* vert_body, double* vert_pos, int32_t* face, float* rgba) {
-  if (!m) return fail(SG_ERR_INVALID, "sg_model_skin: null model");
-  const SgSkinHost& S = m->skin;
-  if (nvert) *nvert = S.nvert;
-  if (nface) *nface = S.nface;
-  if (vert_body) std::copy(S.vert_body.begin(), S.vert_body.end(), vert_body);
-  if (vert_pos) std::copy(S.vert_pos.begin(), S.vert_pos.end(), vert_pos);
-  if (face) std::copy(S.face.begin(), S.face.end(), face);
-  if (rgba)
-    for (int c = 0; c < 4; c++) rgba[c] = S.rgba[c];
-  return SG_OK;
-}
-
-// the skin's tables on the batch's device, uploaded again when the model's skin has changed since (an earlier skin render, on whatever
-// stream it went out, may still read the old ones: the device is waited for first -- once per sg_model_set_skin, not per render)
-static int skin_prepare(sg_batch* b) {
-  const SgSkinHost& S = b->m->skin;
-  if (b->skin_version == S.version) return SG_OK;
-  const SgKinHost& K = b->m->kin;
-  SgSkinTables T;
-  sg_skin_tables(S, K.ints.data() + K.o.gbody, K.o.ngeom, K.o.nbody, &T);
-  HIPCHK(hipDeviceSynchronize());
-  b->skin_version = 0;
-  b->skin_mem.release();
-  SgArena& A = b->skin_mem;
-  int *vb = nullptr, *as = nullptr, *ad = nullptr, *hid = nullptr;
-  double* vp = nullptr;
-  uint32_t* fc = nullptr;
-  if (!(A.upload(&vb, S.vert_body) && A.upload(&vp, S.vert_pos) && A.upload(&fc, T.faces) && A.upload(&as, T.adj_start) && A.upload(&ad, T.adj) &&
-        A.upload(&hid, T.hidden))) {
-    const bool nomem = A.nomem;
-    A.release();
-    return devmem_fail(nomem, "sg_render_ex (skin tables)");
-  }
-  SgSkinDev& d = b->skin_dev;
-  d.vert_body = vb; d.vert_pos = vp; d.faces = fc; d.adj_start = as; d.adj = ad; d.hidden = hid;
-  d.nvert = S.nvert; d.nface = S.nface;
-  for (int c = 0; c < 3; c++) d.rgb[c] = S.rgba[c];
-  b->skin_version = S.version;
-  return SG_OK;
-}
-
-int sg_render_ex(sg_batch* b, const double* cam, const int32_t* env_ids, int n_ids, int width, int height, int flags, uint8_t* rgba, float* depth,
-                 int32_t* segid, void* stream) {
-  if (flags & ~SG_RENDER_SKIN) return fail(SG_ERR_INVALID, "sg_render_ex: unknown flag bits");
-  if (!b || !cam) return fail(SG_ERR_INVALID, "sg_render_ex: null batch or camera");
-  if (!(flags & SG_RENDER_SKIN) || b->m->skin.nvert == 0) return sg_render(b, cam, env_ids, n_ids, width, height, rgba, depth, segid, stream);
-  if (int rc = render_check("sg_render_ex", b, cam, width, height)) return rc;
-  const SgKinHost& K = b->m->kin;
-  const SgSkinHost& S = b->m->skin;
-  hipStream_t s = (hipStream_t)stream;
-  const int* dids = nullptr;
-  if (int rc = kin_prepare(b, "sg_render_ex", env_ids, n_ids, s, &dids)) return rc;
-  if (int rc = skin_prepare(b)) return rc;
-  const size_t nb = K.o.nbody;
-  if (!b->rrecs.reserve((size_t)n_ids * K.o.ngeom * SGR_REC, s)) return devmem_fail(b->rrecs.nomem, "sg_render_ex (geom records)");
-  if (!b->skin_xpos.reserve((size_t)n_ids * nb * 3, s)) return devmem_fail(b->skin_xpos.nomem, "sg_render_ex (body poses)");
-  if (!b->skin_xquat.reserve((size_t)n_ids * nb * 4, s)) return devmem_fail(b->skin_xquat.nomem, "sg_render_ex (body poses)");
-  if (!b->skin_vrec.reserve((size_t)n_ids * S.nvert * SGR_VREC, s)) return devmem_fail(b->skin_vrec.nomem, "sg_render_ex (vertex records)");
-  SgSkinRenderArgs A;
-  SgRenderArgs& a = A.r;
-  double eye[3];
-  sgr_camera(cam, width, height, eye, &a.cam);
-  if (int rc = launch_kin(b, dids, n_ids, b->skin_xpos.p, b->skin_xquat.p, nullptr, nullptr, b->rrecs.p, eye, s)) return rc;
-  SgSkinVertArgs V;
-  V.s = b->skin_dev; V.xpos = b->skin_xpos.p; V.xquat = b->skin_xquat.p; V.nbody = K.o.nbody; V.vrec = b->skin_vrec.p;
-  for (int c = 0; c < 3; c++) V.eye[c] = eye[c];
-  hipLaunchKernelGGL(sg_skin_vert_kernel, dim3(n_ids), dim3(256), 0, s, V);
-  HIPCHK(hipGetLastError());
-  a.recs = b->rrecs.p; a.ngeom = K.o.ngeom; a.n_ids = n_ids;
-  a.tiles_x = (width + SGR_TILE - 1) / SGR_TILE;
-  a.ntiles = a.tiles_x * ((height + SGR_TILE - 1) / SGR_TILE);
-  a.rgba = rgba; a.depth = depth; a.segid = segid;
-  A.s = b->skin_dev; A.vrec = b->skin_vrec.p;
-  if (!rgba && !depth && !segid) return SG_OK;
-  if ((long long)a.ntiles * n_ids > 0x7fffffffll) return fail(SG_ERR_INVALID, "sg_render_ex: too many tiles x envs for one launch");
-  hipLaunchKernelGGL(sg_rskin_kernel, dim3((unsigned)(a.ntiles * n_ids)), dim3(256), 0, s, A);
-  HIPCHK(hipGetLastError());
-  return SG_OK;
-}
-
-// ---- contact read-out (sg_contacts.hip) ----
-int sg_model_ncollision_pairs(const sg_model* m) {
-  if (!m) return 0;
-  if (!m->con.ok) return fail(SG_ERR_MODEL, "sg_model_ncollision_pairs: " + m->con.err);
-  return (int)(m->con.pairs.size() / 2);
-}
-
-int sg_get_contacts(sg_batch* b, const int32_t* env_ids, int n_ids, int max_contacts, int32_t* ncon, int32_t* geom, double* dist, double* pos,
-                    double* frame, void* stream) {
-  // (argument checks first, in an order that lets each be reached without a device)
-  if (n_ids <= 0) return fail(SG_ERR_INVALID, "sg_get_contacts: n_ids must be positive");
-  if (max_contacts <= 0 && (geom || dist || pos || frame)) return fail(SG_ERR_INVALID, "sg_get_contacts: max_contacts must be positive when a contact array is given");
-  if (!b) return fail(SG_ERR_INVALID, "sg_get_contacts: null batch");
-  const SgConHost& Cn = b->m->con;
-  const SgKinHost& K = b->m->kin;
-  if (K.ok && !Cn.ok) return fail(SG_ERR_MODEL, "sg_get_contacts: " + Cn.err);
-  hipStream_t s = (hipStream_t)stream;
-  const int* dids = nullptr;
-  if (int rc = kin_prepare(b, "sg_get_contacts", env_ids, n_ids, s, &dids)) return rc;
-  if (!ncon && !geom && !dist && !pos && !frame) return SG_OK;
-  if (!b->con_pairs) {   // (on the side, as the pose tables)
-    SgArena A;
-    int* dp = nullptr;
-    double* dg = nullptr;
-    if (!(A.upload(&dp, Cn.pairs) && A.upload(&dg, Cn.gaux))) return devmem_fail(A.nomem, "sg_get_contacts (pair tables)");
-    A.give_to(b->mem);
-    b->con_pairs = dp; b->con_gaux = dg;
-  }
-  const size_t npose = sgc_pose_doubles(K.o);
-  const size_t lds = sizeof(double) * (SGC_FIXED_DBL + npose);
-  const bool in_lds = lds <= 159 * 1024;   // (the kernel has 256 B of static LDS besides; the CU has 160 KB)
-  if (!in_lds && !b->con_scratch.reserve((size_t)n_ids * npose, s)) return devmem_fail(b->con_scratch.nomem, "sg_get_contacts (pose blocks)");
-  if (in_lds && !b->con_attr_set) {   // per device, as the solver kernels' attribute; what this model's launches ask for (above 64 KB it must be granted)
-    HIPCHK(hipFuncSetAttribute((const void*)sg_contacts_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    b->con_attr_set = true;
-  }
-  SgConArgs a;
-  a.D = b->kin_d; a.I = b->kin_i; a.o = K.o; a.gaux = b->con_gaux; a.pairs = b->con_pairs; a.npair = (int)(Cn.pairs.size() / 2); a.cap = Cn.cap;
-  a.qpos = b->qpos; a.env_ids = dids; a.n_ids = n_ids; a.max_contacts = max_contacts;
-  a.ncon = ncon; a.geom = geom; a.dist = dist; a.pos = pos; a.frame = frame; a.scratch = in_lds ? nullptr : b->con_scratch.p;
-  if (in_lds) hipLaunchKernelGGL(sg_contacts_kernel<true>, dim3(n_ids), dim3(64), lds, s, a);
-  else hipLaunchKernelGGL(sg_contacts_kernel<false>, dim3(n_ids), dim3(64), sizeof(double) * SGC_FIXED_DBL, s, a);
-  HIPCHK(hipGetLastError());
-  return SG_OK;
-}
-
-// ---- ray queries (sg_ray.hip) ----
-// Which layout a call gets: lanes over geoms below SG_RAY_CROSSOVER rays per env, lane per ray from there on.  Measured (DESIGN.md 8.3,
-// profiles/r08_ray_bench.json; 4096 envs, softbox): lanes over geoms wins at 16 rays per env (0.18 against 0.33 ms) and loses at 64 (0.55
-// against 0.40 ms); the two lines cross near 34.  SG_RAY_LAYOUT=rays|geoms, read per call, forces one (the tests run both at every shape).
-#define SG_RAY_CROSSOVER 32
-int sg_ray(sg_batch* b, const int32_t* env_ids, int n_ids, int n_rays, const double* origin, const double* dir, const int32_t* ray_body,
-           const int32_t* ray_exclude, int cat_mask, double max_dist, int flags, double* dist, int32_t* geomid, double* normal, void* stream) {
-  // (argument checks first, in an order that lets most be reached without a device)
-  if (n_ids <= 0 || n_rays <= 0) return fail(SG_ERR_INVALID, "sg_ray: n_ids and n_rays must be positive");
-  if (cat_mask < 1 || cat_mask > SG_RAY_ALL) return fail(SG_ERR_INVALID, "sg_ray: cat_mask outside [1, 31]");
-  if (flags & ~SG_RAY_PER_ENV) return fail(SG_ERR_INVALID, "sg_ray: unknown flag bits");
-  if (!std::isfinite(max_dist)) return fail(SG_ERR_INVALID, "sg_ray: max_dist must be finite (<= 0: unlimited)");
-  if (!b || !origin || !dir) return fail(SG_ERR_INVALID, "sg_ray: null batch, origin or dir");
-  const SgKinHost& K = b->m->kin;
-  if (K.ok)
-    for (const int32_t* ids : {ray_body, ray_exclude})
-      for (int r = 0; ids && r < n_rays; r++)
-        if (ids[r] < -1 || ids[r] >= K.o.nbody)
-          return fail(SG_ERR_INVALID, "sg_ray: body id " + std::to_string(ids[r]) + " of ray " + std::to_string(r) + " outside [-1, " + std::to_string(K.o.nbody) + ")");
-  if (K.ok && K.bad_type >= 0)
-    return fail(SG_ERR_MODEL, "sg_ray: geom type " + std::to_string(K.bad_type) + " has no ray intersection (plane, sphere, capsule and box only)");
-  if (K.ok && K.o.ngeom > SGY_MAXGEOM) return fail(SG_ERR_MODEL, "sg_ray: more than " + std::to_string(SGY_MAXGEOM) + " geoms");
-  if ((long long)n_ids * n_rays > 0x7fffffffll) return fail(SG_ERR_INVALID, "sg_ray: too many envs x rays for one launch");
-  hipStream_t s = (hipStream_t)stream;
-  const int* dids = nullptr;
-  if (int rc = kin_prepare(b, "sg_ray", env_ids, n_ids, s, &dids)) return rc;
-  if (!dist && !geomid && !normal) return SG_OK;
-  const size_t nb = K.o.nbody, ng = K.o.ngeom;
-  if (!b->ray_xpos.reserve((size_t)n_ids * nb * 3, s)) return devmem_fail(b->ray_xpos.nomem, "sg_ray (body poses)");
-  if (!b->ray_xquat.reserve((size_t)n_ids * nb * 4, s)) return devmem_fail(b->ray_xquat.nomem, "sg_ray (body poses)");
-  if (!b->ray_gxpos.reserve((size_t)n_ids * (ng ? ng : 1) * 3, s)) return devmem_fail(b->ray_gxpos.nomem, "sg_ray (geom poses)");
-  if (!b->ray_gxmat.reserve((size_t)n_ids * (ng ? ng : 1) * 9, s)) return devmem_fail(b->ray_gxmat.nomem, "sg_ray (geom poses)");
-  if (!b->ray_ids.reserve(2 * (size_t)n_rays, s)) return devmem_fail(b->ray_ids.nomem, "sg_ray (ray body ids)");
-  if (ray_body) HIPCHK(hipMemcpyAsync(b->ray_ids.p, ray_body, sizeof(int) * n_rays, hipMemcpyHostToDevice, s));
-  if (ray_exclude) HIPCHK(hipMemcpyAsync(b->ray_ids.p + n_rays, ray_exclude, sizeof(int) * n_rays, hipMemcpyHostToDevice, s));
-  if (int rc = launch_kin(b, dids, n_ids, b->ray_xpos.p, b->ray_xquat.p, b->ray_gxpos.p, b->ray_gxmat.p, nullptr, nullptr, s)) return rc;
-  SgRayArgs a;
-  a.D = b->kin_d; a.I = b->kin_i; a.gsize = K.o.gsize; a.gmeta = K.o.gmeta; a.gbody = K.o.gbody; a.ngeom = K.o.ngeom; a.nbody = K.o.nbody;
-  a.xpos = b->ray_xpos.p; a.xquat = b->ray_xquat.p; a.gxpos = b->ray_gxpos.p; a.gxmat = b->ray_gxmat.p;
-  a.origin = origin; a.dir = dir;
-  a.ray_body = ray_body ? b->ray_ids.p : nullptr; a.ray_exclude = ray_exclude ? b->ray_ids.p + n_rays : nullptr;
-  a.n_ids = n_ids; a.n_rays = n_rays; a.per_env = (flags & SG_RAY_PER_ENV) ? 1 : 0; a.cat_mask = cat_mask;
-  a.limit = max_dist > 0 ? max_dist : INFINITY;
-  a.dist = dist; a.geomid = geomid; a.normal = normal;
-  bool by_geoms = n_rays < SG_RAY_CROSSOVER;
-  if (const char* forced = getenv("SG_RAY_LAYOUT")) {
-    if (!strcmp(forced, "rays")) by_geoms = false;
-    else if (!strcmp(forced, "geoms")) by_geoms = true;
-    else if (*forced) return fail(SG_ERR_INVALID, "sg_ray: SG_RAY_LAYOUT must be rays or geoms");
-  }
-  if (by_geoms) {
-    hipLaunchKernelGGL(sg_ray_geoms_kernel, dim3((unsigned)((long long)n_ids * n_rays)), dim3(64), 0, s, a);
-  } else {
-    const int nblk = (n_rays + 255) / 256;
-    hipLaunchKernelGGL(sg_ray_rays_kernel, dim3((unsigned)((long long)n_ids * nblk)), dim3(256), sizeof(double) * SGY_REC * (ng ? ng : 1), s, a, nblk);
-  }
-  HIPCHK(hipGetLastError());
-  return SG_OK;
-}
 
 }  // extern "C"

@@ -9,7 +9,7 @@
 // whose list produced touch_out: the list returned here is the NEXT forward pass's list.  Directly after sg_reset(..., sim_start = 0, ...)
 // or sg_set_state nothing lies between the two, and there the touch bits recomputed from this list equal sg_get_touch_words.
 //
-// This header is plain per-lane / host code (SG_HD, as sg_render.h and sg_general.h): the kernel in sg_contacts.hip calls it on the
+// This header is plain per-lane / host code (SG_HD, as sg_render.h and sg_general.h): the kernel in sg_contacts_kernel.h calls it on the
 // device, and a g++ build runs the same functions pair by pair against the oracle (tests/test_contacts_host.py).
 //   sgc_build_pairs  the candidate geom pairs after the static filters, in the oracle's order (body pairs ascending, geoms of the first
 //                    body outer; contype / conaffinity, weld-group and parent - child filters; the pair swapped into type order)

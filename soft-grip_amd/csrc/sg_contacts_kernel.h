@@ -1,7 +1,7 @@
-// sg_contacts.hip -- the contact list of the current state (mj_collision, fp64) for sg_get_contacts.
+// sg_contacts_kernel.h -- the contact list of the current state (mj_collision, fp64) for sg_get_contacts.
 //
-// Compiled inside sg_api.hip's translation unit, after sg_kin.hip (whose kinematics table and per-body / per-geom routines it reuses), so
-// its device assembly is part of sg_api.device.s and of the build's assembly check.  The kernel only READS the batch's canonical qpos:
+// The kernel of sg_readout.hip's translation unit that reuses the kinematics table and the per-body / per-geom routines of sg_readout.h; its
+// device assembly is in sg_readout.device.s and under the build's assembly check.  The kernel only READS the batch's canonical qpos:
 // every pipeline is served, no step kernel is touched.  The per-pair math and the pair table are in sg_contacts.h.
 //
 //   sg_contacts_kernel   one wavefront per listed env, three stages:
@@ -17,45 +17,10 @@
 //   Order guarantee: slot s of an env holds what the oracle's contact[s] holds -- pairs in table order, a pair's records in the order its
 //   routine emits them.  ncon = min(records, cap), cap = the model's nconmax when positive, at most 512 (add_contact); records past the cap
 //   or past max_contacts are counted (up to the cap) and not written.
+#pragma once
 #include "sg_contacts.h"
+#include "sg_readout.h"
 
-struct SgConHost {
-  bool ok = false;
-  std::string err;
-  int cap = SGC_MAXCON;
-  std::vector<int> pairs;     // [npair][2]
-  std::vector<double> gaux;   // [ngeom][2]: geom_margin, geom_rbound
-};
-
-// the pair table and the per-geom margins / bounding radii from the blob
-static void sgc_from_blob(const void* blob, size_t nbytes, const SgKinHost& K, SgConHost* C) {
-  if (!K.ok) { C->err = K.err; return; }
-  long long c = 0;
-  const long long nb = K.o.nbody, ng = K.o.ngeom;
-#define CF(var, name, dt, want)                                                                                          \
-  const auto* var = (const std::conditional<dt == SG_DT_F64, double, int>::type*)sg_blob_find(blob, nbytes, name, dt, &c); \
-  if (!var || c != want) { C->err = std::string("model blob lacks ") + name; return; }
-  CF(par, "body_parentid", SG_DT_I32, nb);
-  CF(weld, "body_weldid", SG_DT_I32, nb);
-  CF(gadr, "body_geomadr", SG_DT_I32, nb);
-  CF(gnum, "body_geomnum", SG_DT_I32, nb);
-  CF(gbody, "geom_bodyid", SG_DT_I32, ng);
-  CF(gtype, "geom_type", SG_DT_I32, ng);
-  CF(ctype, "geom_contype", SG_DT_I32, ng);
-  CF(caff, "geom_conaffinity", SG_DT_I32, ng);
-  CF(gmargin, "geom_margin", SG_DT_F64, ng);
-  CF(grb, "geom_rbound", SG_DT_F64, ng);
-#undef CF
-  const int* oi = (const int*)sg_blob_find(blob, nbytes, "opt_i", SG_DT_I32, &c);
-  if (!oi || c < 2) { C->err = "model blob lacks opt_i"; return; }
-  C->cap = sgc_cap(oi[1]);
-  if (!sgc_build_pairs((int)nb, (int)ng, par, weld, gadr, gnum, gbody, gtype, ctype, caff, &C->pairs, &C->err)) return;
-  C->gaux.resize(2 * ng);
-  for (int g = 0; g < ng; g++) { C->gaux[2 * g] = gmargin[g]; C->gaux[2 * g + 1] = grb[g]; }
-  C->ok = true;
-}
-
-// ---- device ----
 struct SgcRec { double dist, pos[3], n[3]; };
 #define SGC_BB_SLOTS 8                                        // box - box pairs in flight
 #define SGC_STAGE_DBL (64 * SGC_MAXREC * 7)                   // staging records of one round

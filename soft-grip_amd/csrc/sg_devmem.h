@@ -1,4 +1,4 @@
-// sg_devmem.h -- the owners of the C ABI's device memory (sg_api.hip).  No HIP include here: hipMalloc, hipFree, hipMemset, hipMemcpy,
+// sg_devmem.h -- the owners of the C ABI's device memory (sg_batch.h).  No HIP include here: hipMalloc, hipFree, hipMemset, hipMemcpy,
 // hipStreamSynchronize, hipStream_t and hipSuccess are whatever the including file declares (the host test includes this over counting fakes).
 // Every call returns true on success; after a failure `nomem` says whether it was the allocation (else a memset, a copy or the synchronise).
 #pragma once

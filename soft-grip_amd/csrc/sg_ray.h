@@ -1,7 +1,7 @@
 // sg_ray.h -- the per-ray math of sg_ray (mj_ray in fp64): ray - primitive intersection, hit normal, bounding-sphere early-out, the body
 // frame -> world map of a ray and the walk over an env's geoms.
 //
-// Plain C++ that both layouts of the ray kernel (sg_ray.hip) run and tests/test_ray_host.py compiles with g++ against an independent NumPy
+// Plain C++ that both layouts of the ray kernel (sg_ray_kernels.h) run and tests/test_ray_host.py compiles with g++ against an independent NumPy
 // caster (tests/ray_ref.py).  The renderer's header (sg_render.h) is NOT shared: its rays leave one eye in fp32 and its records are relative
 // to that eye; a ray query has any origin, per env, and needs fp64 (millimetre gaps 1.7 m from the world origin).
 //

@@ -1,10 +1,10 @@
-// sg_ray.hip -- ray queries on the current state (mj_ray, fp64) for sg_ray.
+// sg_ray_kernels.h -- ray queries on the current state (mj_ray, fp64) for sg_ray.
 //
-// Compiled inside sg_api.hip's translation unit, after sg_contacts.hip, so its device assembly is part of sg_api.device.s and of the
-// build's assembly check.  The poses come from sg_kin_kernel, unchanged: its fp64 xpos / xquat / geom_xpos / geom_xmat outputs, written
+// Kernels of sg_readout.hip's translation unit, so their device assembly is in sg_readout.device.s and under the build's assembly
+// check.  The poses come from sg_kin_kernel, unchanged: its fp64 xpos / xquat / geom_xpos / geom_xmat outputs, written
 // into buffers the batch owns.  The kernels here only read those and the kinematics table; the per-ray math is sg_ray.h.
 //
-// Two layouts, because the two uses sit at opposite ends (which one a call gets: sg_ray in sg_api.hip):
+// Two layouts, because the two uses sit at opposite ends (which one a call gets: sg_ray in sg_readout.hip):
 //   sg_ray_rays_kernel    lane per ray.  256 lanes = one listed env x one block of 256 rays.  The env's geoms are staged in LDS as fp64
 //                         records (128 B a geom, 40 KB at the 320-geom limit: three workgroups share a CU's 160 KB); a record that is not
 //                         finite marks the env bad.  Each lane maps its ray through its body's pose and walks the records in id order.
@@ -12,7 +12,9 @@
 //                         memory, then one wave reduction of (t, geom id) by smaller t, then smaller id.
 // Both call sgy_visit per (ray, geom) and order hits by sgy_better, and sg_ray.h forms no fused multiply-add of its own, so the two give
 // the same bits.  An env whose qpos holds a NaN or inf (sg_kin_kernel writes NaN poses for it) gets dist = NaN, normal = NaN, geomid = -1.
+#pragma once
 #include "sg_ray.h"
+#include "sg_render.h"
 
 static_assert(SGY_MAXGEOM == SGR_MAXGEOM, "sg_ray takes the models sg_render takes");
 static_assert(SGY_PLANE == SGR_PLANE && SGY_SPHERE == SGR_SPHERE && SGY_CAPSULE == SGR_CAPSULE && SGY_BOX == SGR_BOX, "geom type codes");

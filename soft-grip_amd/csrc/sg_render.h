@@ -1,6 +1,6 @@
 // sg_render.h -- the headless renderer's per-ray math: free camera, camera rays, ray - primitive intersection, tile culling, shading.
 //
-// Plain C++ that the render kernel (sg_kin.hip) runs per lane in fp32 and tests/test_render_host.py compiles with g++ against an
+// Plain C++ that the render kernels (sg_kin_kernels.h) run per lane in fp32 and tests/test_render_host.py compiles with g++ against an
 // independent NumPy ray caster (tests/render_ref.py).  A geom is one 16-float record, positioned RELATIVE TO THE CAMERA EYE: the eye is
 // subtracted in fp64 before the cast (sgr_make_record), so the fp32 precision does not depend on where the scene sits.
 //   rec[0..2]   centre - eye (world axes)
@@ -235,6 +235,18 @@ struct SgrHit {
   uint8_t rgba[4];
 };
 
+// the pixel of that hit: background, or the geom shaded
+SGR_HD void sgr_geom_pixel(const float* recs, float best, int bg, const float* bh, const float* bn, const SgrCam& c, const float* d, SgrHit& r) {
+  r.geom = bg;
+  if (bg < 0) {
+    r.depth = INFINITY;
+    sgr_background(r.rgba);
+  } else {
+    r.depth = best * (d[0] * c.fwd[0] + d[1] * c.fwd[1] + d[2] * c.fwd[2]);
+    sgr_shade(recs + SGR_REC * bg, bh, bn, c, r.rgba);
+  }
+}
+
 template <typename IdxT>
 SGR_HD SgrHit sgr_trace(const float* recs, const IdxT* ids, int nids, const SgrCam& c, const float* d) {
   float best = INFINITY, bh[3] = {0, 0, 0}, bn[3] = {0, 0, 1};
@@ -249,14 +261,7 @@ SGR_HD SgrHit sgr_trace(const float* recs, const IdxT* ids, int nids, const SgrC
     }
   }
   SgrHit r;
-  r.geom = bg;
-  if (bg < 0) {
-    r.depth = INFINITY;
-    sgr_background(r.rgba);
-  } else {
-    r.depth = best * (d[0] * c.fwd[0] + d[1] * c.fwd[1] + d[2] * c.fwd[2]);
-    sgr_shade(recs + SGR_REC * bg, bh, bn, c, r.rgba);
-  }
+  sgr_geom_pixel(recs, best, bg, bh, bn, c, d, r);
   return r;
 }
 
@@ -420,13 +425,6 @@ SGR_HD SgrHit sgr_trace_skin(const float* recs, const IdxT* ids, int nids, const
     r.rgba[0] = sgr_u8(albedo[0] * f); r.rgba[1] = sgr_u8(albedo[1] * f); r.rgba[2] = sgr_u8(albedo[2] * f); r.rgba[3] = 255;
     return r;
   }
-  r.geom = bg;
-  if (bg < 0) {
-    r.depth = INFINITY;
-    sgr_background(r.rgba);
-  } else {
-    r.depth = best * (d[0] * c.fwd[0] + d[1] * c.fwd[1] + d[2] * c.fwd[2]);
-    sgr_shade(recs + SGR_REC * bg, bh, bn, c, r.rgba);
-  }
+  sgr_geom_pixel(recs, best, bg, bh, bn, c, d, r);
   return r;
 }

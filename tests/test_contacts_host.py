@@ -155,12 +155,12 @@ def test_abi_entry_points_without_a_device():
 
 
 def test_kernel_in_the_kept_assembly():
-    """sg_contacts.hip is compiled inside sg_api.hip: both instantiations of the kernel are in sg_api.device.s, the assembly check is
+    """sg_contacts_kernel.h is compiled inside sg_readout.hip: both instantiations of the kernel are in sg_readout.device.s, the assembly check is
     clean, no VGPR spills, and the scratch memory is exactly what DESIGN.md 8.1 states: the staging records and the box - box polygon
     work space live in LDS, what is left are the axis tables the shared box - box routine indexes at run time"""
     from softgrip_amd import build_native, isa_check
     build_native.build()
-    api = [f for f in build_native.device_asm_files() if os.path.basename(f) == "sg_api.device.s"]
+    api = [f for f in build_native.device_asm_files() if os.path.basename(f) == "sg_readout.device.s"]
     assert len(api) == 1
     assert not isa_check.check_asm(api[0])
     text = open(api[0]).read()

@@ -184,12 +184,12 @@ def test_abi_entry_point_without_a_device():
 
 
 def test_kernels_in_the_kept_assembly():
-    """sg_ray.hip is compiled inside sg_api.hip: both kernels are in sg_api.device.s, the assembly check is clean, and they hold what
+    """sg_ray_kernels.h is compiled inside sg_readout.hip: both kernels are in sg_readout.device.s, the assembly check is clean, and they hold what
     DESIGN.md 8.3 states: no scratch, no spills, the lane-per-ray kernel at most 64 registers (eight waves per SIMD) with 256 B of
     static LDS beside the staged records, the lanes-over-geoms kernel at most 128 registers and no LDS"""
     from softgrip_amd import build_native, isa_check
     build_native.build()
-    api = [f for f in build_native.device_asm_files() if os.path.basename(f) == "sg_api.device.s"]
+    api = [f for f in build_native.device_asm_files() if os.path.basename(f) == "sg_readout.device.s"]
     assert len(api) == 1
     assert not isa_check.check_asm(api[0])
     text = open(api[0]).read()

@@ -147,11 +147,11 @@ def test_abi_entry_points_without_a_device():
 
 
 def test_new_kernels_have_no_scratch_and_no_spills():
-    """the kept assembly (sg_kin.hip is compiled inside sg_api.hip): both kernels 0 bytes of scratch and no VGPR spills, the render
+    """the kept assembly (sg_readout.device.s: sg_kin_kernels.h is compiled inside sg_readout.hip): both kernels 0 bytes of scratch and no VGPR spills, the render
     kernel at least 4 waves per SIMD by its registers (<= 128) and its LDS (4 waves of 256-lane workgroups per SIMD = 4 per CU)"""
     from softgrip_amd import build_native
     build_native.build()
-    api = [f for f in build_native.device_asm_files() if os.path.basename(f) == "sg_api.device.s"]
+    api = [f for f in build_native.device_asm_files() if os.path.basename(f) == "sg_readout.device.s"]
     assert len(api) == 1
     text = open(api[0]).read()
     seen = {}

@@ -363,7 +363,7 @@ def test_skin_kernels_keep_no_scratch_and_five_workgroups_per_cu():
     workgroups per CU by its LDS; sg_render_kernel itself still at its 21.4 KB"""
     from softgrip_amd import build_native
     build_native.build()
-    api = [f for f in build_native.device_asm_files() if os.path.basename(f) == "sg_api.device.s"]
+    api = [f for f in build_native.device_asm_files() if os.path.basename(f) == "sg_readout.device.s"]
     assert len(api) == 1
     seen = {}
     for block in open(api[0]).read().split("  - .agpr_count:")[1:]:
