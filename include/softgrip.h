@@ -246,9 +246,26 @@ int sg_model_ncollision_pairs(const sg_model* m);
  * SG_ERR_INVALID (checked before anything touches the device): NULL batch, origin or dir; n_ids <= 0 or n_rays <= 0; an env id out of
  * range; a body id outside [-1, nbody); cat_mask outside [1, 31]; unknown flag bits; a max_dist that is not finite.
  * Two kernel layouts serve the call (a lane per ray; the lanes of a wavefront over the geoms of one ray), chosen from n_rays; the env
- * var SG_RAY_LAYOUT=rays|geoms, read per call, forces one.  Both give the same bits. */
+ * var SG_RAY_LAYOUT=rays|geoms, read per call, forces one.  Both give the same bits.
+ * SG_RAY_SKIN in `flags`, on a model with a skin (sg_model_set_skin): the rays see the soft object as the surface the renderer draws
+ * with SG_RENDER_SKIN and not as its collision capsules.
+ *   candidates   the skin's triangles when cat_mask holds SG_RAY_ELEM.  The geoms of the bodies the skin's vertices are bound to are
+ *                NEVER candidates, whatever cat_mask says (the renderer's hidden geoms).  Everything else, the centre sphere included,
+ *                is as without the flag.  ray_exclude[r] = body also removes every triangle with a vertex bound to that body.
+ *   vertices     xpos[body] + R(xquat[body]) vert_pos in fp64, from this call's poses.
+ *   hit          front faces only (counter-clockwise seen from outside): with a, b, c relative to the origin and n = (b - a) x (c - a),
+ *                n . d < 0 and t = (n . a) / (n . d) > 0 -- the entry-hit rule, so an origin inside the closed skin sees nothing of it.
+ *                A triangle seen edge-on is a miss; a hit beyond max_dist is a miss.
+ *   geomid       ngeom + face index: geomid >= ngeom means "skin, triangle geomid - ngeom".  The order is the one above -- smaller
+ *                distance, then smaller id -- so a geom wins a tie against a triangle and the smaller face index among triangles.
+ *   normal       the triangle's unit face normal n / |n|, world axes: flat, NOT interpolated (a distance sensor).
+ *   watertight   a ray that crosses the closed skin from outside hits it, also when it passes exactly through a shared edge or a
+ *                vertex: an edge's value is computed once, the endpoint of smaller vertex index first, from the vertices' coordinates in a
+ *                frame built from the ray direction, with an exact sign; zero counts as inside.
+ * An env with a pose or a vertex that is not finite gets NaN, NaN, -1 as above.  With the flag on a model WITHOUT a skin, or without
+ * the flag, the call is exactly the plain one: the same kernels, the same launch, the same bits.  Primitives beside the skin: as above. */
 enum { SG_RAY_GROUND = 1, SG_RAY_STATIC = 2, SG_RAY_FINGER = 4, SG_RAY_ELEM = 8, SG_RAY_CENTER = 16, SG_RAY_ALL = 31 };   /* cat_mask */
-enum { SG_RAY_PER_ENV = 1 };   /* flags */
+enum { SG_RAY_PER_ENV = 1, SG_RAY_SKIN = 4 };   /* flags (bit 2 is not assigned: SG_ERR_INVALID, as every unknown bit) */
 int sg_ray(sg_batch* b, const int32_t* env_ids, int n_ids, int n_rays, const double* origin, const double* dir,
            const int32_t* ray_body, const int32_t* ray_exclude, int cat_mask, double max_dist, int flags,
            double* dist, int32_t* geomid, double* normal, void* stream);

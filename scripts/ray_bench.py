@@ -10,7 +10,16 @@ The method of scripts/contacts_bench.py: each figure is a window of `reps` back-
 alternating with a window of sg_step on the same batch `rounds` times; the figure is the median window / reps.  The step windows
 advance the state, so the batch is put back on the sampled state (sg_set_state) before every window.
 
-usage: python scripts/ray_bench.py [--envs 4096] [--reps 10] [--rounds 5] [--out profiles/r08_ray_bench.json]"""
+--skin: the same method for sg_ray with SG_RAY_SKIN, on softball (implicit damper) at env step 20 of the squeeze:
+  (a) the 8 x 8 tactile map against the skin and against the capsules (the plain call), automatic choice and both forced layouts
+  (b) n_rays swept over 1 ... 1024 under both forced layouts with the flag: the crossing point of the skin path
+  (c) the plain call's (a) figures once more from another build of the library, measured in the same session: run the script with
+      --skin --plain-only under SOFTGRIP_LIB=<that build> first and hand its --out to this run as --parent-json
+  --stages: nothing is timed; the tactile map is cast `reps` times against the skin and `reps` times against the capsules, for a run
+      under `rocprofv3 --kernel-trace --stats -- python scripts/ray_bench.py --skin --stages`: the per-kernel split of the call
+
+usage: python scripts/ray_bench.py [--envs 4096] [--reps 10] [--rounds 5] [--out profiles/r08_ray_bench.json]
+       python scripts/ray_bench.py --skin [--plain-only] [--parent-json FILE] [--out profiles/r10_ray_skin_bench.json]"""
 import argparse
 import json
 import os
@@ -39,6 +48,10 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--skin", action="store_true", help="time SG_RAY_SKIN on softball at env step 20 instead")
+    ap.add_argument("--plain-only", action="store_true", help="with --skin: only the plain call's tactile map (a build without the flag can run it)")
+    ap.add_argument("--stages", action="store_true", help="with --skin: only cast the tactile map `reps` times each way (for a kernel trace)")
+    ap.add_argument("--parent-json", default=None, help="with --skin: the --plain-only result of another build, copied in under 'parent_build'")
     args = ap.parse_args()
     import torch
     import softgrip_amd as sg
@@ -49,20 +62,22 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("ray_bench.py needs a GPU: there is nothing to time without one")
     n = args.envs
-    m = sg.load_model(os.path.join(ROOT, "models", "softbox.sgmodel"), "explicit")
+    scene, damper, nstep = ("softball", "implicit", 20) if args.skin else ("softbox", "explicit", 100)
+    m = sg.load_model(os.path.join(ROOT, "models", scene + ".sgmodel"), damper)
     nm = native.NativeModel(m)
     b = native.NativeBatch(nm, n, 0)
-    b.set_stiffness(np.random.RandomState(0).uniform(300, 1400, n), list(range(11, 64)), [0])
+    if not args.skin:
+        b.set_stiffness(np.random.RandomState(0).uniform(300, 1400, n), list(range(11, 64)), [0])
     flags = torch.zeros(n, dtype=torch.int32, device=b.device)
     sens = torch.zeros(n, nm.nsensordata, dtype=torch.float64, device=b.device)
     b.reset(1, sens=sens, flags=flags)
     sched = episode_schedule()
-    for t in range(100):
+    for t in range(nstep):
         if sched[t] is not None:
-            b.set_ctrl_broadcast(np.full(2, sched[t]))
+            b.set_ctrl_broadcast(np.full(nm.nu, sched[t]))
         b.step(7, sens=sens, flags=flags)
     st = b.get_state()
-    res = {"device": torch.cuda.get_device_name(0), "scene": "softbox", "state": "env step 100", "envs": n, "ngeom": nm.ngeom, "reps": args.reps,
+    res = {"device": torch.cuda.get_device_name(0), "scene": scene, "state": "env step %d" % nstep, "envs": n, "ngeom": nm.ngeom, "reps": args.reps,
            "rounds": args.rounds, "method": "HIP events around `reps` back-to-back calls, median over `rounds` windows alternating with sg_step windows, ms per call",
            "cases": []}
 
@@ -106,11 +121,14 @@ def main():
 
         def fn():
             b._check(b.L.sg_ray(b.ptr, i32(hid), k, nr, native._ptr(o), native._ptr(d), i32(hb), i32(hb), int(kw.get("cat_mask", 31)),
-                                float(kw.get("max_dist", 0.0)), 0, native._ptr(dist), native._ptr(geom), None, b._stream()))
+                                float(kw.get("max_dist", 0.0)), int(kw.get("flags", 0)), native._ptr(dist), native._ptr(geom), None, b._stream()))
         fn.dist, fn.geom = dist, geom
         return fn
 
     dev = b.device
+    if args.skin:
+        skin_cases(args, res, m, nm, b, torch, native, tactile_rays, measure, caster)
+        return
     # (a) the tactile map's rays
     tr = tactile_rays(m, (8, 8))
     fa = caster(torch.tensor(tr["origin"].reshape(-1, 3), device=dev), torch.tensor(tr["direction"].reshape(-1, 3), device=dev), body=tr["body"].reshape(-1),
@@ -157,6 +175,63 @@ def main():
             fjson.write("\n")
     print("tactile map / one sg_step: %.3f; lanes-over-geoms faster up to %d rays per env; sg_ray / sg_render on camera rays: %.2f"
           % (res["tactile_over_step"], res["geoms_layout_faster_up_to"], res["ray_over_render"]))
+
+
+def skin_cases(args, res, m, nm, b, torch, native, tactile_rays, measure, caster):
+    """--skin: (a) the tactile map against capsules and skin, (b) the n_rays sweep with the flag, (c) the other build's plain figures"""
+    import ray_ref as RR
+    dev = b.device
+    res["library"] = os.environ.get("SOFTGRIP_LIB", "the tree's own build")
+    tr = tactile_rays(m, (8, 8))
+    ta = dict(body=tr["body"].reshape(-1), cat_mask=native.SG_RAY_ELEM | native.SG_RAY_CENTER, max_dist=float(tr["thickness"].max()) + 0.05)
+    to, td = torch.tensor(tr["origin"].reshape(-1, 3), device=dev), torch.tensor(tr["direction"].reshape(-1, 3), device=dev)
+    label = "(a) tactile_depth rays 8x8, %d rays per env, " % tr["body"].size
+    plain = caster(to, td, **ta)
+    if args.stages:
+        nm.set_skin(m.composite_skin())
+        skin = caster(to, td, flags=native.SG_RAY_SKIN, **ta)
+        for _ in range(args.reps):
+            skin()
+            plain()
+        torch.cuda.synchronize()
+        return
+    for lay in (None, "rays", "geoms"):
+        c = measure(label + "capsules (plain call)", plain, lay, {"skin": False})
+        c["hit_fraction"] = float((plain.geom >= 0).float().mean())
+    if not args.plain_only:
+        if nm.skin() is None:
+            nm.set_skin(m.composite_skin())
+        res["skin"] = {"nvert": int(len(nm.skin()["vert_body"])), "nface": int(len(nm.skin()["face"]))}
+        skin = caster(to, td, flags=native.SG_RAY_SKIN, **ta)
+        for lay in (None, "rays", "geoms"):
+            c = measure(label + "skin (SG_RAY_SKIN)", skin, lay, {"skin": True})
+            c["hit_fraction"] = float((skin.geom >= 0).float().mean())
+            c["skin_hit_fraction"] = float((skin.geom >= nm.ngeom).float().mean())
+        gx = b.poses([0])["geom_xpos"][0].cpu().numpy()
+        o, d = RR.scene_rays(gx, np.asarray(m.geom_type), 1024, 3)
+        ot, dt = torch.tensor(o, device=dev), torch.tensor(d, device=dev)
+        counts = (1, 4, 16, 32, 64, 128, 256, 1024)
+        sweep = {}
+        for nr in counts:
+            for lay in ("rays", "geoms"):
+                f = caster(ot[:nr].contiguous(), dt[:nr].contiguous(), flags=native.SG_RAY_SKIN)
+                sweep[(nr, lay)] = measure("(b) %d world-frame rays per env, skin" % nr, f, lay, {"n_rays": nr, "skin": True})["ms"]
+        res["sweep_ms"] = {"%d" % nr: {lay: sweep[(nr, lay)] for lay in ("rays", "geoms")} for nr in counts}
+        res["geoms_layout_faster_up_to"] = max([nr for nr in counts if sweep[(nr, "geoms")] < sweep[(nr, "rays")]], default=0)
+        auto = [c for c in res["cases"] if c["case"].startswith("(a)") and c["layout"] == "automatic"]
+        res["skin_tactile_over_step"] = [c for c in auto if c["skin"]][0]["over_step"]
+        res["skin_over_capsules"] = [c for c in auto if c["skin"]][0]["ms"] / [c for c in auto if not c["skin"]][0]["ms"]
+    if args.parent_json:
+        with open(args.parent_json) as f:
+            parent = json.load(f)
+        res["parent_build"] = {"what": "(c) the plain call's tactile map from the parent commit's build of the library, same session, same method",
+                               "cases": [c for c in parent["cases"] if c["case"].startswith("(a)")]}
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fjson:
+            json.dump(res, fjson, indent=1)
+            fjson.write("\n")
+    print(json.dumps({k: v for k, v in res.items() if k not in ("cases", "parent_build")}))
 
 
 if __name__ == "__main__":

@@ -96,6 +96,9 @@ struct sg_batch {
   // ray queries: the poses of the last call's envs and its rays' body / exclude ids
   SgScratch<double> ray_xpos, ray_xquat, ray_gxpos, ray_gxmat;   // [n_ids][nbody][3 | 4], [n_ids][ngeom][3 | 9]
   SgScratch<int> ray_ids;                                         // [2][n_rays]
+  SgScratch<double> ray_vtx;                                      // [n_ids][nvert][3] the skin's vertices of the last SG_RAY_SKIN call
+  const int* skin_vis = nullptr;                                  // [skin_nvis] the geoms the skin does not replace (in skin_mem, with skin_dev)
+  int skin_nvis = 0;
   ~sg_batch() {   // (on the batch's device: sg_batch_destroy.  The arenas and scratch buffers free themselves)
     for (auto& e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (auto& e : ev_pgs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }

@@ -10,6 +10,7 @@
 #include "sg_kin_kernels.h"
 #include "sg_contacts_kernel.h"
 #include "sg_ray_kernels.h"
+#include "sg_ray_skin_kernels.h"
 
 // ---- the builders sg_model_create calls (sg_readout.h) ----
 // an array of the blob as `var`, its length in c (want >= 0: that many elements), or the builder ends with T->err set
@@ -222,8 +223,9 @@ struct Readout {
 };
 
 // the skin's tables on the batch's device, uploaded again when the model's skin has changed since (an earlier skin render, on whatever
-// stream it went out, may still read the old ones: the device is waited for first -- once per sg_model_set_skin, not per render)
-static int skin_prepare(sg_batch* b) {
+// stream it went out, may still read the old ones: the device is waited for first -- once per sg_model_set_skin, not per render).  fn: the
+// calling entry point's name (sg_render_ex, sg_ray)
+static int skin_prepare(sg_batch* b, const char* fn) {
   const SgSkinHost& S = b->m->skin;
   if (b->skin_version == S.version) return SG_OK;
   const SgKinHost& K = b->m->kin;
@@ -233,15 +235,19 @@ static int skin_prepare(sg_batch* b) {
   b->skin_version = 0;
   b->skin_mem.release();
   SgArena& A = b->skin_mem;
-  int *vb = nullptr, *as = nullptr, *ad = nullptr, *hid = nullptr;
+  int *vb = nullptr, *as = nullptr, *ad = nullptr, *hid = nullptr, *vis = nullptr;
+  std::vector<int> visible;   // (sg_ray with SG_RAY_SKIN stages these alone)
+  for (int g = 0; g < K.o.ngeom; g++)
+    if (!T.hidden[g]) visible.push_back(g);
   double* vp = nullptr;
   uint32_t* fc = nullptr;
   if (!(A.upload(&vb, S.vert_body) && A.upload(&vp, S.vert_pos) && A.upload(&fc, T.faces) && A.upload(&as, T.adj_start) && A.upload(&ad, T.adj) &&
-        A.upload(&hid, T.hidden))) {
+        A.upload(&hid, T.hidden) && A.upload(&vis, visible))) {
     const bool nomem = A.nomem;
     A.release();
-    return devmem_fail(nomem, "sg_render_ex (skin tables)");
+    return devmem_fail(nomem, std::string(fn) + " (skin tables)");
   }
+  b->skin_vis = vis; b->skin_nvis = (int)visible.size();
   SgSkinDev& d = b->skin_dev;
   d.vert_body = vb; d.vert_pos = vp; d.faces = fc; d.adj_start = as; d.adj = ad; d.hidden = hid;
   d.nvert = S.nvert; d.nface = S.nface;
@@ -267,7 +273,7 @@ static int render(const char* fn, bool skin, sg_batch* b, const double* cam, con
   Readout r{b, fn, (hipStream_t)stream};
   if (int rc = r.prepare(env_ids, n_ids)) return rc;
   if (skin)
-    if (int rc = skin_prepare(b)) return rc;
+    if (int rc = skin_prepare(b, fn)) return rc;
   if (int rc = r.reserve(b->rrecs, (size_t)n_ids * K.o.ngeom * SGR_REC, "geom records")) return rc;
   if (skin) {
     if (int rc = r.reserve(b->skin_xpos, (size_t)n_ids * K.o.nbody * 3, "body poses")) return rc;
@@ -431,13 +437,15 @@ int sg_get_contacts(sg_batch* b, const int32_t* env_ids, int n_ids, int max_cont
 // Which layout a call gets: lanes over geoms below SG_RAY_CROSSOVER rays per env, lane per ray from there on.  Measured (DESIGN.md 8.3,
 // profiles/r08_ray_bench.json; 4096 envs, softbox): lanes over geoms wins at 16 rays per env (0.18 against 0.33 ms) and loses at 64 (0.55
 // against 0.40 ms); the two lines cross near 34.  SG_RAY_LAYOUT=rays|geoms, read per call, forces one (the tests run both at every shape).
+// With SG_RAY_SKIN on a model that has a skin the siblings of sg_ray_skin_kernels.h run: sg_kin_kernel, the vertex kernel, one
+// of the two layouts, chosen by the same constant.
 #define SG_RAY_CROSSOVER 32
 int sg_ray(sg_batch* b, const int32_t* env_ids, int n_ids, int n_rays, const double* origin, const double* dir, const int32_t* ray_body,
            const int32_t* ray_exclude, int cat_mask, double max_dist, int flags, double* dist, int32_t* geomid, double* normal, void* stream) {
   // (argument checks first, in an order that lets most be reached without a device)
   if (n_ids <= 0 || n_rays <= 0) return fail(SG_ERR_INVALID, "sg_ray: n_ids and n_rays must be positive");
   if (cat_mask < 1 || cat_mask > SG_RAY_ALL) return fail(SG_ERR_INVALID, "sg_ray: cat_mask outside [1, 31]");
-  if (flags & ~SG_RAY_PER_ENV) return fail(SG_ERR_INVALID, "sg_ray: unknown flag bits");
+  if (flags & ~(SG_RAY_PER_ENV | SG_RAY_SKIN)) return fail(SG_ERR_INVALID, "sg_ray: unknown flag bits");
   if (!std::isfinite(max_dist)) return fail(SG_ERR_INVALID, "sg_ray: max_dist must be finite (<= 0: unlimited)");
   if (!b || !origin || !dir) return fail(SG_ERR_INVALID, "sg_ray: null batch, origin or dir");
   const SgKinHost& K = b->m->kin;
@@ -450,10 +458,15 @@ int sg_ray(sg_batch* b, const int32_t* env_ids, int n_ids, int n_rays, const dou
     return fail(SG_ERR_MODEL, "sg_ray: geom type " + std::to_string(K.bad_type) + " has no ray intersection (plane, sphere, capsule and box only)");
   if (K.ok && K.o.ngeom > SGY_MAXGEOM) return fail(SG_ERR_MODEL, "sg_ray: more than " + std::to_string(SGY_MAXGEOM) + " geoms");
   if ((long long)n_ids * n_rays > 0x7fffffffll) return fail(SG_ERR_INVALID, "sg_ray: too many envs x rays for one launch");
+  const bool skin = (flags & SG_RAY_SKIN) && b->m->skin.nvert != 0;   // (a model without a skin: the plain call)
   Readout r{b, "sg_ray", (hipStream_t)stream};
   if (int rc = r.prepare(env_ids, n_ids)) return rc;
   if (!dist && !geomid && !normal) return SG_OK;
   const size_t nb = K.o.nbody, ng = K.o.ngeom;
+  if (skin) {
+    if (int rc = skin_prepare(b, "sg_ray")) return rc;
+    if (int rc = r.reserve(b->ray_vtx, (size_t)n_ids * b->skin_dev.nvert * 3, "skin vertices")) return rc;
+  }
   if (int rc = r.reserve(b->ray_xpos, (size_t)n_ids * nb * 3, "body poses")) return rc;
   if (int rc = r.reserve(b->ray_xquat, (size_t)n_ids * nb * 4, "body poses")) return rc;
   if (int rc = r.reserve(b->ray_gxpos, (size_t)n_ids * (ng ? ng : 1) * 3, "geom poses")) return rc;
@@ -476,7 +489,22 @@ int sg_ray(sg_batch* b, const int32_t* env_ids, int n_ids, int n_rays, const dou
     else if (!strcmp(forced, "geoms")) by_geoms = true;
     else if (*forced) return fail(SG_ERR_INVALID, "sg_ray: SG_RAY_LAYOUT must be rays or geoms");
   }
-  if (by_geoms) {
+  if (skin) {
+    const SgSkinDev& S = b->skin_dev;
+    SgSkinRayVertArgs V;
+    V.vert_body = S.vert_body; V.vert_pos = S.vert_pos; V.xpos = a.xpos; V.xquat = a.xquat; V.nvert = S.nvert; V.nbody = K.o.nbody; V.vtx = b->ray_vtx.p;
+    hipLaunchKernelGGL(sg_skinray_vert_kernel, dim3(n_ids), dim3(256), 0, r.s, V);
+    HIPCHK(hipGetLastError());
+    SgSkinRayArgs A;
+    A.r = a; A.vtx = b->ray_vtx.p; A.faces = S.faces; A.vert_body = S.vert_body; A.hidden = S.hidden; A.vis = b->skin_vis;
+    A.nvert = S.nvert; A.nface = S.nface; A.nvis = b->skin_nvis;
+    if (by_geoms) {
+      hipLaunchKernelGGL(sg_skinray_geoms_kernel, dim3((unsigned)((long long)n_ids * n_rays)), dim3(64), 0, r.s, A);
+    } else {
+      const int nblk = (n_rays + 255) / 256;
+      hipLaunchKernelGGL(sg_skinray_rays_kernel, dim3((unsigned)((long long)n_ids * nblk)), dim3(256), sg_skinray_lds(A.nvis, A.nvert, A.nface), r.s, A, nblk);
+    }
+  } else if (by_geoms) {
     hipLaunchKernelGGL(sg_ray_geoms_kernel, dim3((unsigned)((long long)n_ids * n_rays)), dim3(64), 0, r.s, a);
   } else {
     const int nblk = (n_rays + 255) / 256;

@@ -402,12 +402,16 @@ class ManEnv(Env):
         out["geom_names"] = [n or "" for n in self.model.geom_names]
         return out
 
-    def raycast(self, origin, direction, body=None, exclude=None, env_ids=None, cat_mask=native.SG_RAY_ALL, max_dist=0.0, normals=False):
+    def raycast(self, origin, direction, body=None, exclude=None, env_ids=None, cat_mask=native.SG_RAY_ALL, max_dist=0.0, normals=False, skin=False):
         """ray queries on the current state (mj_ray; sg_ray): NativeBatch.raycast's arguments and dict of device tensors (dist [k, R],
-        geom [k, R], normal [k, R, 3] with normals=True)"""
-        return self.env.raycast(origin, direction, body=body, exclude=exclude, env_ids=env_ids, cat_mask=cat_mask, max_dist=max_dist, normals=normals)
+        geom [k, R], normal [k, R, 3] with normals=True).  skin=True (SG_RAY_SKIN): the soft object is seen as its skin (the scene's
+        <skin>, else the one built from the composite's body names; the plain call when there is none) -- its triangles are candidates
+        with SG_RAY_ELEM in cat_mask, the element geoms never; front faces only, t > 0, watertight on shared edges and vertices;
+        geom = ngeom + face index there (a geom wins a tie), normal = the flat face normal, and ``face`` [k, R] (-1 off the skin) is added"""
+        return self.env.raycast(origin, direction, body=body, exclude=exclude, env_ids=env_ids, cat_mask=cat_mask, max_dist=max_dist, normals=normals,
+                                skin=skin)
 
-    def tactile_depth(self, res=(8, 8), max_gap=0.05, env_ids=None, faces=None, cat_mask=native.SG_RAY_ELEM | native.SG_RAY_CENTER):
+    def tactile_depth(self, res=(8, 8), max_gap=0.05, env_ids=None, faces=None, cat_mask=native.SG_RAY_ELEM | native.SG_RAY_CENTER, skin=False):
         """A tactile depth map of the finger pads: for every moving finger box (sg_model_nboxes, its order) a res = (W, H) grid of
         distances from the pad's face to the object surface in front of it.  Returns dict(gap [k, nboxes, H, W] float64 device tensor:
         metres, NEGATIVE where the object has pushed into the pad (the penetration depth), +inf where nothing lies within max_gap;
@@ -417,7 +421,12 @@ class ManEnv(Env):
         docstring so that a C caller can build the same -- cast with ray_body = ray_exclude = the box's body, cat_mask (default: the
         soft object's elements and centre) and max_dist = max over boxes of 2 s[a] + max_gap.  A ray starts on the face opposite the
         pad and crosses the box from inside (an origin inside a geom does not see it, and the box's body is excluded), so
-        gap = dist - 2 s[a]."""
+        gap = dist - 2 s[a].
+
+        skin=True: the same rays, exclusion, max_dist and gap formula against the soft object's SKIN (raycast(skin=True): the surface
+        a depth-type sensor sees) and not against the element capsules the solver collides with: the triangles are candidates with
+        SG_RAY_ELEM in cat_mask, front faces only, watertight; geom is then ngeom + face index on the skin and the dict carries
+        ``face`` [k, nboxes, H, W] int32 (the triangle seen, -1 off the skin or for none) next to it."""
         import torch
         key = (tuple(int(r) for r in res), None if faces is None else tuple((int(a), int(s)) for a, s in faces))
         cache = self.__dict__.setdefault("_tactile_cache", {})
@@ -433,15 +442,21 @@ class ManEnv(Env):
         max_gap = float(max_gap)
         if B == 0:
             k = self.n_envs if env_ids is None else len(env_ids)
-            return dict(gap=torch.empty(k, 0, H, W, dtype=torch.float64, device=self.env.device), geom=torch.empty(k, 0, H, W, dtype=torch.int32, device=self.env.device))
+            empty = dict(gap=torch.empty(k, 0, H, W, dtype=torch.float64, device=self.env.device), geom=torch.empty(k, 0, H, W, dtype=torch.int32, device=self.env.device))
+            if skin:
+                empty["face"] = torch.empty_like(empty["geom"])
+            return empty
         out = self.env.raycast(ent["origin"], ent["direction"], body=ent["body"], exclude=ent["body"], env_ids=env_ids, cat_mask=cat_mask,
-                               max_dist=float(ent["thickness"].max()) + max_gap)
+                               max_dist=float(ent["thickness"].max()) + max_gap, skin=skin)
         dist = out["dist"].view(-1, B, H, W)
         geom = out["geom"].view(-1, B, H, W)
         gap = dist - ent["thick_t"].view(1, B, 1, 1)
         seen = (dist >= 0) & (gap <= max_gap)
         inf = torch.full_like(gap, float("inf"))
-        return dict(gap=torch.where(seen | torch.isnan(dist), gap, inf), geom=torch.where(seen, geom, torch.full_like(geom, -1)))
+        res_ = dict(gap=torch.where(seen | torch.isnan(dist), gap, inf), geom=torch.where(seen, geom, torch.full_like(geom, -1)))
+        if skin:
+            res_["face"] = torch.where(seen, out["face"].view(-1, B, H, W), torch.full_like(geom, -1))
+        return res_
 
     # ---- fused episode: the create_dataset.py schedule without a host round trip per step ----
     def rollout(self, schedule, out=None, reset=True):

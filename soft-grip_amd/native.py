@@ -29,6 +29,7 @@ SG_RENDER_SKIN = 1
 # sg_ray: category bits of cat_mask (ground plane, static, moving finger box, shell element, centre sphere) and flags
 SG_RAY_GROUND, SG_RAY_STATIC, SG_RAY_FINGER, SG_RAY_ELEM, SG_RAY_CENTER, SG_RAY_ALL = 1, 2, 4, 8, 16, 31
 SG_RAY_PER_ENV = 1
+SG_RAY_SKIN = 4
 SG_COMPILE_NO_NEIGHBORS, SG_COMPILE_IMPLICIT_TENDON_DAMPER = 1, 2
 
 
@@ -309,15 +310,27 @@ class NativeBatch:
         self._check(self.L.sg_get_contacts(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, mc, _ptr(out.get("ncon")),
                                            _ptr(out.get("geom")), _ptr(out.get("dist")), _ptr(out.get("pos")), _ptr(out.get("frame")), self._stream()))
 
-    def raycast(self, origin, direction, body=None, exclude=None, env_ids=None, cat_mask=SG_RAY_ALL, max_dist=0.0, normals=False):
+    def raycast(self, origin, direction, body=None, exclude=None, env_ids=None, cat_mask=SG_RAY_ALL, max_dist=0.0, normals=False, skin=False):
         """mj_ray for the listed envs (None: all) on the current state (sg_ray).  origin / direction: float64 device tensors [R, 3] --
         the same rays for every env -- or [k, R, 3], rays of their own per listed env; directions need not be unit.  body / exclude:
         R ints (host) or None: the body whose frame ray r is given in and follows (-1: world) and the body whose geoms it does not see
         (-1: none).  cat_mask: SG_RAY_* bits of the geom categories that are candidates; max_dist <= 0: unlimited.  Returns a dict of
         device tensors dist [k, R] float64 (metres, -1: miss), geom [k, R] int32 (-1: miss) and, with normals=True, normal [k, R, 3]
         (outward, world axes, zeros for a miss).  Entry hits only: an origin inside a geom does not see that geom.  An env whose qpos
-        is not finite gets NaN / -1."""
+        is not finite gets NaN / -1.
+
+        skin=True (SG_RAY_SKIN): the rays see the soft object as its skin and not as its element geoms; a model without one gets
+        ``model.composite_skin()`` attached first, and the call is the plain one when there is none.  The skin's triangles are
+        candidates when cat_mask holds SG_RAY_ELEM; the geoms of the bodies its vertices are bound to never are; exclude[r] also
+        removes the triangles with a vertex bound to that body.  Front faces only (counter-clockwise seen from outside, t > 0: an
+        origin inside the closed skin sees nothing of it), watertight on shared edges and vertices.  ``geom`` is then the raw id --
+        ngeom + face index on the skin, where a geom wins a tie against a triangle and the smaller face index among triangles --
+        ``normal`` the flat unit face normal there, and the dict gains ``face`` [k, R] int32: geom - ngeom on skin hits, -1 elsewhere."""
         t = self.torch
+        if skin and self.nmodel.skin() is None and hasattr(self.nmodel.model, "composite_skin"):
+            made = self.nmodel.model.composite_skin()
+            if made is not None:
+                self.nmodel.set_skin(made)
         ids, k = self._ids(env_ids)
         assert origin.is_cuda and direction.is_cuda and origin.dtype == t.float64 and direction.dtype == t.float64
         assert origin.shape == direction.shape and origin.shape[-1] == 3 and origin.dim() in (2, 3), origin.shape
@@ -333,7 +346,11 @@ class NativeBatch:
             out["normal"] = t.empty(k, nr, 3, dtype=t.float64, device=self.device)
         i32 = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
         self._check(self.L.sg_ray(self.ptr, i32(ids), k, nr, _ptr(origin), _ptr(direction), i32(hb), i32(hx), int(cat_mask), float(max_dist),
-                                  SG_RAY_PER_ENV if per_env else 0, _ptr(out["dist"]), _ptr(out["geom"]), _ptr(out.get("normal")), self._stream()))
+                                  (SG_RAY_PER_ENV if per_env else 0) | (SG_RAY_SKIN if skin else 0), _ptr(out["dist"]), _ptr(out["geom"]),
+                                  _ptr(out.get("normal")), self._stream()))
+        if skin:
+            ng = self.nmodel.ngeom
+            out["face"] = t.where(out["geom"] >= ng, out["geom"] - ng, t.full_like(out["geom"], -1))
         return out
 
     def render(self, camera=None, env_ids=None, width=320, height=240, rgb=True, depth=True, seg=True, skin=False):
