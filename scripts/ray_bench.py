@@ -14,13 +14,19 @@ advance the state, so the batch is put back on the sampled state (sg_set_state) 
   (a) the 8 x 8 tactile map against the skin and against the capsules (the plain call), automatic choice and both forced layouts
   (b) n_rays swept over 1 ... 1024 under both forced layouts with the flag: the crossing point of the skin path
   (c) the plain call's (a) figures once more from another build of the library, measured in the same session: run the script with
-      --skin --plain-only under SOFTGRIP_LIB=<that build> first and hand its --out to this run as --parent-json
+      --skin --plain-only under SOFTGRIP_LIB=<that build> first and hand its --out to this run as --parent-json (of a full --skin result
+      only the plain call's cases are copied)
   --stages: nothing is timed; the tactile map is cast `reps` times against the skin and `reps` times against the capsules, for a run
       under `rocprofv3 --kernel-trace --stats -- python scripts/ray_bench.py --skin --stages`: the per-kernel split of the call
+
+Every timed query's outputs (dist, geom ids and, written by that call alone, the normals) are hashed (SHA-256, one more call on the
+sampled state) into its case; with --parent-json
+FILE, the result of the same command under SOFTGRIP_LIB=<another build>, the digests are compared case by case: SAME or DIFFERENT.
 
 usage: python scripts/ray_bench.py [--envs 4096] [--reps 10] [--rounds 5] [--out profiles/r08_ray_bench.json]
        python scripts/ray_bench.py --skin [--plain-only] [--parent-json FILE] [--out profiles/r10_ray_skin_bench.json]"""
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -42,6 +48,31 @@ def window(torch, fn, reps):
     return a.elapsed_time(b) / reps
 
 
+def digest(torch, fn):
+    """SHA-256 of what a timed query wrote (its `outputs`: device tensors), None for a call without any"""
+    outs = getattr(fn, "outputs", ())
+    if not outs:
+        return None
+    torch.cuda.synchronize()
+    h = hashlib.sha256()
+    for t in outs:
+        h.update(t.cpu().numpy().tobytes())
+    return h.hexdigest()
+
+
+def bits_against(res, parent):
+    """per case of this run that the other build's run has too: SAME or DIFFERENT output digests; printed, and kept under 'bits_vs_parent'"""
+    theirs = {(c["case"], c["layout"]): c.get("sha256") for c in parent["cases"]}
+    out = []
+    for c in res["cases"]:
+        key = (c["case"], c["layout"])
+        if c.get("sha256") and theirs.get(key):
+            out.append({"case": key[0], "layout": key[1], "bits": "SAME" if c["sha256"] == theirs[key] else "DIFFERENT"})
+            print("%-9s %s [%s]" % (out[-1]["bits"], key[0], key[1]), flush=True)
+    res["bits_vs_parent"] = {"library": parent.get("library"), "cases": out, "different": sum(x["bits"] == "DIFFERENT" for x in out)}
+    print("bits against the other build: %d cases, %d DIFFERENT" % (len(out), res["bits_vs_parent"]["different"]), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
@@ -51,7 +82,8 @@ def main():
     ap.add_argument("--skin", action="store_true", help="time SG_RAY_SKIN on softball at env step 20 instead")
     ap.add_argument("--plain-only", action="store_true", help="with --skin: only the plain call's tactile map (a build without the flag can run it)")
     ap.add_argument("--stages", action="store_true", help="with --skin: only cast the tactile map `reps` times each way (for a kernel trace)")
-    ap.add_argument("--parent-json", default=None, help="with --skin: the --plain-only result of another build, copied in under 'parent_build'")
+    ap.add_argument("--parent-json", default=None, help="the result of another build (SOFTGRIP_LIB): its output digests are compared with this "
+                    "run's, case by case; with --skin its plain tactile map figures are copied in under 'parent_build'")
     args = ap.parse_args()
     import torch
     import softgrip_amd as sg
@@ -79,7 +111,7 @@ def main():
     st = b.get_state()
     res = {"device": torch.cuda.get_device_name(0), "scene": scene, "state": "env step %d" % nstep, "envs": n, "ngeom": nm.ngeom, "reps": args.reps,
            "rounds": args.rounds, "method": "HIP events around `reps` back-to-back calls, median over `rounds` windows alternating with sg_step windows, ms per call",
-           "cases": []}
+           "library": "another build (SOFTGRIP_LIB)" if os.environ.get("SOFTGRIP_LIB") else "the tree's own build", "cases": []}
 
     def restore():
         b.set_state(qpos=st["qpos"], qvel=st["qvel"], act=st["act"], qacc_warmstart=st["qacc_warmstart"], ctrl=st["ctrl"])
@@ -98,9 +130,11 @@ def main():
             tr.append(window(torch, fn, args.reps))
             ts.append(window(torch, lambda: b.step(7, sens=sens, flags=flags), args.reps))
         restore()
+        getattr(fn, "full", fn)()  # (once more on the sampled state, the normals written too, for the digest)
+        sha = digest(torch, fn)
         os.environ.pop("SG_RAY_LAYOUT", None)
         case = {"case": label, "layout": layout or "automatic", "ms": float(np.median(tr)), "ms_windows": [float(x) for x in tr],
-                "step_ms": float(np.median(ts)), "step_ms_windows": [float(x) for x in ts]}
+                "step_ms": float(np.median(ts)), "step_ms_windows": [float(x) for x in ts], "sha256": sha}
         case["over_step"] = case["ms"] / case["step_ms"]
         case.update(extra or {})
         res["cases"].append(case)
@@ -119,10 +153,13 @@ def main():
         i32 = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
         hid = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32)
 
-        def fn():
+        normal = torch.empty(k, nr, 3, dtype=torch.float64, device=b.device)
+
+        def fn(nrm=None):
             b._check(b.L.sg_ray(b.ptr, i32(hid), k, nr, native._ptr(o), native._ptr(d), i32(hb), i32(hb), int(kw.get("cat_mask", 31)),
-                                float(kw.get("max_dist", 0.0)), int(kw.get("flags", 0)), native._ptr(dist), native._ptr(geom), None, b._stream()))
+                                float(kw.get("max_dist", 0.0)), int(kw.get("flags", 0)), native._ptr(dist), native._ptr(geom), nrm, b._stream()))
         fn.dist, fn.geom = dist, geom
+        fn.full, fn.outputs = (lambda: fn(native._ptr(normal))), (dist, geom, normal)     # (the timed call writes no normals; the hashed one does)
         return fn
 
     dev = b.device
@@ -168,6 +205,9 @@ def main():
     a_auto = [c for c in res["cases"] if c["case"].startswith("(a)") and c["layout"] == "automatic"][0]
     res["tactile_over_step"] = a_auto["over_step"]
     res["tactile_costs_less_than_one_step"] = a_auto["ms"] < a_auto["step_ms"]
+    if args.parent_json:
+        with open(args.parent_json) as f:
+            bits_against(res, json.load(f))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as fjson:
@@ -181,7 +221,6 @@ def skin_cases(args, res, m, nm, b, torch, native, tactile_rays, measure, caster
     """--skin: (a) the tactile map against capsules and skin, (b) the n_rays sweep with the flag, (c) the other build's plain figures"""
     import ray_ref as RR
     dev = b.device
-    res["library"] = os.environ.get("SOFTGRIP_LIB", "the tree's own build")
     tr = tactile_rays(m, (8, 8))
     ta = dict(body=tr["body"].reshape(-1), cat_mask=native.SG_RAY_ELEM | native.SG_RAY_CENTER, max_dist=float(tr["thickness"].max()) + 0.05)
     to, td = torch.tensor(tr["origin"].reshape(-1, 3), device=dev), torch.tensor(tr["direction"].reshape(-1, 3), device=dev)
@@ -225,7 +264,8 @@ def skin_cases(args, res, m, nm, b, torch, native, tactile_rays, measure, caster
         with open(args.parent_json) as f:
             parent = json.load(f)
         res["parent_build"] = {"what": "(c) the plain call's tactile map from the parent commit's build of the library, same session, same method",
-                               "cases": [c for c in parent["cases"] if c["case"].startswith("(a)")]}
+                               "cases": [c for c in parent["cases"] if c["case"].startswith("(a)") and not c.get("skin")]}
+        bits_against(res, parent)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as fjson:

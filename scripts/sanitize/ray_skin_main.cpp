@@ -1,5 +1,5 @@
-// The host walk of sg_ray with SG_RAY_SKIN (csrc/sg_ray_skin.h + sg_ray.h) under AddressSanitizer and UBSan: a stand-alone program, nothing
-// of it is loaded into python.  tests/test_ray_skin_host.py builds and runs it:
+// The walk of sg_ray with SG_RAY_SKIN (csrc/sg_ray_walk.h over sg_ray_skin.h + sg_ray.h: the text the kernels compile) under AddressSanitizer
+// and UBSan: a stand-alone program, nothing of it is loaded into python.  tests/test_ray_skin_host.py builds and runs it:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I soft-grip_amd/csrc scripts/sanitize/ray_skin_main.cpp
 // Skins: none at all, one face, and the limits (256 vertices, 512 faces); every array has exactly the size the walk may read, so one
 // element past an end is a report.  Both reduction orders (the two kernel layouts) must agree bit for bit.
@@ -7,7 +7,7 @@
 #include <cstring>
 #include <vector>
 
-#include "sg_ray_skin.h"
+#include "sg_ray_walk.h"
 
 struct Scene {
   int ng = 0, nvert = 0, nface = 0;
@@ -16,46 +16,11 @@ struct Scene {
   std::vector<uint32_t> faces;       // [nface]
 };
 
+// one ray through the shared walk (csrc/sg_ray_walk.h: the text the kernels compile); layout: which kernel layout's walkers
 static void walk(const Scene& S, int layout, const double* o_in, const double* d_in, int excl, int cat_mask, double limit, double* dist, int* geom, double* n) {
-  double o[3], d[3];
-  const bool live = sgy_map_ray(nullptr, nullptr, o_in, d_in, o, d);
-  const bool tris = (cat_mask >> SGYS_CAT_ELEM) & 1;
-  SgysFrame fr = {};
-  if (live) sgys_frame(d, &fr);
-  auto geom_at = [&](int g, SgyBest* b) {
-    if (!S.hidden[g]) sgy_visit(g, &S.recs[(size_t)SGY_REC * g], o, d, cat_mask, excl, limit, b);
-  };
-  auto face_at = [&](int f, SgyBest* b) {
-    int ia, ib, ic;
-    sgys_face(S.faces[f], &ia, &ib, &ic);
-    sgys_visit(S.ng + f, &S.verts[3 * ia], ia, &S.verts[3 * ib], ib, &S.verts[3 * ic], ic, S.vbody.data(), fr, o, d, excl, b);
-  };
-  SgyBest best = {INFINITY, -1, 0};
-  if (live && layout == 0) {
-    for (int g = 0; g < S.ng; g++) geom_at(g, &best);
-    for (int f = 0; tris && f < S.nface; f++) face_at(f, &best);
-  } else if (live) {
-    SgyBest w[64];
-    for (int l = 0; l < 64; l++) {
-      w[l] = SgyBest{INFINITY, -1, 0};
-      for (int g = l; g < S.ng; g += 64) geom_at(g, &w[l]);
-      for (int f = l; tris && f < S.nface; f += 64) face_at(f, &w[l]);
-    }
-    for (int m = 32; m >= 1; m >>= 1) {
-      SgyBest nx[64];
-      for (int l = 0; l < 64; l++) nx[l] = sgy_better(w[l ^ m].t, w[l ^ m].geom, w[l].t, w[l].geom) ? w[l ^ m] : w[l];
-      for (int l = 0; l < 64; l++) w[l] = nx[l];
-    }
-    best = w[0];
-  }
-  if (best.geom >= S.ng) {
-    int ia, ib, ic;
-    sgys_face(S.faces[best.geom - S.ng], &ia, &ib, &ic);
-    sgys_finish(best, &S.verts[3 * ia], &S.verts[3 * ib], &S.verts[3 * ic], limit, dist, geom, n);
-  } else {
-    const double none[SGY_REC] = {0};
-    sgy_finish(best, best.geom >= 0 ? &S.recs[(size_t)SGY_REC * best.geom] : none, o, d, limit, dist, geom, n);
-  }
+  SgywHostGeoms G = {S.recs.data(), S.hidden.data(), S.ng};
+  const SgywSkin K = {S.verts.data(), S.faces.data(), S.vbody.data(), S.nface};
+  sgyw_host_ray(G, K, layout, nullptr, nullptr, o_in, d_in, excl, cat_mask, limit, dist, geom, n);
 }
 
 // a closed-ish surface: a (rows x cols) grid of vertices wrapped on a unit sphere about (0, 0, 1), two triangles per cell, wound outward

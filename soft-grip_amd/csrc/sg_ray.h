@@ -1,8 +1,9 @@
-// sg_ray.h -- the per-ray math of sg_ray (mj_ray in fp64): ray - primitive intersection, hit normal, bounding-sphere early-out, the body
-// frame -> world map of a ray and the walk over an env's geoms.
+// sg_ray.h -- the per-(ray, geom) math of sg_ray (mj_ray in fp64): ray - primitive intersection, hit normal, bounding-sphere early-out, the body
+// frame -> world map of a ray, one visit of a walker and the order hits are reduced by.  The traversal itself is sg_ray_walk.h.
 //
-// Plain C++ that both layouts of the ray kernel (sg_ray_kernels.h) run and tests/test_ray_host.py compiles with g++ against an independent NumPy
-// caster (tests/ray_ref.py).  The renderer's header (sg_render.h) is NOT shared: its rays leave one eye in fp32 and its records are relative
+// Plain C++: the ray kernels compile it for the device (sg_ray_kernels.h, sg_ray_skin_kernels.h), and through sg_ray_walk.h the g++ build of
+// tests/ray_ref.py (tests/test_ray_host.py, against that file's independent NumPy caster) and scripts/sanitize/ray_skin_main.cpp for the
+// host.  The renderer's header (sg_render.h) is NOT shared: its rays leave one eye in fp32 and its records are relative
 // to that eye; a ray query has any origin, per env, and needs fp64 (millimetre gaps 1.7 m from the world origin).
 //
 // A geom is one record of SGY_REC doubles (128 B), world frame:

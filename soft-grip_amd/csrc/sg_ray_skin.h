@@ -1,6 +1,6 @@
 // sg_ray_skin.h -- the per-(ray, triangle) math of sg_ray with SG_RAY_SKIN: the soft object's skin (sg_skin.h: triangles bound to bodies) as
-// candidates of a ray query, in fp64.  Plain C++ like sg_ray.h: both layouts of the skin ray kernels (sg_ray_skin_kernels.h) run it and
-// tests/test_ray_skin_host.py compiles it with g++ against an independent NumPy caster (tests/ray_skin_ref.py).
+// candidates of a ray query, in fp64.  Plain C++ like sg_ray.h, and compiled by the same three: the ray kernels (sg_ray_skin_kernels.h), the g++ test build (tests/test_ray_skin_host.py, against the NumPy caster tests/ray_skin_ref.py) and the sanitizer
+// program -- all but the lane-per-ray kernel through the traversal in sg_ray_walk.h.
 //
 // Rules (include/softgrip.h restates them):
 //   * a vertex sits at xpos[body] + R(xquat[body]) vert_pos (sgys_vertex); a triangle is taken relative to the ray's origin;

@@ -1,7 +1,7 @@
 // sg_ray_skin_kernels.h -- sg_ray with SG_RAY_SKIN: the soft object's skin as candidates of a ray query (fp64).
 //
 // Siblings of the two kernels of sg_ray_kernels.h, which keep their code, registers and LDS (the plain call launches them as before); the
-// per-(ray, triangle) math is sg_ray_skin.h, the per-(ray, geom) math sg_ray.h.
+// per-(ray, triangle) math is sg_ray_skin.h, the per-(ray, geom) math sg_ray.h, the traversal of the lanes-over-candidates kernel sg_ray_walk.h.
 //   sg_skinray_vert_kernel   256 lanes = one listed env, a lane per vertex: xpos[body] + R(xquat[body]) vert_pos from the poses sg_kin_kernel
 //                            wrote for this call, into a batch-owned fp64 buffer [n_ids][nvert][3] that BOTH layouts read.
 //   sg_skinray_rays_kernel   lane per ray.  256 lanes = one listed env x one block of 256 rays.  Staged in LDS: the records of the geoms
@@ -10,12 +10,14 @@
 //                            vertices, 512 faces) 40 960 + 6 144 + 2 048 + 1 024 + 640 = 50 816 B: three workgroups share a CU's 160 KB.
 //                            Each lane walks the geoms, then the faces; every LDS read is one address per wavefront (a broadcast).
 //   sg_skinray_geoms_kernel  lanes over candidates.  One wavefront per (env, ray): lane l takes geoms l, l + 64, ... (the hidden ones
-//                            skipped), then faces l, l + 64, ..., from global memory, then the wave reduction of (t, id) by sgy_better.
-// Both call sgy_visit / sgys_visit per candidate and order by sgy_better: the same bits.  An env with a pose of a visible geom or a
+//                            skipped), then faces l, l + 64, ..., from global memory, then the wave reduction of (t, id) by sgy_better:
+//                            sgyw_walk, sgyw_reduce and sgyw_finish, the text the host builds compile.  The other three ray kernels keep
+//                            loops of their own in the same order (profiles/r11_ray_walk_merged_rays_body.txt, r11_ray_walk_bench.json).
+// All call sgy_visit / sgys_visit per candidate and order by sgy_better: the same bits.  An env with a pose of a visible geom or a
 // vertex that is not finite gets dist = NaN, normal = NaN, geomid = -1 (a hidden geom rides on a body a vertex is bound to).
 #pragma once
 #include "sg_ray_kernels.h"
-#include "sg_ray_skin.h"
+#include "sg_ray_walk.h"
 
 static_assert(SGYS_MAXVERT == SGR_MAXVERT && SGYS_MAXFACE == SGR_MAXFACE && SGYS_CAT_ELEM == SGR_CAT_ELEM, "sg_ray takes the skins sg_render_ex takes");
 
@@ -123,54 +125,32 @@ __global__ __launch_bounds__(256) void sg_skinray_rays_kernel(SgSkinRayArgs A, i
   sg_ray_write(a, at, dist, geom, n);
 }
 
+// the walk's source of sg_skinray_geoms_kernel: a record built from global memory per visit; bad: one held a pose that is not finite
+struct SgSkinRayFetch {
+  const SgSkinRayArgs& A;
+  int k;
+  bool bad;
+  __device__ __forceinline__ int count() const { return A.r.ngeom; }
+  __device__ __forceinline__ bool hidden(int g) const { return A.hidden[g]; }
+  __device__ __forceinline__ const double* record(int g, double* buf) { bad |= !sg_ray_record(A.r, k, g, buf); return buf; }
+};
+
+// (the faces of an env that turns out bad are walked too, on vertices that are not finite; its results are NaN)
 __global__ __launch_bounds__(64) void sg_skinray_geoms_kernel(SgSkinRayArgs A) {
   const SgRayArgs& a = A.r;
   const int lane = threadIdx.x;
   const int k = blockIdx.x / a.n_rays, r = blockIdx.x - k * a.n_rays;
-  double o[3], d[3];
-  int exclude;
+  double o[3], d[3], dist, n[3];
+  int exclude, geom;
   const bool live = sg_ray_world(a, k, r, o, d, &exclude);
+  SgSkinRayFetch G = {A, k, false};
+  const SgywSkin K = {A.vtx + (size_t)k * A.nvert * 3, A.faces, A.vert_body, A.nface};
   SgyBest best = {INFINITY, -1, 0};
-  bool bad = false;
-  for (int g = lane; g < a.ngeom; g += 64) {
-    if (A.hidden[g]) continue;
-    double rec[SGY_REC];
-    bad |= !sg_ray_record(a, k, g, rec);
-    if (live) sgy_visit(g, rec, o, d, a.cat_mask, exclude, a.limit, &best);
-  }
-  const double* vtx = A.vtx + (size_t)k * A.nvert * 3;
-  for (int i = lane; i < 3 * A.nvert; i += 64) bad |= !isfinite(vtx[i]);
-  bad = __any(bad);
-  if (live && !bad && ((a.cat_mask >> SGYS_CAT_ELEM) & 1)) {
-    SgysFrame fr;
-    sgys_frame(d, &fr);
-    for (int f = lane; f < A.nface; f += 64) {
-      int ia, ib, ic;
-      sgys_face(A.faces[f], &ia, &ib, &ic);
-      double v[9];
-      for (int c = 0; c < 3; c++) { v[c] = vtx[3 * ia + c]; v[3 + c] = vtx[3 * ib + c]; v[6 + c] = vtx[3 * ic + c]; }
-      sgys_visit(a.ngeom + f, v, ia, v + 3, ib, v + 6, ic, A.vert_body, fr, o, d, exclude, &best);
-    }
-  }
-  for (int m = 32; m >= 1; m >>= 1) {
-    const double t = __shfl_xor(best.t, m);
-    const int g = __shfl_xor(best.geom, m), ax = __shfl_xor(best.ax, m);
-    if (sgy_better(t, g, best.t, best.geom)) { best.t = t; best.geom = g; best.ax = ax; }
-  }
+  sgyw_walk(G, K, lane, 64, live, o, d, a.cat_mask, exclude, a.limit, &best);
+  for (int i = lane; i < 3 * A.nvert; i += 64) G.bad |= !isfinite(K.vtx[i]);
+  const bool bad = __any(G.bad);
+  sgyw_reduce(&best);
   if (lane != 0) return;
-  const size_t at = (size_t)k * a.n_rays + r;
-  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-  double n[3] = {qnan, qnan, qnan}, dist, rec[SGY_REC];
-  int geom;
-  if (bad) {
-    sg_ray_write(a, at, qnan, -1, n);
-    return;
-  }
-  if (best.geom >= a.ngeom) {
-    sg_skinray_finish(A, best, vtx, A.faces[best.geom - a.ngeom], at);
-    return;
-  }
-  if (best.geom >= 0) sg_ray_record(a, k, best.geom, rec);   // (a miss reads no record: sgy_finish does not look at it)
-  sgy_finish(best, rec, o, d, a.limit, &dist, &geom, n);
-  sg_ray_write(a, at, dist, geom, n);
+  sgyw_finish(G, K, bad, best, o, d, a.limit, &dist, &geom, n);
+  sg_ray_write(a, (size_t)k * a.n_rays + r, dist, geom, n);
 }

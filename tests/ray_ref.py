@@ -166,16 +166,20 @@ def scene_rays(gx, types, n, seed):
     return o, tgt - o
 
 
-# ---- the g++ build of sg_ray.h: records, the ray map, the walk and the reduction as the two kernel layouts do them ----
+# ---- the g++ build of csrc/sg_ray_walk.h (over sg_ray.h and sg_ray_skin.h): the walk, the reduction and the finish the kernels compile ----
 HOST_DRIVER = r"""
 #include <vector>
-#include "sg_ray.h"
-// layout 0: one walker over the geoms in id order (the lane-per-ray kernel); 1: 64 walkers striding over the geoms, reduced by
-// sgy_better in the butterfly order of the wave reduction (the lanes-over-geoms kernel)
+#include "sg_ray_walk.h"
+extern "C" void skin_vertex_host(int nvert, const int* vbody, const double* vpos, const double* xpos, const double* xquat, double* out) {
+  for (int v = 0; v < nvert; v++) sgys_vertex(xpos + 3 * vbody[v], xquat + 4 * vbody[v], vpos + 3 * v, out + 3 * v);
+}
+
+// the arrays as records, packed faces and views, then sgyw_host_ray per ray (layout: which kernel layout's walkers).  No skin: nface = 0
 extern "C" void ray_host(int layout, int ng, const double* gx, const double* gm, const double* gs, const int* type, const int* cat, const int* gbody,
-                         const double* xpos, const double* xquat, int nr, const double* o_in, const double* d_in, const int* rbody, const int* rexcl,
-                         int cat_mask, double max_dist, double* dist, int* geom, double* normal) {
-  std::vector<double> recs((size_t)ng * SGY_REC + SGY_REC);
+                         const int* hidden, const double* verts, const int* vbody, int nface, const int* face, const double* xpos,
+                         const double* xquat, int nr, const double* o_in, const double* d_in, const int* rbody, const int* rexcl, int cat_mask,
+                         double max_dist, double* dist, int* geom, double* normal) {
+  std::vector<double> recs((size_t)ng * SGY_REC);
   for (int g = 0; g < ng; g++) {
     double* r = &recs[(size_t)SGY_REC * g];
     for (int c = 0; c < 3; c++) r[c] = gx[3 * g + c];
@@ -183,35 +187,21 @@ extern "C" void ray_host(int layout, int ng, const double* gx, const double* gm,
     for (int c = 0; c < 3; c++) r[12 + c] = gs[3 * g + c];
     r[15] = sgy_meta_word(sgy_meta(type[g], cat[g], gbody[g]));
   }
-  const double limit = max_dist > 0 ? max_dist : INFINITY;
+  std::vector<uint32_t> packed(nface);
+  for (int f = 0; f < nface; f++) packed[f] = (uint32_t)face[3 * f] | ((uint32_t)face[3 * f + 1] << 8) | ((uint32_t)face[3 * f + 2] << 16);
+  SgywHostGeoms G = {recs.data(), hidden, ng};
+  const SgywSkin K = {verts, packed.data(), vbody, nface};
   for (int q = 0; q < nr; q++) {
-    const int body = rbody ? rbody[q] : -1, excl = rexcl ? rexcl[q] : -1;
-    double o[3], d[3];
-    const bool live = sgy_map_ray(body >= 0 ? xpos + 3 * body : nullptr, xquat + 4 * (body >= 0 ? body : 0), o_in + 3 * q, d_in + 3 * q, o, d);
-    SgyBest best = {INFINITY, -1, 0};
-    if (live && layout == 0) {
-      for (int g = 0; g < ng; g++) sgy_visit(g, &recs[(size_t)SGY_REC * g], o, d, cat_mask, excl, limit, &best);
-    } else if (live) {
-      SgyBest w[64];
-      for (int l = 0; l < 64; l++) {
-        w[l] = SgyBest{INFINITY, -1, 0};
-        for (int g = l; g < ng; g += 64) sgy_visit(g, &recs[(size_t)SGY_REC * g], o, d, cat_mask, excl, limit, &w[l]);
-      }
-      for (int m = 32; m >= 1; m >>= 1) {
-        SgyBest nx[64];
-        for (int l = 0; l < 64; l++) nx[l] = sgy_better(w[l ^ m].t, w[l ^ m].geom, w[l].t, w[l].geom) ? w[l ^ m] : w[l];
-        for (int l = 0; l < 64; l++) w[l] = nx[l];
-      }
-      best = w[0];
-    }
-    sgy_finish(best, &recs[(size_t)SGY_REC * (best.geom >= 0 ? best.geom : 0)], o, d, limit, dist + q, geom + q, normal + 3 * q);
+    const int body = rbody ? rbody[q] : -1;
+    sgyw_host_ray(G, K, layout, body >= 0 ? xpos + 3 * body : nullptr, xquat + 4 * (body >= 0 ? body : 0), o_in + 3 * q, d_in + 3 * q,
+                  rexcl ? rexcl[q] : -1, cat_mask, max_dist > 0 ? max_dist : INFINITY, dist + q, geom + q, normal + 3 * q);
   }
 }
 """
 
 
 def build_host(tmpdir):
-    """compiles sg_ray.h with g++ into tmpdir -> ctypes function ray_host"""
+    """compiles the driver above with g++ into tmpdir -> the ctypes library (ray_host, skin_vertex_host)"""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = os.path.join(tmpdir, "ray_host.cpp")
     so = os.path.join(tmpdir, "libray_host.so")
@@ -220,23 +210,39 @@ def build_host(tmpdir):
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(root, "soft-grip_amd", "csrc"), "-o", so, src])
     L = C.CDLL(so)
     L.ray_host.restype = None
-    return L.ray_host
+    L.skin_vertex_host.restype = None
+    return L
 
 
-def cast_with(fn, gx, gm, types, sizes, cats, geom_body, origin, direction, xpos=None, xquat=None, body=None, exclude=None, cat_mask=ALL_BITS,
-              max_dist=0.0, layout=0):
-    """the host build on the same inputs (body-frame rays mapped by the header's own code) -> dist, geom, normal"""
-    a = lambda x, dt: np.ascontiguousarray(x, dtype=dt)  # noqa: E731
-    p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
-    gx, gm, gs = a(gx, np.float64), a(np.reshape(gm, (-1, 9)), np.float64), a(sizes, np.float64)
-    ty, ct, gb = a(types, np.int32), a(cats, np.int32), a(geom_body, np.int32)
-    o, d = a(np.reshape(origin, (-1, 3)), np.float64), a(np.reshape(direction, (-1, 3)), np.float64)
-    xp = a(np.zeros((1, 3)) if xpos is None else xpos, np.float64)
-    xq = a(np.array([[1.0, 0, 0, 0]]) if xquat is None else xquat, np.float64)
-    rb = None if body is None else a(body, np.int32)
-    rx = None if exclude is None else a(exclude, np.int32)
+def _a(x, dt):
+    return np.ascontiguousarray(x, dtype=dt)
+
+
+def _p(x):
+    return None if x is None else x.ctypes.data_as(C.c_void_p)
+
+
+def cast_host(L, gx, gm, types, sizes, cats, geom_body, hidden, verts, vert_body, face, origin, direction, xpos, xquat, body, exclude, cat_mask,
+              max_dist, layout):
+    """the host build on the same inputs (body-frame rays mapped by the header's own code) -> dist, id, normal.  hidden None: no geom is"""
+    gx, gm, gs = _a(np.reshape(gx, (-1, 3)), np.float64), _a(np.reshape(gm, (-1, 9)), np.float64), _a(np.reshape(sizes, (-1, 3)), np.float64)
+    ty, ct, gb = _a(types, np.int32), _a(cats, np.int32), _a(geom_body, np.int32)
+    hid = None if hidden is None else _a(hidden, np.int32)
+    vs, vb, fc = _a(np.reshape(verts, (-1, 3)), np.float64), _a(vert_body, np.int32), _a(np.reshape(face, (-1, 3)), np.int32)
+    o, d = _a(np.reshape(origin, (-1, 3)), np.float64), _a(np.reshape(direction, (-1, 3)), np.float64)
+    xp = _a(np.zeros((1, 3)) if xpos is None else xpos, np.float64)
+    xq = _a(np.array([[1.0, 0, 0, 0]]) if xquat is None else xquat, np.float64)
+    rb = None if body is None else _a(body, np.int32)
+    rx = None if exclude is None else _a(exclude, np.int32)
     n = len(o)
     dist, geom, normal = np.empty(n), np.empty(n, np.int32), np.empty((n, 3))
-    fn(C.c_int(layout), C.c_int(len(ty)), p(gx), p(gm), p(gs), p(ty), p(ct), p(gb), p(xp), p(xq), C.c_int(n), p(o), p(d), p(rb), p(rx),
-       C.c_int(int(cat_mask)), C.c_double(float(max_dist)), p(dist), p(geom), p(normal))
+    L.ray_host(C.c_int(layout), C.c_int(len(ty)), _p(gx), _p(gm), _p(gs), _p(ty), _p(ct), _p(gb), _p(hid), _p(vs), _p(vb), C.c_int(len(fc)), _p(fc),
+               _p(xp), _p(xq), C.c_int(n), _p(o), _p(d), _p(rb), _p(rx), C.c_int(int(cat_mask)), C.c_double(float(max_dist)), _p(dist), _p(geom), _p(normal))
     return dist, geom, normal
+
+
+def cast_with(L, gx, gm, types, sizes, cats, geom_body, origin, direction, xpos=None, xquat=None, body=None, exclude=None, cat_mask=ALL_BITS,
+              max_dist=0.0, layout=0):
+    """the plain call: the skin call with no vertices, no faces and nothing hidden"""
+    return cast_host(L, gx, gm, types, sizes, cats, geom_body, None, np.zeros((0, 3)), np.zeros(0), np.zeros((0, 3)), origin, direction, xpos, xquat,
+                     body, exclude, cat_mask, max_dist, layout)

@@ -13,8 +13,6 @@ triangles are cast here:
 
 unstable() is ray_ref.unstable's notion for this caster, and the comparison is ray_ref.compare itself."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
@@ -106,120 +104,20 @@ def faces_of(gid, ngeom):
     return np.where(gid >= ngeom, gid - ngeom, -1).astype(np.int32)
 
 
-# ---- the g++ build of sg_ray_skin.h + sg_ray.h: vertices, the walk and the reduction as the two kernel layouts do them ----
-HOST_DRIVER = r"""
-#include <vector>
-#include "sg_ray_skin.h"
-extern "C" void skin_vertex_host(int nvert, const int* vbody, const double* vpos, const double* xpos, const double* xquat, double* out) {
-  for (int v = 0; v < nvert; v++) sgys_vertex(xpos + 3 * vbody[v], xquat + 4 * vbody[v], vpos + 3 * v, out + 3 * v);
-}
-
-// layout 0: one walker over the visible geoms in id order, then the faces (the lane-per-ray kernel); 1: 64 walkers striding over geoms
-// and faces, reduced by sgy_better in the butterfly order of the wave reduction (the lanes-over-candidates kernel)
-extern "C" void skin_ray_host(int layout, int ng, const double* gx, const double* gm, const double* gs, const int* type, const int* cat, const int* gbody,
-                              const int* hidden, int nvert, const double* verts, const int* vbody, int nface, const int* face, const double* xpos,
-                              const double* xquat, int nr, const double* o_in, const double* d_in, const int* rbody, const int* rexcl, int cat_mask,
-                              double max_dist, double* dist, int* geom, double* normal) {
-  std::vector<double> recs((size_t)ng * SGY_REC + SGY_REC);
-  for (int g = 0; g < ng; g++) {
-    double* r = &recs[(size_t)SGY_REC * g];
-    for (int c = 0; c < 3; c++) r[c] = gx[3 * g + c];
-    for (int c = 0; c < 9; c++) r[3 + c] = gm[9 * g + c];
-    for (int c = 0; c < 3; c++) r[12 + c] = gs[3 * g + c];
-    r[15] = sgy_meta_word(sgy_meta(type[g], cat[g], gbody[g]));
-  }
-  std::vector<uint32_t> packed(nface + 1);
-  for (int f = 0; f < nface; f++) packed[f] = (uint32_t)face[3 * f] | ((uint32_t)face[3 * f + 1] << 8) | ((uint32_t)face[3 * f + 2] << 16);
-  const double limit = max_dist > 0 ? max_dist : INFINITY;
-  const bool tris = (cat_mask >> SGYS_CAT_ELEM) & 1;
-  for (int q = 0; q < nr; q++) {
-    const int body = rbody ? rbody[q] : -1, excl = rexcl ? rexcl[q] : -1;
-    double o[3], d[3];
-    const bool live = sgy_map_ray(body >= 0 ? xpos + 3 * body : nullptr, xquat + 4 * (body >= 0 ? body : 0), o_in + 3 * q, d_in + 3 * q, o, d);
-    SgysFrame fr;
-    if (live) sgys_frame(d, &fr);
-    auto tri = [&](int f, SgyBest* b) {
-      int ia, ib, ic;
-      sgys_face(packed[f], &ia, &ib, &ic);
-      sgys_visit(ng + f, verts + 3 * ia, ia, verts + 3 * ib, ib, verts + 3 * ic, ic, vbody, fr, o, d, excl, b);
-    };
-    SgyBest best = {INFINITY, -1, 0};
-    if (live && layout == 0) {
-      for (int g = 0; g < ng; g++)
-        if (!hidden[g]) sgy_visit(g, &recs[(size_t)SGY_REC * g], o, d, cat_mask, excl, limit, &best);
-      for (int f = 0; tris && f < nface; f++) tri(f, &best);
-    } else if (live) {
-      SgyBest w[64];
-      for (int l = 0; l < 64; l++) {
-        w[l] = SgyBest{INFINITY, -1, 0};
-        for (int g = l; g < ng; g += 64)
-          if (!hidden[g]) sgy_visit(g, &recs[(size_t)SGY_REC * g], o, d, cat_mask, excl, limit, &w[l]);
-        for (int f = l; tris && f < nface; f += 64) tri(f, &w[l]);
-      }
-      for (int m = 32; m >= 1; m >>= 1) {
-        SgyBest nx[64];
-        for (int l = 0; l < 64; l++) nx[l] = sgy_better(w[l ^ m].t, w[l ^ m].geom, w[l].t, w[l].geom) ? w[l ^ m] : w[l];
-        for (int l = 0; l < 64; l++) w[l] = nx[l];
-      }
-      best = w[0];
-    }
-    if (best.geom >= ng) {
-      int ia, ib, ic;
-      sgys_face(packed[best.geom - ng], &ia, &ib, &ic);
-      sgys_finish(best, verts + 3 * ia, verts + 3 * ib, verts + 3 * ic, limit, dist + q, geom + q, normal + 3 * q);
-    } else {
-      sgy_finish(best, &recs[(size_t)SGY_REC * (best.geom >= 0 ? best.geom : 0)], o, d, limit, dist + q, geom + q, normal + 3 * q);
-    }
-  }
-}
-"""
-
-
-def build_host(tmpdir):
-    """compiles the driver above (sg_ray_skin.h, sg_ray.h) with g++ into tmpdir -> the ctypes library"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = os.path.join(tmpdir, "ray_skin_host.cpp")
-    so = os.path.join(tmpdir, "libray_skin_host.so")
-    with open(src, "w") as f:
-        f.write(HOST_DRIVER)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(root, "soft-grip_amd", "csrc"), "-o", so, src])
-    L = C.CDLL(so)
-    L.skin_ray_host.restype = None
-    L.skin_vertex_host.restype = None
-    return L
-
-
-def _a(x, dt):
-    return np.ascontiguousarray(x, dtype=dt)
-
-
-def _p(x):
-    return None if x is None else x.ctypes.data_as(C.c_void_p)
+# ---- the g++ build: tests/ray_ref.py's (one driver over csrc/sg_ray_walk.h for the plain call and this one) ----
+build_host = RR.build_host
 
 
 def vertices_with(L, skin, xpos, xquat):
-    vb, vp = _a(skin["vert_body"], np.int32), _a(skin["vert_pos"], np.float64)
-    xp, xq = _a(xpos, np.float64), _a(xquat, np.float64)
+    vb, vp = RR._a(skin["vert_body"], np.int32), RR._a(skin["vert_pos"], np.float64)
+    xp, xq = RR._a(xpos, np.float64), RR._a(xquat, np.float64)
     out = np.empty((len(vb), 3))
-    L.skin_vertex_host(C.c_int(len(vb)), _p(vb), _p(vp), _p(xp), _p(xq), _p(out))
+    L.skin_vertex_host(C.c_int(len(vb)), RR._p(vb), RR._p(vp), RR._p(xp), RR._p(xq), RR._p(out))
     return out
 
 
 def cast_with(L, gx, gm, types, sizes, cats, geom_body, skin, verts, origin, direction, xpos=None, xquat=None, body=None, exclude=None,
               cat_mask=RR.ALL_BITS, max_dist=0.0, layout=0):
     """the host build on the same inputs (body-frame rays mapped by the header's own code) -> dist, id, normal"""
-    gx, gm, gs = _a(np.reshape(gx, (-1, 3)), np.float64), _a(np.reshape(gm, (-1, 9)), np.float64), _a(np.reshape(sizes, (-1, 3)), np.float64)
-    ty, ct, gb = _a(types, np.int32), _a(cats, np.int32), _a(geom_body, np.int32)
-    hid = _a(hidden_geoms(gb, skin), np.int32)
-    vs, vb, fc = _a(np.reshape(verts, (-1, 3)), np.float64), _a(skin["vert_body"], np.int32), _a(np.reshape(skin["face"], (-1, 3)), np.int32)
-    o, d = _a(np.reshape(origin, (-1, 3)), np.float64), _a(np.reshape(direction, (-1, 3)), np.float64)
-    xp = _a(np.zeros((1, 3)) if xpos is None else xpos, np.float64)
-    xq = _a(np.array([[1.0, 0, 0, 0]]) if xquat is None else xquat, np.float64)
-    rb = None if body is None else _a(body, np.int32)
-    rx = None if exclude is None else _a(exclude, np.int32)
-    n = len(o)
-    dist, geom, normal = np.empty(n), np.empty(n, np.int32), np.empty((n, 3))
-    L.skin_ray_host(C.c_int(layout), C.c_int(len(ty)), _p(gx), _p(gm), _p(gs), _p(ty), _p(ct), _p(gb), _p(hid), C.c_int(len(vs)), _p(vs), _p(vb),
-                    C.c_int(len(fc)), _p(fc), _p(xp), _p(xq), C.c_int(n), _p(o), _p(d), _p(rb), _p(rx), C.c_int(int(cat_mask)), C.c_double(float(max_dist)),
-                    _p(dist), _p(geom), _p(normal))
-    return dist, geom, normal
+    return RR.cast_host(L, gx, gm, types, sizes, cats, geom_body, hidden_geoms(geom_body, skin), verts, skin["vert_body"], skin["face"], origin,
+                        direction, xpos, xquat, body, exclude, cat_mask, max_dist, layout)

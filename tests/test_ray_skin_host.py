@@ -291,7 +291,7 @@ def test_sanitizer_run_of_the_host_walk(tmp_path):
                            os.path.join(ROOT, "soft-grip_amd", "csrc"), "-o", exe, os.path.join(ROOT, "scripts", "sanitize", "ray_skin_main.cpp")])
     res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert res.returncode == 0, res.stdout + res.stderr
-    assert "ray_skin_main: 1800 rays" in res.stdout and not res.stderr.strip(), res.stdout + res.stderr
+    assert res.stdout.strip() == "ray_skin_main: 1800 rays, 530 hits, 499 on a skin, checksum 08cf6f9906f7ed90" and not res.stderr.strip(), res.stdout + res.stderr
 
 
 def test_tactile_depth_with_the_skin(host, monkeypatch):
