@@ -5,29 +5,17 @@ function's ordinal in its file (.LBB7_3 -> .LBB_3: a function that moved to anot
 the resource metadata.  Exit status 1 on any DIFF.  A translation unit split in two: hold the old file against the two new ones concatenated.
 usage: asm_same.py OLD.s NEW.s [OLDNAME=NEWNAME ...]     a rename is a regular expression and its replacement, applied to OLD's text:
        '10tree_stageILi(\\d+)ELi1E=19tree_stage_dynamicsILi\\1E'"""
+import os
 import re
 import sys
 
-META = (".vgpr_count", ".agpr_count", ".sgpr_spill_count", ".vgpr_spill_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "soft-grip_amd"))
+import devasm  # noqa: E402
 
 
 def parse(text):
-    funcs, cur = {}, None
-    isfunc = set(re.findall(r"^\s*\.type\s+([^\s,]+),@function", text, re.M))
-    for line in text.split("\n"):
-        line = line.split(";", 1)[0].strip()
-        m = re.match(r"^([A-Za-z_][\w$.]*):$", line)
-        if m and m.group(1) in isfunc:
-            cur = funcs.setdefault(m.group(1), [])
-        elif line.startswith(".Lfunc_end"):
-            cur = None
-        elif cur is not None and line and (not line.startswith(".") or re.match(r"^\.LBB\w+:$", line)):
-            cur.append(re.sub(r"\.LBB\d+_", ".LBB_", line))
-    kernels = {}
-    for block in text.split("  - .agpr_count:")[1:]:          # one metadata entry per kernel (its keys are sorted: this one is first)
-        block = "  - .agpr_count:" + block
-        name = re.search(r"\.name:\s+(\S+)", block)
-        kernels[name.group(1)] = tuple(re.search(r"\%s:\s+(\d+)" % k, block).group(1) for k in META)
+    funcs = {name: [re.sub(r"\.LBB\d+_", ".LBB_", t) for _, t in body] for name, body in devasm.functions(text).items()}
+    kernels = {name: tuple(str(rec[k]) for k in devasm.META) for name, rec in devasm.kernels(text).items()}
     return funcs, kernels
 
 
@@ -52,7 +40,7 @@ def main(argv):
     for name in sorted(set(ko) | set(kn)):
         same = ko.get(name) == kn.get(name)
         bad += not same
-        print("%s metadata %s  %s" % ("SAME" if same else "DIFF", " ".join("%s=%s" % (k[1:], v) for k, v in zip(META, kn.get(name) or ko.get(name))) if same
+        print("%s metadata %s  %s" % ("SAME" if same else "DIFF", " ".join("%s=%s" % (k, v) for k, v in zip(devasm.META.values(), kn.get(name) or ko.get(name))) if same
                                        else "%s -> %s" % (ko.get(name), kn.get(name)), name))
     print("%d functions, %d kernels: %s" % (len(set(fo) | set(fn)), len(set(ko) | set(kn)), "all SAME" if not bad else "%d DIFF" % bad))
     return 1 if bad else 0

@@ -2,30 +2,27 @@
 soft-grip_amd/build/<hash>/<source>.device.s) the private segment size, the scratch instructions in the prologue / epilogue (callee-saved
 registers of a CALLED function: the price of the staged layout) and the scratch instructions inside loops (what could cost time).
 usage: python scripts/scratch_audit.py file.device.s [name filter]"""
+import os
 import re
 import subprocess
 import sys
 
-lines = open(sys.argv[1]).read().split("\n")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "soft-grip_amd"))
+import devasm  # noqa: E402
+
+text = open(sys.argv[1]).read()
+lines = text.split("\n")
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
-funcs, cur = [], None
-for i, l in enumerate(lines):
-    m = re.match(r"^(\.?L?_Z\w+|\w+):\s*(;.*)?$", l)
-    if m and not l.startswith(".LBB") and (l.startswith("_Z") or l.startswith(".L_Z")):
-        cur = {"name": m.group(1), "start": i}
-        funcs.append(cur)
-    if l.startswith("; codeLenInByte") and cur is not None and "end" not in cur:
-        cur["end"] = i
-        for j in range(i, min(i + 12, len(lines))):
-            mm = re.match(r";\s*ScratchSize:\s*(\d+)", lines[j])
-            if mm:
-                cur["scratch"] = int(mm.group(1))
 print("%-58s %9s %8s %10s %10s %9s" % ("function", "bytes/lane", "instr", "scratch ops", "in loops", "in entry/exit"))
-for f in funcs:
-    if "end" not in f or flt not in f["name"]:
+for fname, stream in devasm.functions(text).items():
+    if not stream or not fname.startswith(("_Z", ".L_Z")) or flt not in fname:
         continue
-    body = lines[f["start"]:f["end"]]
-    nins = nscr = nloop = nedge = 0
+    # (the compiler's comments say which blocks are loops and, behind the function, its scratch size -- also of a function that is no
+    #  kernel, which devasm.kernels does not list: read from the lines themselves, between the stream's first and last line)
+    body = lines[stream[0][0] - 1:stream[-1][0]]
+    scratch = next((m.group(1) for m in map(re.compile(r";\s*ScratchSize:\s*(\d+)").match, lines[stream[-1][0]:]) if m), "?")
+    nscr = nloop = nedge = 0
+    nins = 1                       # (the column has always counted the function's own label line)
     inloop, blk = False, 0
     nblocks = sum(1 for l in body if re.match(r"^\.LBB\d+_\d+:", l))
     for l in body:
@@ -45,6 +42,6 @@ for f in funcs:
                 nloop += 1
             if blk == 0 or blk == nblocks:
                 nedge += 1
-    name = subprocess.run(["c++filt", f["name"].lstrip(".L")], capture_output=True, text=True).stdout.strip()
+    name = subprocess.run(["c++filt", fname.lstrip(".L")], capture_output=True, text=True).stdout.strip()
     name = re.sub(r"\(.*", "", name)
-    print("%-58s %9s %8d %10d %10d %9d" % (name[:58], f.get("scratch", "?"), nins, nscr, nloop, nedge))
+    print("%-58s %9s %8d %10d %10d %9d" % (name[:58], scratch, nins, nscr, nloop, nedge))

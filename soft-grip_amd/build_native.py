@@ -1,5 +1,9 @@
 """Builds libsoftgrip.so (HIP kernels + C ABI) in-tree for gfx950 with hipcc: one translation unit per kernel family, compiled side
-by side, objects cached under soft-grip_amd/build/<variant>/ and re-made only when their source or a header is newer."""
+by side, objects cached under soft-grip_amd/build/<hash of the flags>/ and re-made only when their source or a header is newer.
+What a variant of the library is (the product, --prof, --count, --legacy) is one row of VARIANTS; build(), the removal under force and
+the finders of the kept device assembly (device_asm, device_asm_files; soft-grip_amd/devasm.py reads it) all go through that row.
+One builder at a time per checkout: an exclusive flock on soft-grip_amd/.build.lock, a file that no build removes."""
+import collections
 import concurrent.futures
 import contextlib
 import sys
@@ -15,10 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 if _HERE not in sys.path:
     sys.path.insert(0, _HERE)      # isa_check.py (this directory is a package with a hyphen in its name: imported by file)
 CSRC = os.path.join(_HERE, "csrc")
-LIB = os.path.join(_HERE, "libsoftgrip.so")
-LEGACY_LIB = os.path.join(_HERE, "libsoftgrip_legacy.so")
 SOURCES = ["sg_api.hip", "sg_readout.hip", "sg_phase.hip", "sg_rows.hip", "sg_tree.hip", "sg_plan.cpp", "sg_mjcf.cpp"]   # what the product runs
-LEGACY_SOURCES = ["sg_legacy.hip"]   # r01's fused / split pipelines: test builds only (-DSG_LEGACY_PIPELINES)
 # -amdgpu-sched-strategy=iterative-ilp: LLVM's iterative ILP machine scheduler instead of the default max-occupancy one.  The
 # kernels run at one or two wavefronts per SIMD whatever their register count (the solver by design, the phase kernel by its
 # LDS), so trading registers for a shorter dependency-stalled schedule is free: solver -2.5 %, phase kernel -4.9 % per episode
@@ -46,41 +47,49 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def needs_build(lib=LIB, sources=SOURCES):
-    return _stale(lib, [os.path.join(CSRC, s) for s in sources] + _headers())
+# a variant of the library: its file beside this one, its flags beyond FLAGS, its sources, and the sources compiled under the default
+# machine scheduler.  prof: the kernel section stamps for scripts/section_profile.py.  count: also counts events inside the contact update
+# (contact updates, updates outside the friction cone, QCQP fallback entries and Newton evaluations) -- its cycle stamps are not timings.
+# Both compile sg_phase.hip under the default scheduler: with iterative-ilp the compiler itself crashes in its register allocator on this
+# variant of sg_phase_kernel<4, ...> -- r05, ROCm 7.2.0 -- while sg_tree.hip under the DEFAULT scheduler ends in "Illegal instruction
+# detected: V_CMP_NE_U32_e32 0, $src_shared_base".  legacy: the product plus r01's fused and split pipelines (sg_legacy.hip), which the
+# cross-check tests load by themselves (tests/helpers.py: library_for).
+Variant = collections.namedtuple("Variant", "lib extra sources default_sched")
+VARIANTS = {
+    "": Variant("libsoftgrip.so", [], SOURCES, ()),
+    "prof": Variant("libsoftgrip_prof.so", ["-DSG_SECTION_PROF"], SOURCES, ("sg_phase.hip",)),
+    "count": Variant("libsoftgrip_count.so", ["-DSG_SECTION_PROF", "-DSG_SECTION_COUNT"], SOURCES, ("sg_phase.hip",)),
+    "legacy": Variant("libsoftgrip_legacy.so", ["-DSG_LEGACY_PIPELINES"], SOURCES + ["sg_legacy.hip"], ()),
+}
+OWNED_VARIANTS = tuple(name for name in VARIANTS if name)      # what build(force=True) removes beside the object cache
+
+
+def needs_build(variant=""):
+    v = VARIANTS[variant]
+    return _stale(os.path.join(_HERE, v.lib), [os.path.join(CSRC, s) for s in v.sources] + _headers())
 
 
 def build(force=False, verbose=False, prof=False, count=False, legacy=False):
-    """prof=True builds libsoftgrip_prof.so with the kernel section stamps (-DSG_SECTION_PROF) for scripts/section_profile.py;
-    count=True builds libsoftgrip_count.so, which also counts events inside the contact update (-DSG_SECTION_COUNT: contact
-    updates, updates outside the friction cone, QCQP fallback entries and Newton evaluations) -- its cycle stamps are not timings;
-    legacy=True builds libsoftgrip_legacy.so: the product plus r01's fused and split pipelines (-DSG_LEGACY_PIPELINES), which the
-    cross-check tests load by themselves.  force=True also removes the variant libraries THIS function makes (prof, count, legacy) and
-    the object cache -- not the hand-made `--ko NAME` experiment libraries (scripts/dev/ab_*.sh keep an A/B library of an earlier round
-    there)."""
-    if force:
-        with _build_lock():
+    """the library of one variant (VARIANTS; the product when no flag is set), built when it is missing or older than a source or a
+    header; otherwise the existing file, whichever the variant, unless force or verbose asks for a build.  force=True first removes the
+    variant libraries THIS function makes (prof, count, legacy) and the object cache -- not the hand-made `--ko NAME` experiment
+    libraries (scripts/dev/ab_*.sh keep an A/B library of an earlier round there).  The removal and the compile that follows are one
+    critical section, and whether anything is stale is asked again inside it: of the ranks that start together on a stale library
+    one compiles, the others return what it made."""
+    variant = "count" if count else "prof" if prof else "legacy" if legacy else ""
+    v = VARIANTS[variant]
+    lib = os.path.join(_HERE, v.lib)
+    if not force and not verbose and not needs_build(variant):
+        return lib
+    with _build_lock():
+        if force:
             for name in OWNED_VARIANTS:
                 with contextlib.suppress(FileNotFoundError):
-                    os.remove(os.path.join(_HERE, "libsoftgrip_%s.so" % name))
+                    os.remove(os.path.join(_HERE, VARIANTS[name].lib))
             shutil.rmtree(os.path.join(_HERE, "build"), ignore_errors=True)
-    if count:
-        # (sg_phase.hip under the default machine scheduler: with iterative-ilp the compiler itself crashes in its register allocator on
-        #  this variant of sg_phase_kernel<4, ...> -- r05, ROCm 7.2.0 -- while sg_tree.hip under the DEFAULT scheduler ends in "Illegal
-        #  instruction detected: V_CMP_NE_U32_e32 0, $src_shared_base"; the counting build's cycle stamps are not timings anyway)
-        return _compile(os.path.join(_HERE, "libsoftgrip_count.so"), ["-DSG_SECTION_PROF", "-DSG_SECTION_COUNT"], verbose, default_sched=("sg_phase.hip",))
-    if prof:
-        return _compile(os.path.join(_HERE, "libsoftgrip_prof.so"), ["-DSG_SECTION_PROF"], verbose, default_sched=("sg_phase.hip",))   # (as for --count, below)
-    if legacy:
-        if not force and not needs_build(LEGACY_LIB, SOURCES + LEGACY_SOURCES):
-            return LEGACY_LIB
-        return _compile(LEGACY_LIB, ["-DSG_LEGACY_PIPELINES"], verbose, SOURCES + LEGACY_SOURCES)
-    if not force and not verbose and not needs_build():
-        return LIB
-    return _compile(LIB, [], verbose)
-
-
-OWNED_VARIANTS = ("prof", "count", "legacy")
+        elif not verbose and not needs_build(variant):
+            return lib
+        return _compile_locked(lib, v.extra, verbose, v.sources, v.default_sched)
 
 
 def _compiler_crashed(stderr):
@@ -89,31 +98,19 @@ def _compiler_crashed(stderr):
 
 @contextlib.contextmanager
 def _build_lock():
-    """one builder at a time per checkout (ranks, pytest-xdist workers and helpers.library_for may all ask for a build at once): an
-    exclusive flock on soft-grip_amd/build/.lock; re-entrant inside one process"""
-    if getattr(_build_lock, "depth", 0):
-        yield
-        return
-    os.makedirs(os.path.join(_HERE, "build"), exist_ok=True)
-    with open(os.path.join(_HERE, "build", ".lock"), "w") as f:
+    """one builder at a time per checkout (ranks, pytest-xdist workers, threads and helpers.library_for may all ask for a build at once):
+    an exclusive flock on soft-grip_amd/.build.lock, outside everything build(force=True) removes.  Every entry opens the file anew and
+    a flock belongs to the open file, so a second thread of this process waits exactly as a second process does.  Not re-entrant:
+    build() and the --ko command line enter once and call _compile_locked()."""
+    with open(os.path.join(_HERE, ".build.lock"), "w") as f:      # (closing the file gives the lock back)
         fcntl.flock(f, fcntl.LOCK_EX)
-        _build_lock.depth = 1
-        try:
-            yield
-        finally:
-            _build_lock.depth = 0
-            fcntl.flock(f, fcntl.LOCK_UN)
-
-
-def _compile(out, extra, verbose, sources=SOURCES, default_sched=()):
-    with _build_lock():
-        return _compile_locked(out, extra, verbose, sources, default_sched)
+        yield
 
 
 def _compile_locked(out, extra, verbose, sources, default_sched):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     flags_all = FLAGS + extra + (["-Rpass-analysis=kernel-resource-usage"] if verbose else [])
-    objdir = os.path.join(_HERE, "build", _objdir_name(extra, default_sched))
+    objdir = _objdir(extra, default_sched)
     os.makedirs(objdir, exist_ok=True)
     hdrs = _headers()
 
@@ -182,15 +179,30 @@ def _objdir_name(extra=(), default_sched=()):
     return hashlib.sha1(" ".join(key).encode()).hexdigest()[:12]
 
 
-def device_asm_files(extra=()):
-    """the device assembly kept by the last build of the given variant (flags beyond FLAGS), one file per .hip source"""
-    objdir = os.path.join(_HERE, "build", _objdir_name(extra))
-    return sorted(glob.glob(os.path.join(objdir, "*.device.s")))
+def _objdir(extra, default_sched):
+    return os.path.join(_HERE, "build", _objdir_name(extra, default_sched))
+
+
+def device_asm_files(variant=""):
+    """the device assembly kept by the last build of the given variant, one file per .hip source"""
+    v = VARIANTS[variant]
+    return sorted(glob.glob(os.path.join(_objdir(v.extra, v.default_sched), "*.device.s")))
+
+
+def device_asm(source, variant=""):
+    """the kept device assembly of one source of the given variant: device_asm("sg_readout.hip")"""
+    v = VARIANTS[variant]
+    path = os.path.join(_objdir(v.extra, v.default_sched), os.path.splitext(source)[0] + ".device.s")
+    if not os.path.exists(path):
+        raise FileNotFoundError("no device assembly of %s kept by the %s build (%s): not a .hip source of that variant, or not built yet"
+                                % (source, variant or "product", path))
+    return path
 
 
 if __name__ == "__main__":
     if "--ko" in sys.argv:  # knock-out / experiment builds: --ko NAME -DFLAG ... -> libsoftgrip_NAME.so
         i = sys.argv.index("--ko")
-        print(_compile(os.path.join(_HERE, "libsoftgrip_%s.so" % sys.argv[i + 1]), sys.argv[i + 2:], False))
+        with _build_lock():
+            print(_compile_locked(os.path.join(_HERE, "libsoftgrip_%s.so" % sys.argv[i + 1]), sys.argv[i + 2:], False, SOURCES, ()))
         sys.exit(0)
     print(build(force="--force" in sys.argv, verbose="-v" in sys.argv, prof="--prof" in sys.argv, count="--count" in sys.argv, legacy="--legacy" in sys.argv))

@@ -19,53 +19,50 @@ block's `s_or_b64 exec, exec, s[..]`.  At such a block exec is 0 until the resto
 does not happen; a compiler never has a reason to put one there.
 
 usage: python isa_check.py file.s [...]      (exit code 1 when a site is found)"""
+import os
 import re
 import sys
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+if _HERE not in sys.path:
+    sys.path.insert(0, _HERE)      # devasm.py (this directory is a package with a hyphen in its name: imported by file)
+import devasm  # noqa: E402
 
 _VEC = re.compile(r"^(v_|ds_|global_|flat_|scratch_|buffer_)")
 _OK = re.compile(r"^v_(readlane|writelane|readfirstlane)_b32")
 _LABEL = re.compile(r"^(\.LBB\d+_\d+):")
-_FUNC = re.compile(r"^(\.?L?_Z\w+|\w+):\s*(;.*)?$")
 
 
 def check_asm_text(text):
     """-> list of (function, block label, [(line number, instruction), ...]) for every flagged block"""
-    lines = text.split("\n")
+    funcs = devasm.functions(text)
     loop_exits = set()
-    for k, l in enumerate(lines):
-        mm = re.match(r"\s*s_cbranch_execz (\.LBB\d+_\d+)", l)
-        if not mm:
-            continue
-        q = k - 1
-        while q > 0 and (not lines[q].strip() or lines[q].strip().startswith((";", ".L", ".loc"))):
-            q -= 1
-        if re.match(r"\s*s_andn2_b64 exec, exec,", lines[q]):
-            loop_exits.add(mm.group(1))
-    out, func = [], None
-    for i, l in enumerate(lines):
-        m = _LABEL.match(l)
-        if not m:
-            f = _FUNC.match(l)
-            if f and not l.startswith("."):
-                func = f.group(1)
-            elif f and l.startswith((".L_Z", "_Z")):
-                func = f.group(1)
-            continue
-        if m.group(1) not in loop_exits:
-            continue
-        j, pre = i + 1, []
-        while j < len(lines):
-            t = lines[j].strip()
-            if _LABEL.match(lines[j]) or t.startswith(("s_cbranch", "s_branch", "s_endpgm", "s_setpc", "s_swappc")):
-                pre = []          # the block has no exec restore of its own: nothing to say about it
-                break
-            if re.match(r"s_or_b64 exec, exec, s\[", t):
-                break
-            if t and not t.startswith((";", ".")) and _VEC.match(t) and not _OK.match(t):
-                pre.append((j + 1, t))
-            j += 1
-        if pre:
-            out.append((func, m.group(1), pre))
+    for body in funcs.values():
+        prev = ""
+        for _, t in body:
+            if t.endswith(":"):       # (a label between the two does not part them)
+                continue
+            m = re.match(r"s_cbranch_execz (\.LBB\d+_\d+)", t)
+            if m and re.match(r"s_andn2_b64 exec, exec,", prev):
+                loop_exits.add(m.group(1))
+            prev = t
+    out = []
+    for func, body in funcs.items():
+        for i, (_, label) in enumerate(body):
+            m = _LABEL.match(label)
+            if not m or m.group(1) not in loop_exits:
+                continue
+            pre = []
+            for n, t in body[i + 1:]:
+                if _LABEL.match(t) or t.startswith(("s_cbranch", "s_branch", "s_endpgm", "s_setpc", "s_swappc")):
+                    pre = []          # the block has no exec restore of its own: nothing to say about it
+                    break
+                if re.match(r"s_or_b64 exec, exec, s\[", t):
+                    break
+                if _VEC.match(t) and not _OK.match(t):
+                    pre.append((n, t))
+            if pre:
+                out.append((func, m.group(1), pre))
     return out
 
 

@@ -158,21 +158,14 @@ def test_kernel_in_the_kept_assembly():
     """sg_contacts_kernel.h is compiled inside sg_readout.hip: both instantiations of the kernel are in sg_readout.device.s, the assembly check is
     clean, no VGPR spills, and the scratch memory is exactly what DESIGN.md 8.1 states: the staging records and the box - box polygon
     work space live in LDS, what is left are the axis tables the shared box - box routine indexes at run time"""
-    from softgrip_amd import build_native, isa_check
+    from softgrip_amd import build_native, isa_check, devasm
     build_native.build()
-    api = [f for f in build_native.device_asm_files() if os.path.basename(f) == "sg_readout.device.s"]
-    assert len(api) == 1
-    assert not isa_check.check_asm(api[0])
-    text = open(api[0]).read()
-    seen = {}
-    for block in text.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        val = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))  # noqa: E731
-        seen[name] = dict(scratch=val("private_segment_fixed_size"), vspill=val("vgpr_spill_count"), sspill=val("sgpr_spill_count"), vgpr=val("vgpr_count"),
-                          agpr=int(re.match(r"\s*(\d+)", block).group(1)), lds=val("group_segment_fixed_size"))
+    api = build_native.device_asm("sg_readout.hip")
+    assert not isa_check.check_asm(api)
+    seen = devasm.kernels(open(api).read())
     con = {k: v for k, v in seen.items() if "sg_contacts_kernel" in k}
     assert len(con) == 2, sorted(seen)
     for k, v in con.items():
         print(k, v)
-        assert v["vspill"] == 0 and v["scratch"] == SCRATCH_BYTES, (k, v)
+        assert v["vgpr_spill"] == 0 and v["scratch"] == SCRATCH_BYTES, (k, v)
         assert v["vgpr"] + v["agpr"] <= 512, (k, v)

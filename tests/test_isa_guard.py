@@ -78,20 +78,11 @@ def test_tree_stage_functions_save_no_callee_saved_registers():
     (build_native.SOURCE_FLAGS: -fno-optimize-sibling-calls for sg_tree.hip).  Held here on the assembly the product build kept: the whole
     unit below 2 500 scratch instructions and every sweep function below 40 (they have 4 - 11), so a flag or compiler change that brings
     the saves back fails the CPU suite instead of showing up as traffic."""
-    import re
-    from softgrip_amd import build_native
+    from softgrip_amd import build_native, devasm
     build_native.build()
-    tree = [f for f in build_native.device_asm_files() if os.path.basename(f) == "sg_tree.device.s"]
-    assert len(tree) == 1
-    total, per, cur = 0, {}, None
-    with open(tree[0]) as f:
-        for line in f:
-            m = re.match(r"^(_Z\w+):", line)
-            if m:
-                cur = m.group(1)
-            elif cur and line.lstrip().startswith("scratch_"):
-                total += 1
-                per[cur] = per.get(cur, 0) + 1
+    funcs = devasm.functions(open(build_native.device_asm("sg_tree.hip")).read())
+    per = {k: sum(t.startswith("scratch_") for _, t in body) for k, body in funcs.items()}
+    total = sum(per.values())
     sweeps = {k: v for k, v in per.items() if "tree_sweep" in k}
     assert total < 2500, total
     assert all(v < 40 for v in sweeps.values()), sweeps
@@ -103,19 +94,10 @@ def test_phase_kernel_lds_blocks_fit_eight_workgroups_per_cu():
     instead of two until its pair list and slot pushes moved to the work space (SG_PHASE_SLIM).  Held here on the assembly the product
     build kept: every instantiation of sg_phase_kernel asks for at most 160 KB / 8 of LDS and for at most 256 registers (two wavefronts per
     SIMD = eight workgroups per CU), so an array added to Smem2 fails the CPU suite instead of showing up as a third round."""
-    import re
-    from softgrip_amd import build_native
+    from softgrip_amd import build_native, devasm
     build_native.build()
-    phase = [f for f in build_native.device_asm_files() if os.path.basename(f) == "sg_phase.device.s"]
-    assert len(phase) == 1
-    text = open(phase[0]).read()
-    seen = {}
-    for block in text.split("  - .agpr_count:")[1:]:           # one metadata entry per kernel
-        name = re.search(r"\.name:\s+(\S+)", block)
-        lds = re.search(r"\.group_segment_fixed_size:\s+(\d+)", block)
-        vg = re.search(r"\.vgpr_count:\s+(\d+)", block)
-        if name and lds and vg and "sg_phase_kernel" in name.group(1):
-            seen[name.group(1)] = (int(lds.group(1)), int(vg.group(1)))
+    kernels = devasm.kernels(open(build_native.device_asm("sg_phase.hip")).read())
+    seen = {k: (v["lds"], v["vgpr"]) for k, v in kernels.items() if "sg_phase_kernel" in k}
     assert len(seen) >= 16, sorted(seen)                        # four element rounds x (neighbour rows or not) x (main pass, general pass)
     for k, (lds, vg) in seen.items():
         assert lds <= 160 * 1024 // 8, (k, lds)

@@ -187,24 +187,17 @@ def test_kernels_in_the_kept_assembly():
     """sg_ray_kernels.h is compiled inside sg_readout.hip: both kernels are in sg_readout.device.s, the assembly check is clean, and they hold what
     DESIGN.md 8.3 states: no scratch, no spills, the lane-per-ray kernel at most 64 registers (eight waves per SIMD) with 256 B of
     static LDS beside the staged records, the lanes-over-geoms kernel at most 128 registers and no LDS"""
-    from softgrip_amd import build_native, isa_check
+    from softgrip_amd import build_native, isa_check, devasm
     build_native.build()
-    api = [f for f in build_native.device_asm_files() if os.path.basename(f) == "sg_readout.device.s"]
-    assert len(api) == 1
-    assert not isa_check.check_asm(api[0])
-    text = open(api[0]).read()
-    seen = {}
-    for block in text.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        val = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))  # noqa: E731
-        seen[name] = dict(scratch=val("private_segment_fixed_size"), vspill=val("vgpr_spill_count"), sspill=val("sgpr_spill_count"), vgpr=val("vgpr_count"),
-                          agpr=int(re.match(r"\s*(\d+)", block).group(1)), lds=val("group_segment_fixed_size"))
+    api = build_native.device_asm("sg_readout.hip")
+    assert not isa_check.check_asm(api)
+    seen = devasm.kernels(open(api).read())
     rays = [v for k, v in seen.items() if "sg_ray_rays_kernel" in k]
     geoms = [v for k, v in seen.items() if "sg_ray_geoms_kernel" in k]
     assert len(rays) == 1 and len(geoms) == 1, sorted(seen)
     print(rays[0], geoms[0])
     for v in rays + geoms:
-        assert v["scratch"] == 0 and v["vspill"] == 0 and v["sspill"] == 0, v
+        assert v["scratch"] == 0 and v["vgpr_spill"] == 0 and v["sgpr_spill"] == 0, v
     assert rays[0]["vgpr"] + rays[0]["agpr"] <= 64 and rays[0]["lds"] <= 256, rays[0]
     assert geoms[0]["vgpr"] + geoms[0]["agpr"] <= 128 and geoms[0]["lds"] == 0, geoms[0]
 

@@ -255,24 +255,17 @@ def test_abi_flag_without_a_device():
 def test_kernels_in_the_kept_assembly():
     """the three kernels of sg_ray_skin_kernels.h are in sg_readout.device.s exactly once each, the assembly check is clean, none has
     scratch or spills, and the lane-per-ray kernel stays within the registers DESIGN.md 8.4 states, with 256 B of static LDS"""
-    from softgrip_amd import build_native, isa_check
+    from softgrip_amd import build_native, isa_check, devasm
     build_native.build()
-    api = [f for f in build_native.device_asm_files() if os.path.basename(f) == "sg_readout.device.s"]
-    assert len(api) == 1
-    assert not isa_check.check_asm(api[0])
-    text = open(api[0]).read()
-    seen = {}
-    for block in text.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        val = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))  # noqa: E731
-        seen[name] = dict(scratch=val("private_segment_fixed_size"), vspill=val("vgpr_spill_count"), sspill=val("sgpr_spill_count"), vgpr=val("vgpr_count"),
-                          agpr=int(re.match(r"\s*(\d+)", block).group(1)), lds=val("group_segment_fixed_size"))
+    api = build_native.device_asm("sg_readout.hip")
+    assert not isa_check.check_asm(api)
+    seen = devasm.kernels(open(api).read())
     kern = {}
     for key in ("sg_skinray_vert_kernel", "sg_skinray_rays_kernel", "sg_skinray_geoms_kernel"):
         found = [v for k, v in seen.items() if key in k]
         assert len(found) == 1, (key, sorted(seen))
         kern[key] = found[0]
-        assert found[0]["scratch"] == 0 and found[0]["vspill"] == 0 and found[0]["sspill"] == 0, (key, found[0])
+        assert found[0]["scratch"] == 0 and found[0]["vgpr_spill"] == 0 and found[0]["sgpr_spill"] == 0, (key, found[0])
     print(kern)
     rays = kern["sg_skinray_rays_kernel"]
     assert rays["vgpr"] + rays["agpr"] <= REG_LIMIT_RAYS and rays["lds"] <= 256, rays

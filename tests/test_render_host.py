@@ -149,22 +149,15 @@ def test_abi_entry_points_without_a_device():
 def test_new_kernels_have_no_scratch_and_no_spills():
     """the kept assembly (sg_readout.device.s: sg_kin_kernels.h is compiled inside sg_readout.hip): both kernels 0 bytes of scratch and no VGPR spills, the render
     kernel at least 4 waves per SIMD by its registers (<= 128) and its LDS (4 waves of 256-lane workgroups per SIMD = 4 per CU)"""
-    from softgrip_amd import build_native
+    from softgrip_amd import build_native, devasm
     build_native.build()
-    api = [f for f in build_native.device_asm_files() if os.path.basename(f) == "sg_readout.device.s"]
-    assert len(api) == 1
-    text = open(api[0]).read()
-    seen = {}
-    for block in text.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        val = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))  # noqa: E731
-        seen[name] = dict(scratch=val("private_segment_fixed_size"), vspill=val("vgpr_spill_count"), vgpr=val("vgpr_count"),
-                          agpr=int(re.match(r"\s*(\d+)", block).group(1)), lds=val("group_segment_fixed_size"))
+    api = build_native.device_asm("sg_readout.hip")
+    seen = devasm.kernels(open(api).read())
     kin = [v for k, v in seen.items() if "sg_kin_kernel" in k]
     ren = [v for k, v in seen.items() if "sg_render_kernel" in k]
     assert len(kin) == 1 and len(ren) == 1, sorted(seen)
     for v in kin + ren:
-        assert v["scratch"] == 0 and v["vspill"] == 0, v
+        assert v["scratch"] == 0 and v["vgpr_spill"] == 0, v
     assert ren[0]["vgpr"] + ren[0]["agpr"] <= 128, ren[0]
     assert 4 * ren[0]["lds"] <= 160 * 1024, ren[0]
 

@@ -361,22 +361,16 @@ def test_set_skin_rejections_leave_the_old_skin_in_place():
 def test_skin_kernels_keep_no_scratch_and_five_workgroups_per_cu():
     """the kept assembly: the skin's two kernels without scratch or spills, the render sibling within 128 registers and at five
     workgroups per CU by its LDS; sg_render_kernel itself still at its 21.4 KB"""
-    from softgrip_amd import build_native
+    from softgrip_amd import build_native, devasm
     build_native.build()
-    api = [f for f in build_native.device_asm_files() if os.path.basename(f) == "sg_readout.device.s"]
-    assert len(api) == 1
-    seen = {}
-    for block in open(api[0]).read().split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        val = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))  # noqa: E731
-        seen[name] = dict(scratch=val("private_segment_fixed_size"), vspill=val("vgpr_spill_count"), vgpr=val("vgpr_count"),
-                          agpr=int(re.match(r"\s*(\d+)", block).group(1)), lds=val("group_segment_fixed_size"))
+    api = build_native.device_asm("sg_readout.hip")
+    seen = devasm.kernels(open(api).read())
     vert = [v for k, v in seen.items() if "sg_skin_vert_kernel" in k]
     ren = [v for k, v in seen.items() if "sg_rskin_kernel" in k]
     plain = [v for k, v in seen.items() if "sg_render_kernel" in k]
     assert len(vert) == 1 and len(ren) == 1 and len(plain) == 1, sorted(seen)
     for v in vert + ren:
-        assert v["scratch"] == 0 and v["vspill"] == 0, v
+        assert v["scratch"] == 0 and v["vgpr_spill"] == 0, v
     assert ren[0]["vgpr"] + ren[0]["agpr"] <= 128, ren[0]
     assert 5 * ren[0]["lds"] <= 160 * 1024, ren[0]
     assert plain[0]["lds"] == 21392, plain[0]
