@@ -270,6 +270,32 @@ int sg_ray(sg_batch* b, const int32_t* env_ids, int n_ids, int n_rays, const dou
            const int32_t* ray_body, const int32_t* ray_exclude, int cat_mask, double max_dist, int flags,
            double* dist, int32_t* geomid, double* normal, void* stream);
 
+/* The recurrence of one direction of one fp64 LSTM layer with H = 128 hidden units (csrc/sg_lstm.hip), for the Conv-LSTM and
+ * Conv-BiLSTM regressors (soft-grip_amd/lstm.py).  Keras' conventions: gate order i, f, g (the candidate), o along the 4H axis, sigmoid
+ * for i, f and o, tanh for g and for the cell, row-major kernels.  The caller keeps what is regular -- the input projection
+ * z = x.kernel + bias for all time steps, and the weight gradients as GEMMs over the stored sequences -- and these two calls do what
+ * is serial in time, each as ONE kernel launch that walks all T steps with h and c on chip.  They need no batch and no model: all
+ * pointers are device pointers on the current device, `stream` is a hipStream_t (NULL: the default stream), and neither call
+ * synchronises the host, allocates or keeps anything: U is read row-major as given, straight from L2, with no re-packing and no scratch.
+ * No atomics: two runs give the same bits, and a batch row's results do not depend on B.
+ *   z      [B][T][4H]  in: x.kernel + bias in CONSUMPTION order (the caller has reversed time for a layer that goes backwards);
+ *                      out when save != 0: the activated gates i, f, g, o in place -- what the backward call takes as `gates`;
+ *                      left as it was when save == 0
+ *   U      [H][4H]     the recurrent kernel: z_t += h_{t-1} . U
+ *   h0, c0 [B][H] or NULL (zeros): the state before the first step
+ *   h_seq  [B][T][H] or NULL: h after every step, in consumption order;  h_last, c_last [B][H] or NULL: the state after step T - 1
+ *   c_seq  [B][T][H]: c after every step; written and required when save != 0, untouched otherwise
+ * SG_ERR_INVALID, checked before anything touches the device: B <= 0 or T <= 0, H != 128, NULL z or U, save without c_seq. */
+int sg_lstm_forward(int B, int T, int H, double* z, const double* U, const double* h0, const double* c0,
+                    double* h_seq, double* h_last, double* c_last, double* c_seq, int save, void* stream);
+/* the reverse-time pass of the same direction.  In: `gates` (z after a saving forward call), c_seq and c0 as there, U, and the gradients
+ * flowing in: dh_seq [B][T][H] or NULL (zeros), with respect to every h of h_seq, and dh_last [B][H] or NULL, added to step T - 1's.
+ * Out: dz [B][T][4H], the gradient with respect to the forward call's input z (the pre-activations), from which the caller forms the
+ * weight gradients; dh0, dc0 [B][H] or NULL, the gradient with respect to the initial state.
+ * SG_ERR_INVALID as above: B <= 0 or T <= 0, H != 128, NULL gates, c_seq, U or dz. */
+int sg_lstm_backward(int B, int T, int H, const double* gates, const double* c_seq, const double* c0, const double* U,
+                     const double* dh_seq, const double* dh_last, double* dz, double* dh0, double* dc0, void* stream);
+
 /* kernel timing hook for bench.py: average device time (ms) of one sg_step/sg_reset call's kernels over the
  * calls since the last call with reset != 0, measured with HIP events on the launch
  * stream.  Synchronises the host. */

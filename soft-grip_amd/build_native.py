@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 if _HERE not in sys.path:
     sys.path.insert(0, _HERE)      # isa_check.py (this directory is a package with a hyphen in its name: imported by file)
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["sg_api.hip", "sg_readout.hip", "sg_phase.hip", "sg_rows.hip", "sg_tree.hip", "sg_plan.cpp", "sg_mjcf.cpp"]   # what the product runs
+SOURCES = ["sg_api.hip", "sg_readout.hip", "sg_phase.hip", "sg_rows.hip", "sg_tree.hip", "sg_lstm.hip", "sg_plan.cpp", "sg_mjcf.cpp"]   # what the product runs
 # -amdgpu-sched-strategy=iterative-ilp: LLVM's iterative ILP machine scheduler instead of the default max-occupancy one.  The
 # kernels run at one or two wavefronts per SIMD whatever their register count (the solver by design, the phase kernel by its
 # LDS), so trading registers for a shorter dependency-stalled schedule is free: solver -2.5 %, phase kernel -4.9 % per episode
@@ -33,6 +33,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-amdg
 # carries the IR's `tail` marker, which the tail-call pass puts on nearly every call.  With the pass off for this file the saves are gone:
 # 10 678 -> 1 554 scratch instructions in the translation unit (scripts/scratch_audit.py, profiles/r05_tree_scratch_audit.txt).
 SOURCE_FLAGS = {"sg_tree.hip": ["-fno-optimize-sibling-calls"]}
+# where a source's object and kept device assembly go below the variant's object directory.  The simulator's translation units sit in the
+# directory itself: device_asm_files() lists exactly those, and tests/test_isa_guard.py holds that list to its five names.  The regressor's
+# LSTM kernels (sg_lstm.hip) are no part of the step path and keep theirs one level down, in nn/: compiled with the same flags, linked
+# into the same library, put through the same isa_check at build time, found by device_asm("sg_lstm.hip") -- and re-checked from there by
+# tests/test_lstm_host.py.
+SOURCE_SUBDIR = {"sg_lstm.hip": "nn"}
 
 
 def _headers():
@@ -117,7 +123,8 @@ def _compile_locked(out, extra, verbose, sources, default_sched):
     def one(src):
         flags = [f for f in flags_all if f not in ("-mllvm", "-amdgpu-sched-strategy=iterative-ilp")] if src in default_sched else flags_all
         own = SOURCE_FLAGS.get(src, [])
-        obj = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
+        obj = os.path.join(objdir, SOURCE_SUBDIR.get(src, ""), os.path.splitext(src)[0] + ".o")
+        os.makedirs(os.path.dirname(obj), exist_ok=True)
         path = os.path.join(CSRC, src)
         if not verbose and not _stale(obj, [path] + hdrs):
             return obj, ""
@@ -155,6 +162,10 @@ def _compile_locked(out, extra, verbose, sources, default_sched):
                 os.replace(dev[0], os.path.splitext(obj)[0] + ".device.s")
                 log += "isa_check: %s clean\n" % src if not bad else describe(bad, src) + "\n"
             os.replace(tmp, obj)
+            if os.path.dirname(obj) != objdir:      # what a build from before the source had a subdirectory left in the directory itself
+                for ext in (".o", ".device.s"):
+                    with contextlib.suppress(FileNotFoundError):
+                        os.remove(os.path.join(objdir, os.path.splitext(src)[0] + ext))
         finally:
             shutil.rmtree(tmpdir, ignore_errors=True)
         return obj, log
@@ -184,7 +195,8 @@ def _objdir(extra, default_sched):
 
 
 def device_asm_files(variant=""):
-    """the device assembly kept by the last build of the given variant, one file per .hip source"""
+    """the device assembly kept by the last build of the given variant, one file per .hip source of the simulator (the sources without a
+    SOURCE_SUBDIR entry; the others' assembly: device_asm(source))"""
     v = VARIANTS[variant]
     return sorted(glob.glob(os.path.join(_objdir(v.extra, v.default_sched), "*.device.s")))
 
@@ -192,7 +204,7 @@ def device_asm_files(variant=""):
 def device_asm(source, variant=""):
     """the kept device assembly of one source of the given variant: device_asm("sg_readout.hip")"""
     v = VARIANTS[variant]
-    path = os.path.join(_objdir(v.extra, v.default_sched), os.path.splitext(source)[0] + ".device.s")
+    path = os.path.join(_objdir(v.extra, v.default_sched), SOURCE_SUBDIR.get(source, ""), os.path.splitext(source)[0] + ".device.s")
     if not os.path.exists(path):
         raise FileNotFoundError("no device assembly of %s kept by the %s build (%s): not a .hip source of that variant, or not built yet"
                                 % (source, variant or "product", path))

@@ -24,6 +24,7 @@ SYMBOLS = [
     "sg_get_touch_words", "sg_model_nboxes", "sg_model_nv", "sg_model_njnt", "sg_tree_workgroups_per_cu",
     "sg_get_poses", "sg_model_nbody", "sg_model_ngeom", "sg_model_default_camera", "sg_render",
     "sg_get_contacts", "sg_model_ncollision_pairs", "sg_model_set_skin", "sg_model_skin", "sg_render_ex", "sg_ray",
+    "sg_lstm_forward", "sg_lstm_backward",
 ]
 SG_RENDER_SKIN = 1
 # sg_ray: category bits of cat_mask (ground plane, static, moving finger box, shell element, centre sphere) and flags
@@ -98,6 +99,8 @@ def load_library(path):
     L.sg_model_ncollision_pairs.argtypes = [vp]
     L.sg_ray.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, dp, dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_double, C.c_int,
                          dp, ip, dp, vp]
+    L.sg_lstm_forward.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int, vp]
+    L.sg_lstm_backward.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, vp]
     L.sg_profile_enable.argtypes = [vp, C.c_int]
     L.sg_profile_read.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
     L.sg_profile_read_solver.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
