@@ -58,17 +58,40 @@ static int tree_alloc(sg_batch* b) {
             A.zeros(&t.cws, n * (size_t)m->tree_cws) && A.zeros(&t.touch_words, 2 * n) && A.upload(&t.sched, m->tplan.sched) &&
             A.upload(&t.nbtab, m->tplan.nbtab) && hipMemcpy(t.H, &m->tplan.h, sizeof(SgPlanHeader), hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(t.T, &m->tree, sizeof(SgTreeDev), hipMemcpyHostToDevice) == hipSuccess;
-  bool nomem = A.nomem;
-  if (ok && !b->w.secprof) {   // (a model outside the two-finger class has no split-pipeline work space)
-    ok = b->mem.zeros(&b->w.secprof, 48);
-    nomem = b->mem.nomem;
-  }
   if (!ok) {
     A.release();
     t = SgTreeBufs();
-    return devmem_fail(nomem, "tree pipeline");
+    return devmem_fail(A.nomem, "tree pipeline");
   }
   b->tree_ready = true;
+  return SG_OK;
+}
+
+// the same for pipelines 0 .. 2: the plan's tables, the solver's (sg_rows_host.h) and the work space, every buffer sized by
+// sg_rows_work_each -- ~0.1 MB per env, which a batch that only ever runs the tree pipeline does not hold
+static int rows_alloc(sg_batch* b) {
+  SgRowsBufs& r = b->r;
+  if (r.ready) return SG_OK;
+  const sg_model* m = b->m;
+  const SgPlanHeader& H = m->plan.h;
+  SgArena& A = b->rows_mem;
+  r.shape = sg_rows_shape(H);
+  r.nsl = sg_rows_nsl(H.nelem);
+  r.w.secprof = b->secprof;
+  bool ok = A.zeros(&r.H, 1) && hipMemcpy(r.H, &H, sizeof H, hipMemcpyHostToDevice) == hipSuccess && A.upload(&r.elem, m->plan.elem) &&
+            A.upload(&r.gpairs, m->plan.gpairs) &&
+            sg_rows_work_each(r.w, H, m->rounds, (size_t)b->n, SG_LEGACY_ON != 0, [&A](auto** p, size_t count) { return A.zeros(p, count); });
+  if (ok && r.shape.nb_mode) {
+    SgRowsTables T;
+    sg_rows_tables(m->plan, &T);
+    ok = A.upload(&r.nbtab, m->plan.nbtab) && A.upload(&r.sched, T.sched) && A.upload(&r.tab, T.tab) && A.upload(&r.cpos, T.cpos);
+  }
+  if (!ok) {
+    A.release();
+    r = SgRowsBufs();
+    return devmem_fail(A.nomem, "rows pipeline");
+  }
+  r.ready = true;
   return SG_OK;
 }
 
@@ -84,7 +107,7 @@ static int launch_tree(sg_batch* b, int mode, const uint8_t* mask, int nsub, dou
   a.flags = flags ? flags : b->flags; a.touch = touch ? touch : b->touch; a.touch_words = b->t.touch_words;
   a.ncon = b->ncon; a.nefc = b->nefc; a.iters = b->iters;
   a.cws = b->t.cws; a.cws_stride = m->tree_cws;
-  a.nenv = b->n; a.nsub = nsub; a.mode = mode; a.secprof = b->w.secprof;
+  a.nenv = b->n; a.nsub = nsub; a.mode = mode; a.secprof = b->secprof;
   if (!b->tree_attr_set) {
     HIPCHK(sg_tree_prepare());
     b->tree_attr_set = true;
@@ -127,11 +150,9 @@ int sg_model_create(const void* blob, size_t nbytes, sg_model** out) {
     delete m;
     return fail(SG_ERR_MODEL, "sg_model_create: more than 256 composite elements");
   }
-  if (m->has_fast && m->plan.h.nnb > 0) {  // the rows PGS kernel keeps every equality row of 8 envs in LDS (launch_split)
-    if (sizeof(double) * SG_ROWS_LDS_NB(4, m->plan.h.nelem, m->plan.h.eq_rounds, 1) > 160 * 1024 || m->plan.h.nelem > 254) {  // (11-bit slider offsets in the table words)
-      delete m;
-      return fail(SG_ERR_MODEL, "sg_model_create: too many neighbour equality rows for the PGS kernel's LDS");
-    }
+  if (m->has_fast && !sg_rows_admits(m->plan.h, &err)) {
+    delete m;
+    return fail(SG_ERR_MODEL, "sg_model_create: " + err);
   }
   *out = m;
   return SG_OK;
@@ -188,6 +209,19 @@ void sg_batch_destroy(sg_batch* b) {
   delete b;
 }
 
+// the pipeline a new batch starts on: the rows pipeline for the two-finger class, unless SG_PIPELINE names another that runs the model
+static int first_pipeline(const sg_model* m) {
+  if (!m->has_fast) return 3;
+  const char* pm = getenv("SG_PIPELINE");
+  int p = (pm && strcmp(pm, "tree") == 0 && m->has_tree) ? 3 : 2;
+#ifdef SG_LEGACY_PIPELINES
+  if (pm && strcmp(pm, "fused") == 0) p = 0;
+  if (pm && strcmp(pm, "split") == 0) p = 1;
+#endif
+  if (m->plan.h.nnb > 0 && p != 3) p = 2;  // neighbour equality rows: the rows pipeline (or the tree pipeline when asked for)
+  return p;
+}
+
 int sg_batch_create(const sg_model* m, int n_envs, int device, sg_batch** out) {
   if (!m || !out || n_envs <= 0) return fail(SG_ERR_INVALID, "sg_batch_create: bad argument");
   int ndev = 0;
@@ -200,62 +234,14 @@ int sg_batch_create(const sg_model* m, int n_envs, int device, sg_batch** out) {
   SgArena& A = b->mem;
   const SgPlanHeader& H = m->plan.h;
   const size_t n = n_envs, nv = H.nv, nq = H.nq, njnt = H.njnt, nu = H.nu, nt = H.ntendon;   // nq = nv = njnt unless the model has a free joint
-  bool ok = A.zeros(&b->dH, 1) && hipMemcpy(b->dH, &H, sizeof H, hipMemcpyHostToDevice) == hipSuccess && A.upload(&b->delem, m->plan.elem) &&
-            A.zeros(&b->qpos, n * nq) && A.zeros(&b->qvel, n * nv) && A.zeros(&b->warm, n * nv) && A.zeros(&b->act, n * nu) &&
+  bool ok = A.zeros(&b->qpos, n * nq) && A.zeros(&b->qvel, n * nv) && A.zeros(&b->warm, n * nv) && A.zeros(&b->act, n * nu) &&
             A.zeros(&b->ctrl, n * nu) && A.zeros(&b->kenv, n) && A.zeros(&b->ctrl_row, nu) && A.zeros(&b->kmask_jnt, njnt) &&
             A.zeros(&b->kmask_ten, nt) && A.zeros(&b->flags, n) && A.zeros(&b->touch, n) && A.zeros(&b->ncon, n) && A.zeros(&b->nefc, n) &&
-            A.zeros(&b->iters, n) && A.upload(&b->dgpairs, m->plan.gpairs);
+            A.zeros(&b->iters, n) && A.zeros(&b->secprof, 48);
   if (!ok) return devmem_fail(A.nomem, "sg_batch_create (state)");
   b->kmask_jnt_host.assign(njnt, 0); b->kmask_ten_host.assign(nt, 0);
-  if (m->has_fast) {  // work space of the split pipeline
-    const size_t S = 2 * n, N = H.nelem;
-    SgWork& w = b->w;
-    ok = A.zeros(&w.secprof, 48) && A.zeros(&w.crec, SG_LEGACY_ON ? SG_CAP * ((n + SG_EPW - 1) / SG_EPW + 1) * SG_RF * SG_SPW : 0) && A.zeros(&w.ns, S) &&
-         A.zeros(&w.crow, (SG_CAP + 2) * ((n + 7) / 8 + 2) * SG_RK * 64) && A.zeros(&w.cdummy, ((n + 3) / 4) * SG_RK * 64) &&
-         A.zeros(&w.envh, 4 * n) && A.zeros(&w.shared, n) && A.zeros(&w.pending, n) && A.zeros(&w.status, n) && A.zeros(&w.iters, n) &&
-         A.zeros(&w.ncon, n) && A.zeros(&w.nefc, n) && A.zeros(&w.touch, n) && A.zeros(&w.sMinv, 16 * S) && A.zeros(&w.saF, 4 * S) &&
-         A.zeros(&w.lim_active, S) && A.zeros(&w.lim, 4 * SG_MAXLIM * S) && A.zeros(&w.as, n * N) && A.zeros(&w.eqf, n * N) &&
-         A.zeros(&w.eqb, n * N) && A.zeros(&w.eqR, n * N) && A.zeros(&w.asme, n * N) && A.zeros(&w.fsm, n * N) &&
-         A.zeros(&w.chh, n * 2 * SG_CHW) && A.zeros(&w.nbf, n * (3 * N + 1)) && A.zeros(&w.nbb, n * (3 * N + 1)) && A.zeros(&w.nbR, n * (3 * N + 1)) &&
-         A.zeros(&w.cst, (H.nnb > 0 && SG_ROWS_NB_MODE(H.nelem, H.eq_rounds) == 2) ? SG_CST_INDEX((n + 3) / 4, 0, 0, H.eq_rounds + 8) : 0) &&
-         A.zeros(&w.gcon, n * SG_GEN_MAXCON * SG_GEN_W) && A.zeros(&w.gen, n) && A.zeros(&w.gen_count, 4) && A.zeros(&w.gen_list, n) &&
-         A.zeros(&w.gpairs16, SG_PHASE_SLIM(m->rounds) ? n * SG_PAIRS_CAP(4) : 0) && A.zeros(&w.gcval, SG_PHASE_SLIM(m->rounds) ? n * SG_MAXCH * 64 : 0);
-    if (!ok) return devmem_fail(A.nomem, "sg_batch_create (split-pipeline work space)");
-    const char* pm = getenv("SG_PIPELINE");
-    b->pipeline = (pm && strcmp(pm, "tree") == 0 && m->has_tree) ? 3 : 2;
-#ifdef SG_LEGACY_PIPELINES
-    if (pm && strcmp(pm, "fused") == 0) b->pipeline = 0;
-    if (pm && strcmp(pm, "split") == 0) b->pipeline = 1;
-#endif
-    if (H.nnb > 0 && b->pipeline != 3) b->pipeline = 2;  // neighbour equality rows: the rows pipeline (or the tree pipeline when asked for)
-  }
-  if (m->has_fast && H.nnb > 0) {
-    std::vector<SgEqSlot> sch = m->plan.sched;
-    SgEqSlot idle;
-    idle.e = idle.p[0] = idle.p[1] = idle.p[2] = H.nelem;
-    for (int g = 0; g < 8 * SG_EQ_SLOTS; g++) sch.push_back(idle);  // the kernel fetches slots a few rounds ahead
-    // the solver's table words (sg_pgs_rows_kernel): lane 2 b + h of a 16-lane group holds, for the block e in slot b of the round,
-    // x | y << 11 | (2 e + h) << 22: the byte offsets of two slider words, (x, y) = 8 (e, p0) for h = 0 and 8 (p1, p2) for h = 1, and the
-    // lane's pair of row states in 16-byte units
-    // (models that keep the step factors in LDS -- SG_ROWS_NB_MODE 1, the box scene -- get TWO words per lane and round instead:
-    //  x | y << 16 and the byte offset of the lane's pair of 32-byte records)
-    const bool two_words = SG_ROWS_NB_MODE(H.nelem, H.eq_rounds) == 1;
-    std::vector<unsigned> tab((two_words ? 4 : 2) * sch.size());
-    for (size_t i = 0; i < 2 * sch.size(); i++) {
-      const SgEqSlot& sl = sch[i >> 1];
-      const int h = (int)(i & 1);
-      const unsigned x = h ? sl.p[1] : sl.e, y = h ? sl.p[2] : sl.p[0];
-      if (two_words) { tab[2 * i] = (8u * x) | ((8u * y) << 16); tab[2 * i + 1] = 64u * (unsigned)sl.e + 32u * (unsigned)h; }
-      else tab[i] = (8u * x) | ((8u * y) << 11) | ((2u * (unsigned)sl.e + (unsigned)h) << 22);
-    }
-    // where the phase kernel puts a block's four step factors: round r, slot g of the schedule = lanes 2 g, 2 g + 1 of the env's
-    // 16-lane group, two doubles each (SG_CST_INDEX)
-    std::vector<int> cpos(H.nelem, 0);
-    for (size_t i = 0; i < m->plan.sched.size(); i++)
-      if (m->plan.sched[i].e < H.nelem) cpos[m->plan.sched[i].e] = (int)(i / SG_EQ_SLOTS) * 128 + 4 * (int)(i % SG_EQ_SLOTS);
-    if (!(A.upload(&b->dnbtab, m->plan.nbtab) && A.upload(&b->dsched, sch) && A.upload(&b->dtab, tab) && A.upload(&b->dcpos, cpos)))
-      return devmem_fail(A.nomem, "sg_batch_create (solver tables)");
-  }
+  b->pipeline = first_pipeline(m);
+  if (int rc = b->pipeline == 3 ? tree_alloc(b) : rows_alloc(b)) return rc;
   // state as after mj_resetData
   std::vector<double> q0(nq, 0.0);
   for (int c = 0; c < H.nchain; c++)
@@ -268,8 +254,6 @@ int sg_batch_create(const sg_model* m, int n_envs, int device, sg_batch** out) {
   std::vector<double> qall(n * nq);
   for (size_t i = 0; i < n; i++) memcpy(&qall[i * nq], q0.data(), sizeof(double) * nq);
   HIPCHK(hipMemcpy(b->qpos, qall.data(), sizeof(double) * n * nq, hipMemcpyHostToDevice));
-  if (b->pipeline == 3)
-    if (int rc = tree_alloc(b)) return rc;
   *out = guard.release();
   return SG_OK;
 }
@@ -378,33 +362,33 @@ static int solver_epw(const sg_batch* b) {
 static int launch_split(sg_batch* b, int mode, const uint8_t* mask, int nsub, double* sens, long long stride, int32_t* flags, int32_t* touch,
                         hipStream_t s) {
   const SgPlanHeader& H = b->m->plan.h;
+  SgRowsBufs& r = b->r;   // (allocated: the batch is on pipeline 1 or 2, sg_batch_create / sg_set_pipeline)
   SgPhaseArgs pa;
-  pa.H = b->dH; pa.elem = b->delem;
+  pa.H = r.H; pa.elem = r.elem;
   pa.qpos = b->qpos; pa.qvel = b->qvel; pa.warm = b->warm; pa.act = b->act; pa.ctrl = b->ctrl;
   pa.kenv = b->kenv; pa.kmask_jnt = b->kmask_jnt; pa.kmask_ten = b->kmask_ten;
   pa.mask = mask; pa.sens = nullptr; pa.sens_stride = stride > 0 ? stride : H.nsensordata;
-  pa.w = b->w; pa.nenv = b->n; pa.rowlayout = b->pipeline == 2;
-  pa.nbtab = b->dnbtab; pa.cpos = b->dcpos; pa.cst_rounds = (H.nnb > 0 && SG_ROWS_NB_MODE(H.nelem, H.eq_rounds) == 2) ? H.eq_rounds + 8 : 0;
-  pa.gpairs = b->dgpairs;
+  pa.w = r.w; pa.nenv = b->n; pa.rowlayout = b->pipeline == 2;
+  pa.nbtab = r.nbtab; pa.cpos = r.cpos; pa.cst_rounds = r.shape.cst_rounds;
+  pa.gpairs = r.gpairs;
   pa.nelem = H.nelem; pa.nv = H.nv; pa.nu = H.nu; pa.elem_dof0 = H.elem_dof0; pa.nchain = H.nchain; pa.t0_id = H.t0_id; pa.timestep = H.timestep;
   SgPgsArgs ga;
-  ga.sched = b->dsched; ga.nbtab = b->dnbtab; ga.tab = b->dtab;
-  ga.H = b->dH; ga.elem = b->delem; ga.w = b->w; ga.nenv = b->n;
-  const size_t lds = sizeof(double) * ((size_t)(5 * 8 + 2) * H.nelem + 16 * 4 * SG_MAXLIM + 72);   // (split pipeline, test builds)
-  (void)lds;
-  // rows kernel: joint-fix rows per lane (template parameter, the smallest instantiated value >= ceil(nelem / 8)); its LDS
+  ga.sched = r.sched; ga.nbtab = r.nbtab; ga.tab = r.tab;
+  ga.H = r.H; ga.elem = r.elem; ga.w = r.w; ga.nenv = b->n;
+#ifdef SG_LEGACY_PIPELINES
+  const size_t lds = sizeof(double) * ((size_t)(5 * 8 + 2) * H.nelem + 16 * 4 * SG_MAXLIM + 72);   // (the split pipeline's solver)
+#endif
+  // rows kernel: joint-fix rows per lane r.nsl (template parameter, the smallest instantiated value >= ceil(nelem / 8)); its LDS
   // arrays are padded to 8 * NSL rows
-  const int nsl = sg_rows_nsl(H.nelem);
-  const bool nbm = H.nnb > 0;
+  const bool nbm = r.shape.nb_mode != 0;
   const int epw = solver_epw(b);
-  const int nbmode = nbm ? SG_ROWS_NB_MODE(H.nelem, H.eq_rounds) : 0;
-  const size_t lds_rows = sizeof(double) * (nbm ? SG_ROWS_LDS_NB(epw, H.nelem, H.eq_rounds, nbmode == 2) : SG_ROWS_LDS_FIX(epw, 8 * (size_t)nsl));
-  if (!b->lds_attr_set) {  // per device: a batch on another GPU of the same process needs its own call
+  const size_t lds_rows = sizeof(double) * r.shape.lds_doubles(epw, r.nsl);
+  if (!r.attr_set) {  // per device: a batch on another GPU of the same process needs its own call
     HIPCHK(sg_rows_prepare());
 #ifdef SG_LEGACY_PIPELINES
     HIPCHK(sg_legacy_prepare());
 #endif
-    b->lds_attr_set = true;
+    r.attr_set = true;
   }
   // forward passes to run: (mode 1: one non-integrating forward first) + nsub integrating ones
   const int nfwd = nsub + (mode == 1 ? 1 : 0);
@@ -431,7 +415,7 @@ static int launch_split(sg_batch* b, int mode, const uint8_t* mask, int nsub, do
     if (k < nfwd) {
       if (b->prof)
         if (int rc = begin_event_pair(b, b->ev_pgs, s)) return rc;
-      if (b->pipeline == 2) HIPCHK(sg_launch_rows(ga, nsl, nbmode, epw, b->n, lds_rows, s));
+      if (b->pipeline == 2) HIPCHK(sg_launch_rows(ga, r.nsl, r.shape.nb_mode, epw, b->n, lds_rows, s));
 #ifdef SG_LEGACY_PIPELINES
       else HIPCHK(sg_launch_pgs_split(ga, b->n, lds, s));
 #endif
@@ -441,8 +425,8 @@ static int launch_split(sg_batch* b, int mode, const uint8_t* mask, int nsub, do
   if (b->prof) HIPCHK(hipEventRecord(b->ev[call_ev].second, s));
   // outputs of the call: one small kernel for the five per-env int arrays (five device-to-device copies cost 1 % of a step);
   // with a mask (masked reset) only the selected envs' entries may change
-  hipLaunchKernelGGL(sg_masked_copy_kernel, dim3((b->n + 255) / 256), dim3(256), 0, s, mask, b->n, b->w.status, flags ? flags : b->flags,
-                     b->w.touch, touch ? touch : b->touch, b->w.ncon, b->ncon, b->w.nefc, b->nefc, b->w.iters, b->iters);
+  hipLaunchKernelGGL(sg_masked_copy_kernel, dim3((b->n + 255) / 256), dim3(256), 0, s, mask, b->n, r.w.status, flags ? flags : b->flags,
+                     r.w.touch, touch ? touch : b->touch, r.w.ncon, b->ncon, r.w.nefc, b->nefc, r.w.iters, b->iters);
   HIPCHK(hipGetLastError());
   return SG_OK;
 }
@@ -454,7 +438,7 @@ static int launch(sg_batch* b, int mode, const uint8_t* mask, int nsub, double* 
 #ifdef SG_LEGACY_PIPELINES
   const SgPlanHeader& H = b->m->plan.h;
   SgKArgs a;
-  a.H = b->dH; a.elem = b->delem;
+  a.H = b->r.H; a.elem = b->r.elem;
   a.qpos = b->qpos; a.qvel = b->qvel; a.warm = b->warm; a.act = b->act; a.ctrl = b->ctrl;
   a.kenv = b->kenv; a.kmask_jnt = b->kmask_jnt; a.kmask_ten = b->kmask_ten;
   a.mask = mask;
@@ -536,6 +520,8 @@ int sg_set_pipeline(sg_batch* b, int pipeline) {
 #endif
   if (b->m->plan.h.nnb > 0 && pipeline != 2)
     return fail(SG_ERR_MODEL, "sg_set_pipeline: the model has neighbour equality rows, which only the rows pipeline supports");
+  HIPCHK(hipSetDevice(b->device));
+  if (int rc = rows_alloc(b)) return rc;   // (a batch that started on the tree pipeline)
   b->pipeline = pipeline;
   return SG_OK;
 }
@@ -549,7 +535,7 @@ int sg_get_touch_words(sg_batch* b, int32_t* out, int nwords, void* stream) {
     HIPCHK(hipMemcpy2DAsync(out, sizeof(int32_t) * nwords, b->t.touch_words, sizeof(int32_t) * 2, sizeof(int32_t) * (nwords < 2 ? nwords : 2), b->n,
                             hipMemcpyDeviceToDevice, s));
   else
-    HIPCHK(hipMemcpy2DAsync(out, sizeof(int32_t) * nwords, b->pipeline == 0 ? b->touch : b->w.touch, sizeof(int32_t), sizeof(int32_t), b->n,
+    HIPCHK(hipMemcpy2DAsync(out, sizeof(int32_t) * nwords, b->pipeline == 0 ? b->touch : b->r.w.touch, sizeof(int32_t), sizeof(int32_t), b->n,
                             hipMemcpyDeviceToDevice, s));
   return SG_OK;
 }
@@ -584,8 +570,8 @@ int sg_debug_sections(sg_batch* b, unsigned long long* out32) {
   if (!b || !out32) return fail(SG_ERR_INVALID, "sg_debug_sections: bad argument");
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out32, b->w.secprof, sizeof(unsigned long long) * 48, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemset(b->w.secprof, 0, sizeof(unsigned long long) * 48));
+  HIPCHK(hipMemcpy(out32, b->secprof, sizeof(unsigned long long) * 48, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemset(b->secprof, 0, sizeof(unsigned long long) * 48));
   return SG_OK;
 }
 #endif

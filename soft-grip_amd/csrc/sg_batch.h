@@ -8,7 +8,7 @@
 
 #include "sg_readout.h"
 #include "sg_skin.h"
-#include "sg_work.h"
+#include "sg_rows_host.h"   // (sg_work.h, sg_plan.h)
 #include "sg_devmem.h"   // SgArena, SgScratch: the owners of every device buffer below (after the HIP runtime's declarations)
 
 // the thread's error text (sg_last_error; one object, in sg_api.hip) and the code handed back
@@ -46,18 +46,31 @@ struct SgTreeBufs {
   int* touch_words = nullptr;   // [n][2]
 };
 
+// device tables and work space of the rows pipeline (sg_phase.hip, sg_rows.hip; in legacy builds also of the fused and split pipelines),
+// allocated when a pipeline 0 .. 2 is first selected.  What goes into them and how large they are: sg_rows_host.h
+struct SgRowsBufs {
+  SgPlanHeader* H = nullptr;
+  double* elem = nullptr;
+  SgGenPair* gpairs = nullptr;  // SgPlan::gpairs (the general contact path's candidate pairs)
+  int* nbtab = nullptr;         // neighbour-row models: SgPlan::nbtab and the three tables of SgRowsTables
+  SgEqSlot* sched = nullptr;
+  unsigned* tab = nullptr;
+  int* cpos = nullptr;
+  SgWork w = {};                // (w.secprof: the batch's)
+  SgRowsShape shape;
+  int nsl = 0;                  // sg_rows_nsl(nelem): the solver instantiation's joint-fix rows per lane
+  bool ready = false;           // every table and the work space allocated and filled (rows_alloc)
+  bool attr_set = false;        // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done on this batch's device
+};
+
 struct sg_batch {
   const sg_model* m = nullptr;
   int n = 0, device = 0;
-  SgArena mem;       // every buffer that lives as long as the batch: state, tables, the rows work space, the read-outs' tables
+  SgArena mem;       // every buffer that lives as long as the batch: state, the read-outs' tables
   SgArena tree_mem;  // the buffers of `t`: all of them or none (tree_alloc)
-  SgPlanHeader* dH = nullptr;
-  double *delem = nullptr, *qpos = nullptr, *qvel = nullptr, *warm = nullptr, *act = nullptr, *ctrl = nullptr, *kenv = nullptr, *ctrl_row = nullptr;
-  SgGenPair* dgpairs = nullptr;  // SgPlan::gpairs on the device (the general contact path's candidate pairs)
-  int* dnbtab = nullptr;       // SgPlan::nbtab on the device (neighbour-row models)
-  SgEqSlot* dsched = nullptr;  // SgPlan::sched + eight spare rounds of idle slots
-  unsigned* dtab = nullptr;    // the same schedule as the solver's LDS table words
-  int* dcpos = nullptr;        // per element: where its equality block's step factors sit in a solver wavefront's stream (SgWork::cst)
+  SgArena rows_mem;  // the buffers of `r`: all of them or none (rows_alloc)
+  double *qpos = nullptr, *qvel = nullptr, *warm = nullptr, *act = nullptr, *ctrl = nullptr, *kenv = nullptr, *ctrl_row = nullptr;
+  unsigned long long* secprof = nullptr;   // [48] cycle sums per kernel section of whichever pipeline runs (written by -DSG_SECTION_PROF builds only)
   int *kmask_jnt = nullptr, *kmask_ten = nullptr, *flags = nullptr, *touch = nullptr, *ncon = nullptr, *nefc = nullptr, *iters = nullptr;
   std::vector<int> kmask_jnt_host, kmask_ten_host;   // what the device masks hold (sg_set_stiffness copies them only when they change)
   int epw_override = 0;  // sg_set_solver_envs_per_wavefront: 0 = automatic
@@ -65,8 +78,7 @@ struct sg_batch {
   SgTreeBufs t;
   bool tree_ready = false;    // every table and the work space of the tree pipeline allocated and filled (tree_alloc)
   bool tree_attr_set = false;
-  SgWork w = {};
-  bool lds_attr_set = false;  // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done on this batch's device
+  SgRowsBufs r;
   // profiling
   bool prof = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;

@@ -191,7 +191,7 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
     }
   }
   if constexpr (NB) {  // the schedule (plus eight idle rounds: padding to a multiple of four and the look-ahead) as LDS offsets: lane 2 b + h of a group, block slot b
-    const int ntab = 16 * TABW * (H.eq_rounds + 8);   // a.tab: the same words, laid out by the host once per batch (sg_api.hip)
+    const int ntab = 16 * TABW * (H.eq_rounds + 8);   // a.tab: the same words, laid out by the host once per batch (sg_rows_host.h)
 #pragma unroll 4
     for (int i = lane; i < ntab; i += 64) TAB[i] = a.tab[i];
   }

@@ -1,0 +1,112 @@
+// sg_rows_host.h -- the host side of the rows pipeline (sg_phase.hip, sg_rows.hip), in one place and free of device calls: which models
+// the solver admits, the shape of its launch, the solver's tables as the kernels decode them, and the size of every buffer of SgWork.
+// sg_api.hip's rows_alloc and launch_split are its users in the library; tests/emu/sg_rows_host_test.cpp holds it against the kernels'
+// indexing rules (SG_ROW_INDEX, SG_CST_INDEX, the table decode of sg_pgs_rows_kernel) on the host.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "sg_plan.h"
+#include "sg_work.h"
+
+// ---- the solver's table words (sg_pgs_rows_kernel: adr_of) ----
+// Lane 2 b + h of an env's 16-lane group holds, for the block e in slot b of a round, the byte offsets (x, y) of two slider words in the
+// env's slider array -- (x, y) = 8 (e, p0) for h = 0 and 8 (p1, p2) for h = 1 -- and where the lane's pair of row states sits:
+//   streamed step factors (NB = 2): ONE word   x | y << SG_TAB1_YSH | (2 e + h) << SG_TAB1_RSH    the pair of states in 16-byte units
+//   step factors in LDS   (NB = 1): TWO words  x | y << SG_TAB2_YSH,  64 e + 32 h                   the byte offset of two 32-byte records
+constexpr int SG_TAB1_YSH = 11, SG_TAB1_RSH = 22, SG_TAB2_YSH = 16;
+// what the narrowest field admits: an env's slider array -- nelem sliders, the zero word and a word of padding -- within reach of an
+// 11-bit byte offset
+constexpr int SG_ROWS_MAX_NELEM = (1 << SG_TAB1_YSH) / 8 - 2;
+static_assert(SG_ROWS_MAX_NELEM == 254 && 2 * SG_ROWS_MAX_NELEM + 1 < (1 << (32 - SG_TAB1_RSH)) && SG_TAB1_RSH - SG_TAB1_YSH >= SG_TAB1_YSH &&
+              8 * (SG_ROWS_MAX_NELEM + 2) <= (1 << SG_TAB2_YSH), "every field of a table word holds its largest value");
+
+// does the rows solver run a two-finger model?  (neighbour-row models: the kernel keeps every equality row of its envs in LDS)
+inline bool sg_rows_admits(const SgPlanHeader& H, std::string* err) {
+  if (H.nnb > 0 && (sizeof(double) * SG_ROWS_LDS_NB(4, H.nelem, H.eq_rounds, 1) > 160 * 1024 || H.nelem > SG_ROWS_MAX_NELEM)) {
+    if (err) *err = "too many neighbour equality rows for the PGS kernel's LDS";
+    return false;
+  }
+  return true;
+}
+
+// what a model fixes of the solver's launch
+struct SgRowsShape {
+  int nelem = 0, eq_rounds = 0;
+  int nb_mode = 0;         // template parameter NB of sg_pgs_rows_kernel: 0 no neighbour rows, 1 their step factors in LDS, 2 streamed (SgWork::cst)
+  bool two_words = false;  // the table has two words per lane and round (nb_mode 1)
+  int cst_rounds = 0;      // rounds of SgWork::cst per solver wavefront: eq_rounds + 8 (nb_mode 2), else 0 -- nothing to stream
+  size_t tab_words = 0;    // the table: 16 lanes x (1 | 2) words x (eq_rounds + 8) rounds, 0 without neighbour rows
+  // the kernel's LDS block in doubles: epw envs per wavefront; nsl (sg_rows_nsl) pads the joint-fix rows of a model without neighbour rows
+  size_t lds_doubles(int epw, int nsl) const {
+    return nb_mode ? SG_ROWS_LDS_NB(epw, nelem, eq_rounds, nb_mode == 2) : SG_ROWS_LDS_FIX(epw, 8 * (size_t)nsl);
+  }
+};
+inline SgRowsShape sg_rows_shape(const SgPlanHeader& H) {
+  SgRowsShape s;
+  s.nelem = H.nelem; s.eq_rounds = H.eq_rounds;
+  s.nb_mode = H.nnb > 0 ? SG_ROWS_NB_MODE(H.nelem, H.eq_rounds) : 0;
+  s.two_words = s.nb_mode == 1;
+  s.cst_rounds = s.nb_mode == 2 ? H.eq_rounds + 8 : 0;
+  s.tab_words = s.nb_mode ? (size_t)16 * (s.two_words ? 2 : 1) * (H.eq_rounds + 8) : 0;
+  return s;
+}
+
+// the tables of a neighbour-row model, as the batch uploads them
+struct SgRowsTables {
+  std::vector<SgEqSlot> sched;  // SgPlan::sched + eight spare rounds of idle slots (the kernel fetches slots a few rounds ahead)
+  std::vector<unsigned> tab;    // the same schedule as the solver's table words (above)
+  std::vector<int> cpos;        // per element: where the phase kernel puts its block's four step factors (SgPhaseArgs::cpos)
+};
+inline void sg_rows_tables(const SgPlan& P, SgRowsTables* T) {
+  const SgPlanHeader& H = P.h;
+  T->sched = P.sched;
+  SgEqSlot idle;
+  idle.e = idle.p[0] = idle.p[1] = idle.p[2] = H.nelem;
+  for (int g = 0; g < 8 * SG_EQ_SLOTS; g++) T->sched.push_back(idle);
+  const std::vector<SgEqSlot>& sch = T->sched;
+  const bool two_words = sg_rows_shape(H).two_words;
+  T->tab.assign((two_words ? 4 : 2) * sch.size(), 0u);
+  for (size_t i = 0; i < 2 * sch.size(); i++) {
+    const SgEqSlot& sl = sch[i >> 1];
+    const int h = (int)(i & 1);
+    const unsigned x = h ? sl.p[1] : sl.e, y = h ? sl.p[2] : sl.p[0];
+    if (two_words) { T->tab[2 * i] = (8u * x) | ((8u * y) << SG_TAB2_YSH); T->tab[2 * i + 1] = 64u * (unsigned)sl.e + 32u * (unsigned)h; }
+    else T->tab[i] = (8u * x) | ((8u * y) << SG_TAB1_YSH) | ((2u * (unsigned)sl.e + (unsigned)h) << SG_TAB1_RSH);
+  }
+  // round r, slot g of the schedule = lanes 2 g, 2 g + 1 of the env's 16-lane group, two doubles each (SG_CST_INDEX): doubles from the
+  // start of the env's group in round 0
+  T->cpos.assign(H.nelem, 0);
+  for (size_t i = 0; i < P.sched.size(); i++)
+    if (P.sched[i].e < H.nelem) T->cpos[P.sched[i].e] = (int)(i / SG_EQ_SLOTS) * 128 + 4 * (int)(i % SG_EQ_SLOTS);
+}
+
+// Every buffer of SgWork with its element count, in one place: f(&w.member, count) for each, until one call returns false.  rounds =
+// ceil(nelem / 64); legacy: the build has the split pipeline's solver (its contact records, 126 MB at 4096 envs, are otherwise not
+// allocated).  SgWork::secprof is not here: it belongs to the batch, whichever pipeline runs.  A count of 0 is a buffer no kernel of
+// this model touches (it still gets a pointer of its own).
+template <class F>
+bool sg_rows_work_each(SgWork& w, const SgPlanHeader& H, int rounds, size_t n, bool legacy, F&& f) {
+  const size_t S = 2 * n, N = H.nelem;   // finger streams, elements
+  const bool slim = SG_PHASE_SLIM(rounds);
+  return f(&w.crec, legacy ? SG_CAP * ((n + SG_EPW - 1) / SG_EPW + 1) * SG_RF * SG_SPW : 0) &&   // [SG_CAP][nwb + 1][SG_RF][16]
+         f(&w.ns, S) &&                                                       // [S]
+         f(&w.crow, (SG_CAP + 2) * ((n + 7) / 8 + 2) * SG_RK * 64) &&         // [SG_CAP + 2][nwb + 2][SG_RK / 2][64][2]
+         f(&w.cdummy, ((n + 3) / 4) * SG_RK * 64) &&                          // [ceil(n / 4)][SG_RK / 2][64][2]
+         f(&w.envh, 4 * n) &&                                                 // [4][n]
+         f(&w.shared, n) && f(&w.pending, n) && f(&w.status, n) && f(&w.iters, n) && f(&w.ncon, n) && f(&w.nefc, n) && f(&w.touch, n) &&   // [n]
+         f(&w.sMinv, 16 * S) &&                                               // [16][S]
+         f(&w.saF, 4 * S) &&                                                  // [4][S]
+         f(&w.lim_active, S) &&                                               // [S]
+         f(&w.lim, 4 * SG_MAXLIM * S) &&                                      // [4][SG_MAXLIM][S]
+         f(&w.as, n * N) && f(&w.eqf, n * N) && f(&w.eqb, n * N) && f(&w.eqR, n * N) && f(&w.asme, n * N) && f(&w.fsm, n * N) &&   // [n][N]
+         f(&w.chh, n * 2 * SG_CHW) &&                                         // [n][2][SG_CHW]
+         f(&w.nbf, n * (3 * N + 1)) && f(&w.nbb, n * (3 * N + 1)) && f(&w.nbR, n * (3 * N + 1)) &&   // [n][3 N] (+ 1 each)
+         f(&w.cst, sg_rows_shape(H).cst_rounds ? SG_CST_INDEX((n + 3) / 4, 0, 0, H.eq_rounds + 8) : 0) &&   // [ceil(n / 4)][eq_rounds + 8][64][2]
+         f(&w.gcon, n * SG_GEN_MAXCON * SG_GEN_W) &&                          // [n][SG_GEN_MAXCON][SG_GEN_W]
+         f(&w.gen, n) &&                                                      // [n]
+         f(&w.gen_count, 4) &&                                                // [1] (+ 3)
+         f(&w.gen_list, n) &&                                                 // [n]
+         f(&w.gpairs16, slim ? n * SG_PAIRS_CAP(4) : 0) &&                    // [n][SG_MAXCH * SG_CG * (4 * 64 + 2)]
+         f(&w.gcval, slim ? n * SG_MAXCH * 64 : 0);                           // [n][SG_MAXCH][64]
+}

@@ -3,7 +3,7 @@
 //
 // One translation unit per kernel family -- sg_phase.hip (sg_chain_kernel, sg_phase_kernel), sg_rows.hip (sg_pgs_rows_kernel: the
 // solver), sg_tree.hip (the tree pipeline) and, in test builds only (-DSG_LEGACY_PIPELINES), sg_legacy.hip (r01's fused and split
-// pipelines, kept as cross-checks) -- compiled side by side; sg_api.hip (the C ABI) sees the launchers below and nothing else.
+// pipelines, kept as cross-checks) -- compiled side by side; sg_api.hip (the C ABI) sees the launchers below and nothing else, and sizes and fills what they take through sg_rows_host.h.
 // A substep of the rows pipeline is the chain   chain -> phase(finish + begin) -> [general pass] -> pgs_rows.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -28,7 +28,7 @@ using namespace sgm;
 #define SG_GEN_GRID 256  // blocks of the general contact pass (they stride over the listed envs: no limit on how many there are)
 #define SG_CHW 160       // doubles of chain hand-off per stream (layout: see sg_chain_kernel)
 
-struct SgWork {          // device workspace of one batch (all pointers device memory)
+struct SgWork {          // device workspace of one batch (all pointers device memory; every member's element count: sg_rows_work_each, sg_rows_host.h)
   double* crec;          // [SG_CAP][nwb + 1][SG_RF][16]   nwb = ceil(nenv / 8) PGS wavefronts (+1 dummy block)
   unsigned long long* secprof;  // [32] cycle sums per kernel section (only written when built with -DSG_SECTION_PROF)
   double* crow;          // [SG_CAP + 2][nwb + 2][SG_RK / 2][64][2]   row layout (sg_pgs_rows_kernel), +2 dummy blocks
@@ -71,7 +71,7 @@ struct SgPhaseArgs {
   int rowlayout;  // 1: export contact records in the row layout of sg_pgs_rows_kernel
   const int* nbtab;  // SgPlan::nbtab (neighbour rows per element), nullptr when H.nnb == 0
   const int* cpos;   // neighbour-row models: per element, where the four step factors of its equality block sit in a wavefront's round-major
-                     // stream W.cst (doubles: round * 128 + 4 * block slot); the host derives it from SgPlan::sched (sg_api.hip)
+                     // stream W.cst (doubles: round * 128 + 4 * block slot); the host derives it from SgPlan::sched (sg_rows_tables)
   int cst_rounds;    // eq_rounds + 8: rounds of W.cst per solver wavefront; 0: the solver keeps the factors in LDS (SG_ROWS_NB_MODE 1), nothing to write
   const SgGenPair* gpairs;  // SgPlan::gpairs (the general contact path's candidate pairs)
   // copies of the plan header's sizes, by value: the kernels' first addresses then do not wait for a load from *H
@@ -171,7 +171,7 @@ __device__ __forceinline__ int lanes_below2(unsigned long long m) {
 
 
 struct SgPgsArgs {
-  const unsigned* tab;       // the schedule as the solver's LDS table words (lane 2 b + h of a 16-lane group, block slot b; sg_api.hip)
+  const unsigned* tab;       // the schedule as the solver's LDS table words (lane 2 b + h of a 16-lane group, block slot b; sg_rows_tables)
   const SgEqSlot* sched;  // SgPlan::sched (equality-row schedule of neighbour-row models), nullptr when H.nnb == 0
   const int* nbtab;       // SgPlan::nbtab
   const SgPlanHeader* H;

@@ -1,13 +1,13 @@
 // Host check of the solver's look-ahead index rule (soft-grip_amd/csrc/sg_work.h: sg_rows_load_slot), exhaustively over every slot i and
 // stream length nsmax in [0, SG_CAP], the look-ahead distances given on the command line and 4 and 8 envs per wavefront.  The row blocks
-// are a real allocation of the size the library makes ([SG_CAP + 2][nwb + 2] blocks of 8 KB) and every requested row word is READ from
+// are a real allocation of the size the library makes (sg_rows_host.h: [SG_CAP + 2][nwb + 2] blocks of 8 KB) and every requested row word is READ from
 // it at the addresses the kernel forms, so built with the host sanitizers (address, undefined) an index outside it stops the program.
 // tests/test_rows_touch_index.py builds and runs this; it prints one line per (epw, distance) and "PASS".
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
-#include "../../soft-grip_amd/csrc/sg_work.h"
+#include "../../soft-grip_amd/csrc/sg_rows_host.h"
 
 static int fails = 0;
 #define CHECK(c, ...)                                       \
@@ -19,7 +19,14 @@ static int fails = 0;
 
 int main(int argc, char** argv) {
   const int nenv = 9, nwb = (nenv + 7) / 8;
-  std::vector<double> crow((size_t)(SG_CAP + 2) * (nwb + 2) * (SG_RK / 2) * 64 * 2, 1.0);
+  size_t crow_count = 0;   // the size the library makes: sg_rows_work_each (crow's does not depend on the model)
+  SgWork w = {};
+  sg_rows_work_each(w, SgPlanHeader{}, 1, (size_t)nenv, false, [&](auto** p, size_t count) {
+    if ((void*)p == (void*)&w.crow) crow_count = count;
+    return true;
+  });
+  CHECK(crow_count > 0, "crow is not enumerated");
+  std::vector<double> crow(crow_count, 1.0);
   unsigned long long reads = 0;
   double sum = 0;
   for (int a = 1; a < argc; a++) {

@@ -1,5 +1,6 @@
 """Life cycle of a batch's device memory through the C ABI: a creation that cannot be granted fails cleanly, create / use everything /
-destroy repeats bit for bit, and the read-outs' env lists grow and are reused without changing a row."""
+destroy repeats bit for bit, a pipeline's buffers allocated late compute what those allocated at creation do, and the read-outs' env
+lists grow and are reused without changing a row."""
 import math
 
 import numpy as np
@@ -32,11 +33,13 @@ def _run(b, nsteps, out, tag):
         out.update({"%s%d_%s" % (tag, t, k): v.cpu().numpy().copy() for k, v in (("sens", sens), ("flags", flags), ("touch", touch))})
 
 
-def _start(nm, ks, jids, tids):
-    """a fresh batch after set_stiffness, reset and 3 steps -> (batch, what it computed on the way)"""
+def _start(nm, ks, jids, tids, prepare=None):
+    """a fresh batch (after prepare(batch), if given) through set_stiffness, reset and 3 steps -> (batch, what it computed on the way)"""
     import torch
     from softgrip_amd import native
     b = native.NativeBatch(nm, len(ks), 0)
+    if prepare:
+        prepare(b)
     b.set_stiffness(np.asarray(ks, dtype=np.float64), jids, tids)
     sens = torch.zeros(len(ks), nm.nsensordata, dtype=torch.float64, device=b.device)
     b.reset(1, sens=sens)
@@ -94,6 +97,45 @@ def test_create_use_everything_destroy_repeats_bit_for_bit(scene, damper, n, jid
             assert np.abs(out["step2_sens"]).max() > 0 and (out["contacts_ncon"] >= 0).all() and (out["render_seg"] >= 0).any()
         else:
             _assert_same(out, first, "cycle %d" % (cycle + 1))
+
+
+def _everything(b, out, tag):
+    out.update({"%s_%s" % (tag, k): v for k, v in _host(b.solver_stats()).items()})
+    out.update({"%s_state_%s" % (tag, k): v for k, v in _host(b.get_state()).items()})
+    out[tag + "_touch_words"] = b.touch_words().cpu().numpy().copy()
+
+
+@pytest.mark.parametrize("scene", ["softbox_fix", "softbox"])
+def test_rows_pipeline_allocated_late_gives_the_same_bits(scene, monkeypatch):
+    """a batch that starts on the tree pipeline holds no rows work space (rows_alloc); switched to the rows pipeline it allocates it then
+    and computes what a batch created on the rows pipeline does.  9 envs: two 8-env row blocks, three 4-env solver wavefronts, the last ragged"""
+    nm = _model(scene)
+    ks = np.linspace(400, 1300, 9)
+    monkeypatch.delenv("SG_PIPELINE", raising=False)
+    x, want = _start(nm, ks, JOINT_IDS, TENDON_IDS)
+    assert x.tree_workgroups_per_cu() == 0      # (created plainly: on the rows pipeline, nothing of the tree pipeline allocated)
+    monkeypatch.setenv("SG_PIPELINE", "tree")
+    started_on_tree = []
+
+    def to_rows(b):
+        started_on_tree.append(b.tree_workgroups_per_cu() > 0)
+        b.set_pipeline("rows")
+
+    y, got = _start(nm, ks, JOINT_IDS, TENDON_IDS, prepare=to_rows)
+    monkeypatch.delenv("SG_PIPELINE")
+    if not started_on_tree[0]:
+        assert scene == "softbox"
+        pytest.skip("the model has no tree plan: SG_PIPELINE=tree does not apply to it")
+    _everything(x, want, "rows")
+    _everything(y, got, "rows")
+    _assert_same(got, want, "rows pipeline allocated by sg_set_pipeline")
+    assert int(np.abs(want["step2_flags"]).sum()) == 0 and np.abs(want["step2_sens"]).max() > 0 and want["rows_iters"].max() > 0
+    for b, out in ((x, want), (y, got)):
+        b.set_pipeline("tree")
+        _run(b, 2, out, "tree")
+        _everything(b, out, "tree")
+    _assert_same(got, want, "back on the tree pipeline")
+    assert np.abs(want["tree1_sens"]).max() > 0
 
 
 @pytest.mark.parametrize("readout", ["poses", "contacts", "render"])
