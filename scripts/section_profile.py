@@ -19,7 +19,7 @@ from softgrip_amd.create_dataset import episode_schedule  # noqa: E402
 NAMES = ["0 prologue/load", "1 FINISH", "2 BEGIN elements", "3 narrowphase", "4 envelope checks", "5 contact export (stores)",
          "6 eq rows+recompute_a", "7 warmstart test", "8 export rest", "9 store state"]
 PGS_NAMES = {10: "loop head / imp reduction", 11: "joint-fix rows", 12: "tendon row + write-back", 13: "limit rows", 14: "contact rows",
-             15: "exit", 16: "final M^-1 J' f + export"}
+             15: "exit", 16: "final M^-1 J' f + export", 25: "prologue (pending words, staging loads, table)"}
 CHAIN_NAMES = {17: "load state", 18: "FINISH", 19: "kinematics", 20: "dynamics (M, M^-1, bias, tendon)", 21: "hand-off stores, boxes",
                22: "limit rows", 23: "store state"}
 
@@ -59,7 +59,7 @@ def main():
             nwave = n // epw
             w = np.array(buf[:32], dtype=np.float64) / (nwave * 7)  # 7 PGS launches per sg_step call
             tot = sum(w[k] for k in PGS_NAMES)
-            print("   sg_pgs_rows_kernel: %.0f cycles per wavefront and launch (after the prologue)" % tot)
+            print("   sg_pgs_rows_kernel: %.0f cycles per wavefront and launch (from the kernel's entry: section 25 is the prologue)" % tot)
             print("   contact passes per wavefront and launch: %.1f, contact slots swept: %.0f" % (w[29], w[28]))
             if buf[26]:  # counting build (build_native.py --count): the cycle figures of such a run are not timings
                 print("   contact updates per stream and launch: %.0f, of which outside the friction cone (Newton / QCQP path): %.0f" % (

@@ -812,11 +812,15 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
       // row id (6 KB for the ball): without it the kernel's LDS block is 23 KB instead of 29 (ball) / 20 instead of 25 (cylinder):
       // 7 / 8 workgroups per CU instead of 5 / 6, the 4096 wavefronts in 2.3 / 2 rounds instead of 3.2 / 2.7
       [[maybe_unused]] double nbff[R][3];
+      // the rows' right-hand sides: what their exported state g = b + R f falls back to when the warm start loses (f = 0).  In registers: 6 more VGPRs
+      // per element round -- the four-round instantiation, full before, now takes 148 bytes of scratch per lane instead of 28 (keeping b in the
+      // work space instead made ROCm 7.2.0's register allocator crash on that instantiation under the iterative-ilp scheduler)
+      [[maybe_unused]] double nbbb[R][3];
       [[maybe_unused]] double* const gnbf = W.nbf + (size_t)env * 3 * N;
 #pragma unroll
       for (int r = 0; r < R; r++)
 #pragma unroll
-        for (int d = 0; d < 3; d++) { nbe2[r][d] = -1; nbid[r][d] = -1; nbc0[r][d] = 0; nbff[r][d] = 0; }
+        for (int d = 0; d < 3; d++) { nbe2[r][d] = -1; nbid[r][d] = -1; nbc0[r][d] = 0; nbff[r][d] = 0; nbbb[r][d] = 0; }
       if constexpr (NB) {
         // The solver's step factors c = (1/m) / (A + R) of the block [fix_e, e's neighbour rows] (A = 1/m for the fix row, 2/m for a
         // neighbour row: equal masses, sg_plan_build) go out in the SOLVER's order: four consecutive doubles at the place of the
@@ -825,13 +829,17 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
         // cylinder (218 / 192 elements).  Rows that do not exist hold 0: their update is a no-op.
         const double im0 = 1.0 / (EL(SGE_MASS, 0) + EL(SGE_ARMATURE, 0));
         const SG_CONSTAS int* const cposc = (const SG_CONSTAS int*)a.cpos;
-        const bool wantc = a.rowlayout && a.cst_rounds;   // (uniform; a model whose solver keeps the factors in LDS computes them there)
+        // Rows pipeline: the rows leave READY for the solver, which then stages them without a look-up, a product or a division -- per row its
+        // state g = b + R f of the warm-start force (one fma, as the solver contracted it) and its step factor c, element-major and dense
+        // (sg_eq_fix_index, sg_eq_nb_index): the neighbour rows' here, where R is at hand, the fix row's with the export below.  c goes to
+        // the solver's stream (W.cst) where it streams them, else beside g (nbR; the fix row's: eqR); a row that does not exist holds 0 in both.
+        const bool ready = a.rowlayout != 0, wantc = ready && a.cst_rounds;   // (uniform)
 #pragma unroll
         for (int r = 0; r < R; r++) {
           const int e = r * 64 + lane;
           if (e < N) {
-            double c4[4] = {0.0, 0.0, 0.0, 0.0};
-            if (wantc) c4[0] = sg_div(im0, im0 + eqR[r]);
+            double c4[4] = {0.0, 0.0, 0.0, 0.0}, g3[3] = {0.0, 0.0, 0.0};
+            if (ready) c4[0] = sg_div(im0, im0 + eqR[r]);
 #pragma unroll
             for (int d = 0; d < 3; d++) {
               const int e2 = nbtabc[d * N + e];
@@ -843,8 +851,19 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
                 const double bb = (asme[r] - Sm.asme[e2]) - aref, ff = -((we[r] - Sm.we[e2]) - aref) / Rr;
                 nbe2[r][d] = e2; nbid[r][d] = id; nbc0[r][d] = ff * (0.5 * Rr * ff + bb);
                 nbff[r][d] = ff; gnbf[id] = ff;
-                W.nbb[(size_t)env * 3 * N + id] = bb; W.nbR[(size_t)env * 3 * N + id] = Rr;
-                if (wantc) c4[1 + d] = sg_div(im0, 2.0 * im0 + Rr);
+                nbbb[r][d] = bb;
+                if (ready) { g3[d] = fma(Rr, ff, bb); c4[1 + d] = sg_div(im0, 2.0 * im0 + Rr); }
+                else { W.nbb[(size_t)env * 3 * N + id] = bb; W.nbR[(size_t)env * 3 * N + id] = Rr; }
+              }
+            }
+            if (ready) {
+              const size_t o3 = sg_eq_nb_index((size_t)env, e, 0, N);
+#pragma unroll
+              for (int d = 0; d < 3; d++) W.nbb[o3 + d] = g3[d];
+              if (!wantc) {
+                W.eqR[sg_eq_fix_index((size_t)env, e, N)] = c4[0];
+#pragma unroll
+                for (int d = 0; d < 3; d++) W.nbR[o3 + d] = c4[1 + d];
               }
             }
             if (wantc) {
@@ -978,7 +997,11 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
           for (int r = 0; r < R; r++) {
             eqf[r] = 0;
 #pragma unroll
-            for (int d = 0; d < ND; d++) if (nbid[r][d] >= 0) { nbff[r][d] = 0.0; gnbf[nbid[r][d]] = 0.0; }
+            for (int d = 0; d < ND; d++)
+              if (nbid[r][d] >= 0) {
+                nbff[r][d] = 0.0; gnbf[nbid[r][d]] = 0.0;
+                if (a.rowlayout) W.nbb[sg_eq_nb_index((size_t)env, r * 64 + lane, d, N)] = nbbb[r][d];   // g of f = 0 is b itself
+              }
           }
           tf = 0;
           if (is_chain_lane) {
@@ -1016,8 +1039,13 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
         int e = r * 64 + lane;
         if (e < N) {
           size_t o = (size_t)env * N + e;
-          W.as[o] = Sm.as[e]; W.eqf[o] = eqf[r]; W.eqb[o] = eqb[r]; W.eqR[o] = eqR[r];
-          // (W.nbf holds the neighbour rows' forces already: written where they were built, zeroed with the rest when the warmstart lost)
+          W.as[o] = Sm.as[e];
+          // neighbour-row models on the rows pipeline: the fix row's state g0 = b + R f of the final force (the solver's own product, one fma;
+          // f = 0 where the warm start lost: b exactly); its step factor went out with the neighbour rows', and the solver reads no eqf
+          if (NB && a.rowlayout) W.eqb[o] = fma(eqR[r], eqf[r], eqb[r]);
+          else { W.eqf[o] = eqf[r]; W.eqb[o] = eqb[r]; W.eqR[o] = eqR[r]; }
+          // (W.nbf holds the neighbour rows' forces already: written where they were built, zeroed with the rest when the warmstart lost;
+          //  their exported states likewise)
         }
       }
       if (is_chain_lane) {

@@ -54,6 +54,7 @@ __device__ __forceinline__ double sg_gsum16(double x) {
 template <int NSL, int NB, int EPW>  // NSL >= ceil(nelem / 8): joint-fix rows per lane, unrolled and padded (straight-line code, LDS reads issue back to back)
 __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
   extern __shared__ double lds[];
+  SG_T0();
   // an env's lane group: 8 lanes (fix-only models: two finger quads); 16 lanes for neighbour-row models (EPW = 4): the two finger
   // quads (g < 8) plus two more quads that only work in the equality block (one block of rows per quad and round)
   static_assert(!NB || EPW == 4, "neighbour-row models: four envs of 16 lanes per wavefront");
@@ -72,16 +73,23 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
   const double mur = r == 1 ? mu0 : mu1;
   const double rsel0 = r == 0 ? 1.0 : 0.0, rsel1 = r == 1 ? 1.0 : 0.0, rsel2 = r == 2 ? 1.0 : 0.0;
   const int max_iter = H.iterations;
-  // which of the wavefront's envs have a substep pending: read ONCE, all EPW words together (uniform addresses: scalar loads).  The staging
-  // loops and the epilogue used to re-read the word per env behind a branch -- EPW dependent memory round trips in a row, twice per launch
+  // which of the wavefront's envs have a substep pending: read ONCE, all EPW words together (uniform addresses: scalar loads; the env index
+  // is clamped and nothing short-circuits, so the four loads go out in one go and one wait covers them).  The staging loops and the
+  // epilogue used to re-read the word per env behind a branch -- EPW dependent memory round trips in a row, twice per launch
   unsigned pendmask = 0;
+  {
+    int pw[EPW];
 #pragma unroll
-  for (int e2 = 0; e2 < EPW; e2++) {
-    const int env2 = blockIdx.x * EPW + e2;
-    pendmask |= (env2 < a.nenv && W.pending[env2 < a.nenv ? env2 : 0] != 0) ? 1u << e2 : 0u;
+    for (int e2 = 0; e2 < EPW; e2++) {
+      const int env2 = blockIdx.x * EPW + e2;
+      pw[e2] = W.pending[env2 < a.nenv ? env2 : a.nenv - 1];
+    }
+#pragma unroll
+    for (int e2 = 0; e2 < EPW; e2++) pendmask |= ((int)(blockIdx.x * EPW + e2 < a.nenv) & (int)(pw[e2] != 0)) ? 1u << e2 : 0u;
   }
   const bool valid = in_wave && ((pendmask >> lec) & 1u) != 0;
-  if (pendmask == 0) return;
+  if constexpr (!NB)
+    if (pendmask == 0) return;   // (neighbour-row models: see the end of their prologue)
   // LDS: joint-fix rows padded to NR = 8 * NSL per env (padding rows are neutral: b = 0, R = 1, 1/(A+R) = 0, so their update
   // is a no-op and the row loop needs no bound test).  Per env: AF[j] = (a_s, f) [the only pair written], BR[j] = (b, R),
   // RI[j] = 1 / (A_jj + R_j); shared by the wavefront's envs: IC[j] = (1/m, tendon coefficient).  A row is three 16-byte reads + one 8-byte.
@@ -124,11 +132,11 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
   // of a contact-free substep).
   // (unrolled over the envs: their loads are independent and go out together -- the prologue is a chain of memory round trips, ~1.5 us
   // each, and used to take ~35 us of a 160 us contact-free launch)
+  if constexpr (!NB) {
 #pragma unroll
-  for (int e2 = 0; e2 < EPW; e2++) {
-    const int env2 = blockIdx.x * EPW + e2;
-    const bool v2 = ((pendmask >> e2) & 1u) != 0;  // uniform
-    if constexpr (!NB) {
+    for (int e2 = 0; e2 < EPW; e2++) {
+      const int env2 = blockIdx.x * EPW + e2;
+      const bool v2 = ((pendmask >> e2) & 1u) != 0;  // uniform
       double2* const AF2 = (double2*)lds + (size_t)e2 * NR;
       double2* const BR2 = (double2*)lds + (size_t)EPW * NR + (size_t)e2 * NR;
       double* const RI2 = lds + (size_t)4 * EPW * NR + (size_t)e2 * NR;
@@ -145,73 +153,26 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
         }
         if (j < NR) { AF2[j] = af; BR2[j] = br; RI2[j] = ri; }
       }
-    } else {
-      double* const A2 = lds + (size_t)e2 * NAr;
-      double ssum = 0.0;
-#pragma unroll
-      for (int j0 = 0; j0 < NA; j0 += 64) {
-        const int j = j0 + lane;
-        const double av = (v2 && j < N) ? W.as[(size_t)env2 * N + j] : 0.0;
-        if (j < NAr) A2[j] = av;
-        ssum += av;
-      }
-      ssum = wave_sum2(ssum);
-      if (lane == 0) { Lenv[e2] = ssum; Lenv[EPW + e2] = 0.0; }
     }
   }
-  if constexpr (NB) {
-    // row states of all the wavefront's envs, lane = row: the loads of a row (one table word, three values per env) are
-    // independent of each other and of the other rows' -- they are issued together, not one memory round trip after the other
-    [[maybe_unused]] const double im0s = 1.0 / (a.elem[(size_t)SGE_MASS * N] + a.elem[(size_t)SGE_ARMATURE * N]);
-    constexpr int REC_TRIPS = (4 * (NR + 1) + 63) / 64;   // NR >= N
-#pragma unroll 4
-    for (int t = 0; t < REC_TRIPS; t++) {  // row u = 4 e + d: d = 0 the fix row of e, d = 1 .. 3 its neighbour row in workspace slot (d - 1) N + e
-      const int u = lane + 64 * t;
-      if (u >= 4 * (N + 1)) continue;
-      const int e = u >> 2, d = u & 3, ec = e < N ? e : 0;
-      const bool fix = d == 0;
-      const int tabw = a.nbtab[(fix ? 0 : d - 1) * N + ec];   // loaded beside the rows, not in front of them
-      const bool have = e < N && (fix || tabw >= 0);
-      double bb[EPW], Rr[EPW], ff[EPW];
-#pragma unroll
-      for (int e2 = 0; e2 < EPW; e2++) {
-        const int env2 = blockIdx.x * EPW + e2, envc = env2 < a.nenv ? env2 : 0;
-        const size_t o = fix ? (size_t)envc * N + ec : (size_t)envc * 3 * N + (size_t)(d - 1) * N + ec;
-        bb[e2] = (fix ? W.eqb : W.nbb)[o]; Rr[e2] = (fix ? W.eqR : W.nbR)[o]; ff[e2] = (fix ? W.eqf : W.nbf)[o];
-      }
-#pragma unroll
-      for (int e2 = 0; e2 < EPW; e2++) {
-        const int env2 = blockIdx.x * EPW + e2;
-        const bool v2 = ((pendmask >> e2) & 1u) != 0;  // uniform
-        double* const GS2 = lds + (size_t)EPW * NAr + (size_t)e2 * GW;   // group e = rows 4 e .. 4 e + 3
-        const double gg = (v2 && have) ? bb[e2] + Rr[e2] * ff[e2] : 0.0;
-        if constexpr (CST) GS2[u] = gg;
-        else ((double2*)GS2)[u] = make_double2(gg, (v2 && have) ? sg_div(im0s, (fix ? im0s : 2.0 * im0s) + Rr[e2]) : 0.0);
-      }
-    }
-  }
-  if constexpr (NB) {  // the schedule (plus eight idle rounds: padding to a multiple of four and the look-ahead) as LDS offsets: lane 2 b + h of a group, block slot b
-    const int ntab = 16 * TABW * (H.eq_rounds + 8);   // a.tab: the same words, laid out by the host once per batch (sg_rows_host.h)
-#pragma unroll 4
-    for (int i = lane; i < ntab; i += 64) TAB[i] = a.tab[i];
-  }
+  // What a finger stream and an env bring along.  Neighbour-row models: loaded by EVERY lane from a clamped index -- no predicate, so no branch
+  // and no basic block of its own per load -- and selected afterwards: lanes without a pending env (valid) or outside the finger quads (sv) get
+  // the neutral values.  Fix-only models: loaded behind those two predicates, as ever.
   const bool sv = valid && g < 8;  // lanes of the env's two finger quads
-  const size_t st = 2 * (size_t)(sv ? env : 0) + (sv ? c : 0);
-  int ns = 0, lim_active = 0, shared = 0;
+  const int envl = env < a.nenv ? env : a.nenv - 1;
+  const size_t st = 2 * (size_t)envl + (c & 1);
+  int ns, lim_active, shared, ngen;  // ngen: contacts of an env on the general contact path (sg_general.h); 0 on the fast path
   // lane r of the quad owns finger acceleration aF[r]; of M^-1 it needs row r (its share of a limit row's push) and the diagonal
-  double Mrow[SG_CD] = {0, 0, 0, 0}, Mdiag[SG_CD] = {0, 0, 0, 0}, aFo = 0;
-  double tb = 0, tR = 1, tA = 1, tf = 0;
+  double Mrow[SG_CD], Mdiag[SG_CD], aFo;
+  double tb, tR, tA, tf;
   double lsign[SG_MAXLIM], lR[SG_MAXLIM], lb[SG_MAXLIM], lf[SG_MAXLIM];
-#pragma unroll
-  for (int k = 0; k < SG_MAXLIM; k++) { lsign[k] = 0; lR[k] = 1; lb[k] = 0; lf[k] = 0; }
-  if (valid) {
-    tb = W.envh[(size_t)0 * a.nenv + env]; tR = W.envh[(size_t)1 * a.nenv + env];
-    tA = W.envh[(size_t)2 * a.nenv + env]; tf = W.envh[(size_t)3 * a.nenv + env];
-    shared = W.shared[env];
-  }
-  const int ngen = valid ? W.gen[env] : 0;  // contacts of an env on the general contact path (sg_general.h); 0 on the fast path
-  const bool wave_gen = __ballot(ngen > 0) != 0;
-  if (sv) {
+  auto env_loads = [&]() {
+    tb = W.envh[(size_t)0 * a.nenv + envl]; tR = W.envh[(size_t)1 * a.nenv + envl];
+    tA = W.envh[(size_t)2 * a.nenv + envl]; tf = W.envh[(size_t)3 * a.nenv + envl];
+    shared = W.shared[envl];
+    ngen = W.gen[envl];
+  };
+  auto quad_loads = [&]() {
     ns = W.ns[st];
     lim_active = W.lim_active[st];
 #pragma unroll
@@ -222,7 +183,116 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
       lsign[k] = W.lim[((size_t)0 * SG_MAXLIM + k) * S + st]; lR[k] = W.lim[((size_t)1 * SG_MAXLIM + k) * S + st];
       lb[k] = W.lim[((size_t)2 * SG_MAXLIM + k) * S + st]; lf[k] = W.lim[((size_t)3 * SG_MAXLIM + k) * S + st];
     }
+  };
+  // the neutral values by selects, behind unconditional loads: ve the lane's env is pending, vq ... and the lane in a finger quad.  (Not the two
+  // assignment lambdas below under `if (!valid)` / `if (!sv)`: with those the register allocator moved a loaded value in the middle of the batch
+  // and waited for it there, `s_waitcnt vmcnt(0)` in front of the per-stream loads.)
+  auto neutral_unless = [&](const bool ve, const bool vq) {
+    tb = ve ? tb : 0.0; tR = ve ? tR : 1.0; tA = ve ? tA : 1.0; tf = ve ? tf : 0.0;
+    shared = ve ? shared : 0; ngen = ve ? ngen : 0;
+    ns = vq ? ns : 0; lim_active = vq ? lim_active : 0;
+#pragma unroll
+    for (int d = 0; d < SG_CD; d++) { Mrow[d] = vq ? Mrow[d] : 0.0; Mdiag[d] = vq ? Mdiag[d] : 0.0; }
+    aFo = vq ? aFo : 0.0;
+#pragma unroll
+    for (int k = 0; k < SG_MAXLIM; k++) { lsign[k] = vq ? lsign[k] : 0.0; lR[k] = vq ? lR[k] : 1.0; lb[k] = vq ? lb[k] : 0.0; lf[k] = vq ? lf[k] : 0.0; }
+  };
+  auto env_neutral = [&]() { tb = 0; tR = 1; tA = 1; tf = 0; shared = 0; ngen = 0; };   // a lane without a pending env
+  auto quad_neutral = [&]() {                                                            // a lane outside the finger quads of a pending env
+    ns = 0; lim_active = 0; aFo = 0;
+#pragma unroll
+    for (int d = 0; d < SG_CD; d++) { Mrow[d] = 0; Mdiag[d] = 0; }
+#pragma unroll
+    for (int k = 0; k < SG_MAXLIM; k++) { lsign[k] = 0; lR[k] = 1; lb[k] = 0; lf[k] = 0; }
+  };
+  if constexpr (NB) {
+    // The prologue of a neighbour-row model is ONE batch of loads: slider words, row records, table words and the per-stream values above are
+    // all requested before the first of them is waited for.  Nothing here is conditional: env slots past the batch and lanes past the data
+    // read a clamped address (sg_eq_rec_index) and their value is dropped; envs without a pending substep are staged like the others -- their
+    // lanes never run, the pending mask gates `running` and the epilogue only.  The rows arrive ready from the phase kernel (SgWork::eqb / eqR /
+    // nbb / nbR: the state g = b + R f and, NB = 1, the step factor c), lane = row u = 4 e + d over REC_TRIPS trips: no look-up by row id, no
+    // division.  (Until r07 every load sat behind a predicate in a block of its own, ~34 dependent round trips per launch.)
+    constexpr int ATRIPS = (NA + 63) / 64, REC_TRIPS = sg_eq_rec_trips(NR);   // NR >= N
+    constexpr int TAB_BATCH = 4;   // 16-byte table words per lane that join the batch (64 rounds of one-word lanes, 32 of two-word ones); a longer schedule's rest follows in a loop
+    const int ntab4 = 4 * TABW * (H.eq_rounds + 8);   // a.tab in 16-byte words: the schedule (plus eight idle rounds: padding to a multiple of four and the look-ahead)
+                                                      // as LDS offsets, lane 2 b + h of a group, block slot b; laid out by the host once per batch (sg_rows_host.h)
+    double av[EPW][ATRIPS], gv[EPW][REC_TRIPS];
+    [[maybe_unused]] double cv[EPW][REC_TRIPS];
+    uint4 tw[TAB_BATCH];
+#pragma unroll
+    for (int e2 = 0; e2 < EPW; e2++) {
+      const int env2 = blockIdx.x * EPW + e2;
+      const double* const as2 = W.as + (size_t)(env2 < a.nenv ? env2 : a.nenv - 1) * N;
+#pragma unroll
+      for (int k = 0; k < ATRIPS; k++) { const int j = 64 * k + lane; av[e2][k] = as2[j < N ? j : N - 1]; }
+    }
+#pragma unroll
+    for (int t = 0; t < REC_TRIPS; t++) {
+      const int u = sg_eq_rec_row(lane, t);
+      const bool fix = ((u < 4 * N ? u : 4 * N - 1) & 3) == 0;   // (the clamped row 4 N - 1 is a neighbour row)
+#pragma unroll
+      for (int e2 = 0; e2 < EPW; e2++) {
+        const size_t o = sg_eq_rec_index((size_t)(blockIdx.x * EPW + e2), u, N, (size_t)a.nenv);
+        gv[e2][t] = (fix ? W.eqb : W.nbb)[o];
+        if constexpr (!CST) cv[e2][t] = (fix ? W.eqR : W.nbR)[o];
+      }
+    }
+    env_loads();
+    quad_loads();
+#pragma unroll
+    for (int q = 0; q < TAB_BATCH; q++) { const int i = lane + 64 * q; tw[q] = ((const uint4*)a.tab)[i < ntab4 ? i : ntab4 - 1]; }
+    __builtin_amdgcn_sched_barrier(0);   // ---- everything above is on its way before anything below waits
+    double ssum[EPW];
+#pragma unroll
+    for (int e2 = 0; e2 < EPW; e2++) {
+      double* const A2 = lds + (size_t)e2 * NAr;
+      ssum[e2] = 0.0;
+#pragma unroll
+      for (int k = 0; k < ATRIPS; k++) {
+        const int j = 64 * k + lane;
+        const double v = j < N ? av[e2][k] : 0.0;    // word N ("no partner") and the padding stay zero
+        A2[j < NAr ? j : NAr - 1] = v;               // (lanes past the array write the last padding word's zero again: no predicate)
+        ssum[e2] += v;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {   // wave_sum2 of the four envs side by side: one LDS round trip per step, not four
+      double t_[EPW];
+#pragma unroll
+      for (int e2 = 0; e2 < EPW; e2++) t_[e2] = __shfl_xor(ssum[e2], o);
+#pragma unroll
+      for (int e2 = 0; e2 < EPW; e2++) ssum[e2] += t_[e2];
+    }
+#pragma unroll
+    for (int e2 = 0; e2 < EPW; e2++) {   // (lane 0's to keep; the others' go to their sink words: no branch inside the batch)
+      *(lane == 0 ? &Lenv[e2] : &Lzero[1 + lane]) = ssum[e2];
+      *(lane == 0 ? &Lenv[EPW + e2] : &Lzero[1 + lane]) = 0.0;
+    }
+#pragma unroll
+    for (int t = 0; t < REC_TRIPS; t++) {
+      const int u = sg_eq_rec_row(lane, t);
+      const bool live = sg_eq_rec_live(u, N);   // group N (the idle slots' rows) stays zero
+      const int us = sg_eq_rec_stored(u, N) ? u : 4 * (N + 1) - 1;   // lanes past the records write group N's last zero again: no predicate
+#pragma unroll
+      for (int e2 = 0; e2 < EPW; e2++) {
+        double* const GS2 = lds + (size_t)EPW * NAr + (size_t)e2 * GW;   // group e = rows 4 e .. 4 e + 3
+        if constexpr (CST) GS2[us] = live ? gv[e2][t] : 0.0;
+        else ((double2*)GS2)[us] = make_double2(live ? gv[e2][t] : 0.0, live ? cv[e2][t] : 0.0);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < TAB_BATCH; q++) { const int i = lane + 64 * q; ((uint4*)TAB)[i < ntab4 ? i : ntab4 - 1] = tw[q]; }   // (past the table: its last word again)
+    // (A wavefront none of whose envs has a substep pending is not sent home from here: a return in front of the consumers of a load lets the
+    //  compiler move the load behind it, into a round trip of its own.  Such a wavefront -- there is one after a masked reset at most -- has
+    //  no running lane: it leaves the sweeps at their first test and the epilogue's stores are all gated by the mask.)
+    for (int i = lane + 64 * TAB_BATCH; i < ntab4; i += 64) ((uint4*)TAB)[i] = ((const uint4*)a.tab)[i];
+    neutral_unless(valid, sv);
+  } else {
+    env_neutral(); quad_neutral();
+    if (valid) env_loads();
+    if (sv) quad_loads();
   }
+  const bool wave_gen = __ballot(ngen > 0) != 0;
   __syncthreads();
   int nsmax_v = ns;
 #pragma unroll
@@ -251,7 +321,7 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
   [[maybe_unused]] const double2* const cp0 = (const double2*)(W.cst + SG_CST_INDEX(blockIdx.x, 0, lane, H.eq_rounds + 8));
   [[maybe_unused]] double2 c0, c1, c2, c3;
   if constexpr (CST) { c0 = cp0[0]; c1 = cp0[64]; c2 = cp0[128]; c3 = cp0[192]; }
-  SG_T0();
+  SG_T(25);   // the prologue: everything up to here
   for (int it = 0; it < max_iter; it++) {
     if (!__ballot(running)) break;
     SG_T(10);

@@ -39,10 +39,16 @@ struct SgWork {          // device workspace of one batch (all pointers device m
   double *sMinv, *saF;   // [16][S], [4][S]
   int* lim_active;       // [S]
   double* lim;           // [4][SG_MAXLIM][S]: sign, R, b, f
-  double *as, *eqf, *eqb, *eqR;  // [nenv][N]
+  double *as, *eqf, *eqb, *eqR;  // [nenv][N]  slider accelerations; the fix rows' force, right-hand side b, regulariser R.  Neighbour-row models on the
+                         // rows pipeline (SgPhaseArgs::rowlayout, H.nnb > 0) hand the solver its rows READY instead (sg_eq_fix_index): eqb = the row's
+                         // state g0 = b + R f of the final warm-start force, eqR = its step factor c0 = (1/m) / (1/m + R) -- eqR only where the solver
+                         // keeps the factors in LDS (SG_ROWS_NB_MODE 1; mode 2 streams them from cst and eqR is not written) -- and eqf is not written
   double *asme, *fsm;    // [nenv][N]  begin -> finish hand-off
   double* chh;           // [nenv][2][SG_CHW]  chain hand-off (enum SGH_*)
-  double *nbf, *nbb, *nbR;  // [nenv][3 N]  neighbour equality rows (models with H.nnb > 0) by slot (SgPlan::nbtab): force, right-hand side, regulariser
+  double *nbf, *nbb, *nbR;  // [nenv][3 N]  neighbour equality rows (models with H.nnb > 0) by slot (SgPlan::nbtab): force, right-hand side, regulariser.
+                         // Rows pipeline: nbf as said (the phase kernel gathers from it by row id); nbb and nbR are element-major and dense,
+                         // [nenv][N][3] (sg_eq_nb_index): nbb = g_d = b + R f of element e's d-th neighbour row, nbR = c_d = (1/m) / (2/m + R)
+                         // (mode 1 only, as eqR); a row that does not exist holds 0 in both
   double* cst;           // [ceil(nenv / 4)][eq_rounds + 8][64][2]  step factors c = (1/m) / (A + R) of the equality rows in the SOLVER's order: what lane l of
                          // wavefront w reads in round k of its equality block (SG_CST_INDEX); written by the phase kernel, zero where a slot / row is idle
   double* gcon;          // [nenv][SG_GEN_MAXCON][SG_GEN_W]  contacts of envs on the general contact path (sg_general.h), in mj_collision's order
@@ -95,6 +101,23 @@ struct SgPhaseArgs {
 #define SG_RK 16
 // the solver's stream of step factors (SgWork::cst), in doubles: wavefront w (four envs), round k of its equality block, lane l
 #define SG_CST_INDEX(w, k, l, rounds) ((((size_t)(w) * (rounds) + (k)) * 64 + (l)) * 2)
+// the equality block as the phase kernel exports it to the rows solver (neighbour-row models): element-major and dense, no look-up by row id.
+// Fix row of element e: SgWork::eqb / eqR [nenv][N]; its neighbour row d = 0 .. 2: SgWork::nbb / nbR [nenv][N][3]
+__host__ __device__ constexpr size_t sg_eq_fix_index(size_t env, int e, int N) { return env * (size_t)N + (size_t)e; }
+__host__ __device__ constexpr size_t sg_eq_nb_index(size_t env, int e, int d, int N) { return (env * (size_t)N + (size_t)e) * 3 + (size_t)d; }
+// The solver stages an env's 4 (N + 1) row records in trips of 64 lanes: lane l of trip t holds row u = 4 e + d -- d = 0 the fix row of
+// element e, d = 1 .. 3 its neighbour rows; group e = N is the idle slots' and stays zero, as does the padding behind it
+__host__ __device__ constexpr int sg_eq_rec_trips(int nr) { return (4 * (nr + 1) + 63) / 64; }   // nr >= N: the instantiation's padded row count
+__host__ __device__ constexpr int sg_eq_rec_row(int lane, int trip) { return lane + 64 * trip; }
+__host__ __device__ constexpr bool sg_eq_rec_stored(int u, int N) { return u < 4 * (N + 1); }      // the row has a record in LDS
+__host__ __device__ constexpr bool sg_eq_rec_live(int u, int N) { return u < 4 * N; }              // ... and is read from memory (else it is zero)
+// where row u of an env is read from: the fix rows' array (d = 0) or the neighbour rows' -- clamped, so that every lane of every trip and
+// every env slot of a ragged last wavefront forms an address inside the batch's arrays and the loads need no predicate
+__host__ __device__ constexpr size_t sg_eq_rec_index(size_t env, int u, int N, size_t nenv) {
+  const size_t envc = env < nenv ? env : nenv - 1;
+  const int uc = u < 4 * N ? u : 4 * N - 1, e = uc >> 2, d = uc & 3;
+  return d == 0 ? sg_eq_fix_index(envc, e, N) : sg_eq_nb_index(envc, e, d - 1, N);
+}
 #define SG_ROW_INDEX(slot, wave, k, lane, nwb) \
   ((((((size_t)(slot)) * ((nwb) + 2) + (wave)) * (SG_RK / 2) + (k) / 2) * 64 + (lane)) * 2 + ((k) & 1))
 
