@@ -5,7 +5,7 @@
 //   sg_phase_kernel<R,CPL,NB,GEN>  one WAVEFRONT per env, lane = shell element.  FINISH part: takes the solver's result for the
 //                           previous substep (slider and chain constraint accelerations), produces qacc, the warmstart and
 //                           integrates.  BEGIN part: smooth dynamics, collision, constraint rows, warmstart test, and EXPORTS the
-//                           constraint problem to the work space in the solver's layouts (sg_work.h).
+//                           constraint problem to the work space in the solver's layouts (sg_rows_layout.h).
 //
 // What they replace: mj_step's stages around mj_fwdConstraint for reference environment/manenv.py:48-49.
 #include "sg_work.h"
@@ -335,22 +335,22 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
     double* const kd = (double*)&Sm.K[half];
     double* const box = &Sm.boxp[half * SG_CG][0];
     double* const boxm = &Sm.boxm[half * SG_CG][0];
-    double* const lim = CS.lim_sign;  // lim_sign, lim_R, lim_b, lim_f are contiguous, as SGH_LIMSIGN .. SGH_LIMF are
+    double* const lim = CS.lim_sign;  // lim_sign, lim_R, lim_b, lim_f are contiguous, as SGH_LIMSIGN .. SGH_LIMF are (sg_work.h: asserted)
 #pragma unroll
     for (int j0 = 0; j0 < SG_CHW; j0 += 32) {
       const int j = j0 + (lane & 31);
       const double v = j < SG_CHW ? ch[j] : 0.0;
       if (j >= SGH_QSM && j < SGH_QSM + SG_CD) CS.qacc_smooth[j - SGH_QSM] = v;
-      else if (j >= SGH_K && j < SGH_K + 48) kd[j - SGH_K] = v;
-      else if (j >= SGH_MINV && j < SGH_MINV + 16) CS.Minv[j - SGH_MINV] = v;
+      else if (j >= SGH_K && j < SGH_K + SGH_N_K) kd[j - SGH_K] = v;
+      else if (j >= SGH_MINV && j < SGH_MINV + SGH_N_M) CS.Minv[j - SGH_MINV] = v;
       else if (j >= SGH_V && j < SGH_V + SG_CD) CS.v[j - SGH_V] = v;
       else if (j >= SGH_W && j < SGH_W + SG_CD) CS.w[j - SGH_W] = v;
-      else if (j >= SGH_BOX && j < SGH_BOX + 12 * SG_CG) {
-        const int g = (j - SGH_BOX) / 12, k = (j - SGH_BOX) % 12;
+      else if (j >= SGH_BOX && j < SGH_BOX + SGH_N_BOX) {
+        const int g = (j - SGH_BOX) / SGH_N_BOX1, k = (j - SGH_BOX) % SGH_N_BOX1;
         if (k < 3) box[3 * g + k] = v; else boxm[9 * g + k - 3] = v;
       }
       else if (j == SGH_LIMACT) CS.lim_active = (int)v;
-      else if (j >= SGH_LIMSIGN && j < SGH_LIMSIGN + 4 * SG_MAXLIM) lim[j - SGH_LIMSIGN] = v;
+      else if (j >= SGH_LIMSIGN && j < SGH_LIMSIGN + SGH_N_LIM) lim[j - SGH_LIMSIGN] = v;
     }
   }
   const bool dead = (status & (SG_FLAG_BADQPOS | SG_FLAG_BADQVEL | SG_FLAG_BADQACC)) != 0;
@@ -657,7 +657,7 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
       // ---- contact rows: built one slot at a time and exported at once; only a 7-double summary per slot stays
       //      in registers for the warmstart test (g = Jf' f, Js.f, invm, f.(R f/2 + b), slider index)
       const int myn = high ? ns1 : ns0;
-      const size_t st = 2 * (size_t)env + half;
+      const size_t st = SG_STREAM(env, half);
       const int nwb = (a.nenv + SG_EPW - 1) / SG_EPW;
       double cg[CPL][SG_CD], cjsf[CPL], cinvm[CPL], ccost0[CPL];
       int csl_[CPL];
@@ -723,17 +723,17 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
               for (int q = 0; q < SG_RK; q++) fld[q] = 0.0;
               if (r < 3) {
 #pragma unroll
-                for (int d = 0; d < SG_CD; d++) fld[d] = c.Jf[r][d];
-                fld[4] = c.Js[r]; fld[5] = c.b[r]; fld[6] = c.f[r];
-                fld[7] = Afull[r][0] * c.f[0] + Afull[r][1] * c.f[1] + Afull[r][2] * c.f[2];
-                fld[8] = Afull[r][0]; fld[9] = Afull[r][1]; fld[10] = Afull[r][2];
-                fld[11] = c.invm * c.Js[r];
-                fld[15] = c.R;
+                for (int d = 0; d < SG_CD; d++) fld[SGR_JF0 + d] = c.Jf[r][d];
+                fld[SGR_JS] = c.Js[r]; fld[SGR_B] = c.b[r]; fld[SGR_F] = c.f[r];
+                fld[SGR_AF] = Afull[r][0] * c.f[0] + Afull[r][1] * c.f[1] + Afull[r][2] * c.f[2];
+                fld[SGR_A0] = Afull[r][0]; fld[SGR_A1] = Afull[r][1]; fld[SGR_A2] = Afull[r][2];
+                fld[SGR_IMJS] = c.invm * c.Js[r];
+                fld[SGR_R] = c.R;
               } else {  // the fourth lane carries what the three rows share (R is replicated on the row lanes: no broadcast)
-                fld[0] = P11; fld[1] = P12; fld[2] = P22; fld[4] = __hiloint2double(0, sl);
-                fld[8] = ee1; fld[9] = ee2; fld[10] = ecs; fld[11] = esn;
+                fld[SGQ_P11] = P11; fld[SGQ_P12] = P12; fld[SGQ_P22] = P22; fld[SGQ_SLIDER] = __hiloint2double(0, sl);
+                fld[SGQ_E1] = ee1; fld[SGQ_E2] = ee2; fld[SGQ_COS] = ecs; fld[SGQ_SIN] = esn;
               }
-              fld[12] = Wm[0][r]; fld[13] = Wm[1][r]; fld[14] = Wm[2][r];
+              fld[SGR_W0] = Wm[0][r]; fld[SGR_W1] = Wm[1][r]; fld[SGR_W2] = Wm[2][r];
 #pragma unroll
               for (int pr = 0; pr < SG_RK / 2; pr++) fp[r][pr] = make_double2(fld[2 * pr], fld[2 * pr + 1]);
             }
@@ -1024,7 +1024,7 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
               if (a.rowlayout) {
 #pragma unroll
                 for (int r = 0; r < 3; r++)  // f and A f (one pair)
-                  *(double2*)(W.crow + SG_ROW_INDEX(i, env >> 3, 6, 8 * (env & 7) + 4 * half + r, (a.nenv + 7) / 8)) = make_double2(0.0, 0.0);
+                  *(double2*)(W.crow + SG_ROW_INDEX(i, env >> 3, SGR_F, 8 * (env & 7) + 4 * half + r, (a.nenv + 7) / 8)) = make_double2(0.0, 0.0);
               }
             }
           }
@@ -1053,14 +1053,14 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
         W.lim_active[st] = CS.lim_active;
       }
       if (half < nchain) {  // the 32 lanes of a half write its chain's 4 x SG_MAXLIM limit values (contiguous in CS) and M^-1 J' f
-        static_assert(4 * SG_MAXLIM == 32, "one limit value per lane of a half");
+        static_assert(SGH_N_LIM == 32, "one limit value per lane of a half");
         const int i = lane & 31;
-        W.lim[(size_t)i * S + st] = (&CS.lim_sign[0])[i];
-        if (i < SG_CD) W.saF[(size_t)i * S + st] = i == 0 ? aF[0] : (i == 1 ? aF[1] : (i == 2 ? aF[2] : aF[3]));
+        W.lim[SG_LIM_FLAT_INDEX(i, st, S)] = (&CS.lim_sign[0])[i];
+        if (i < SG_CD) W.saF[SG_SAF_INDEX(i, st, S)] = i == 0 ? aF[0] : (i == 1 ? aF[1] : (i == 2 ? aF[2] : aF[3]));
       }
       if (lane == 0) {
-        W.envh[(size_t)0 * a.nenv + env] = tb; W.envh[(size_t)1 * a.nenv + env] = tR;
-        W.envh[(size_t)2 * a.nenv + env] = tA; W.envh[(size_t)3 * a.nenv + env] = tf;
+        W.envh[SG_ENVH_INDEX(SG_ENVH_TB, env, a.nenv)] = tb; W.envh[SG_ENVH_INDEX(SG_ENVH_TR, env, a.nenv)] = tR;
+        W.envh[SG_ENVH_INDEX(SG_ENVH_TA, env, a.nenv)] = tA; W.envh[SG_ENVH_INDEX(SG_ENVH_TF, env, a.nenv)] = tf;
         W.shared[env] = shared_slider;
         W.pending[env] = 1;
         W.ncon[env] = ns0 + ns1 + ngen;
@@ -1125,7 +1125,7 @@ __global__ __launch_bounds__(64) void sg_chain_kernel(SgPhaseArgs a) {
   const int nv = a.nv, nu = a.nu;
   const size_t S = 2 * (size_t)a.nenv;
   if (env >= a.nenv) return;
-  const size_t st = 2 * (size_t)env + c;
+  const size_t st = SG_STREAM(env, c);
   if (a.mask && !a.mask[env]) return;
   SgWork& W = a.w;
   if (a.first && c == 0) { W.status[env] = 0; if (!a.do_finish) W.pending[env] = 0; }
@@ -1161,7 +1161,7 @@ __global__ __launch_bounds__(64) void sg_chain_kernel(SgPhaseArgs a) {
     double aF[SG_CD], qacc_c[SG_CD];
 #pragma unroll
     for (int d = 0; d < SG_CD; d++) {
-      aF[d] = W.saF[(size_t)d * S + st];
+      aF[d] = W.saF[SG_SAF_INDEX(d, st, S)];
       qacc_c[d] = ch[SGH_QSM + d] + aF[d];
       if (isbad(qacc_c[d])) bad_acc = true;
     }
@@ -1169,7 +1169,7 @@ __global__ __launch_bounds__(64) void sg_chain_kernel(SgPhaseArgs a) {
     {
       double* kd = (double*)&K;
 #pragma unroll
-      for (int i = 0; i < 48; i++) kd[i] = ch[SGH_K + i];
+      for (int i = 0; i < SGH_N_K; i++) kd[i] = ch[SGH_K + i];
     }
     if (a.sens) {
       ChainMotion Mo;
@@ -1208,7 +1208,7 @@ __global__ __launch_bounds__(64) void sg_chain_kernel(SgPhaseArgs a) {
         if (damp) {
           double MhB[16], MhBinv[16], rhs[SG_CD], Mm[16];
 #pragma unroll
-          for (int i = 0; i < 16; i++) { Mm[i] = ch[SGH_M + i]; MhB[i] = Mm[i]; }
+          for (int i = 0; i < SGH_N_M; i++) { Mm[i] = ch[SGH_M + i]; MhB[i] = Mm[i]; }
 #pragma unroll
           for (int d = 0; d < SG_CD; d++) MhB[5 * d] += h * C.damping[d];
           spd_inverse4(MhB, MhBinv);
@@ -1260,11 +1260,11 @@ __global__ __launch_bounds__(64) void sg_chain_kernel(SgPhaseArgs a) {
       for (int d = 0; d < SG_CD; d++) { rec[SGH_QSM + d] = D.qacc_smooth[d]; rec[SGH_QFRC + d] = D.qfrc_smooth[d]; rec[SGH_V + d] = v[d]; rec[SGH_W + d] = w[d]; }
       rec[SGH_ACTDOT] = D.act_dot;
 #pragma unroll
-      for (int i = 0; i < 16; i++) { rec[SGH_M + i] = D.M[i]; rec[SGH_MINV + i] = D.Minv[i]; W.sMinv[(size_t)i * S + st] = D.Minv[i]; }
+      for (int i = 0; i < SGH_N_M; i++) { rec[SGH_M + i] = D.M[i]; rec[SGH_MINV + i] = D.Minv[i]; W.sMinv[SG_MINV_INDEX(i, st, S)] = D.Minv[i]; }
       {
         const double* kd = (const double*)&K;
 #pragma unroll
-        for (int i = 0; i < 48; i++) rec[SGH_K + i] = kd[i];
+        for (int i = 0; i < SGH_N_K; i++) rec[SGH_K + i] = kd[i];
       }
 #pragma unroll
       for (int g = 0; g < SG_CG; g++) {
@@ -1277,9 +1277,9 @@ __global__ __launch_bounds__(64) void sg_chain_kernel(SgPhaseArgs a) {
           mulmat33(bm2, bm_, C.g_mat[g]);
         }
 #pragma unroll
-        for (int k = 0; k < 3; k++) rec[SGH_BOX + 12 * g + k] = bp_[k] + t[k];
+        for (int k = 0; k < 3; k++) rec[SGH_BOX + SGH_N_BOX1 * g + k] = bp_[k] + t[k];
 #pragma unroll
-        for (int k = 0; k < 9; k++) rec[SGH_BOX + 12 * g + 3 + k] = bm2[k];
+        for (int k = 0; k < 9; k++) rec[SGH_BOX + SGH_N_BOX1 * g + 3 + k] = bm2[k];
       }
       SG_T(21);
       LimitRows L;
@@ -1287,9 +1287,8 @@ __global__ __launch_bounds__(64) void sg_chain_kernel(SgPhaseArgs a) {
       rec[SGH_LIMACT] = (double)L.active;
 #pragma unroll
       for (int k = 0; k < SG_MAXLIM; k++) { rec[SGH_LIMSIGN + k] = L.sign[k]; rec[SGH_LIMR + k] = L.R[k]; rec[SGH_LIMB + k] = L.b[k]; rec[SGH_LIMF + k] = L.f[k]; }
-      static_assert(SG_CHW % 2 == 0 && SGH_LIMF + SG_MAXLIM <= SG_CHW, "hand-off record layout");
 #pragma unroll
-      for (int i = 0; i < (SGH_LIMF + SG_MAXLIM + 1) / 2; i++) ((double2*)ch)[i] = make_double2(rec[2 * i], rec[2 * i + 1]);
+      for (int i = 0; i < (SGH_END + 1) / 2; i++) ((double2*)ch)[i] = make_double2(rec[2 * i], rec[2 * i + 1]);
     }
   }
   SG_T(22);

@@ -90,36 +90,30 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
   const bool valid = in_wave && ((pendmask >> lec) & 1u) != 0;
   if constexpr (!NB)
     if (pendmask == 0) return;   // (neighbour-row models: see the end of their prologue)
-  // LDS: joint-fix rows padded to NR = 8 * NSL per env (padding rows are neutral: b = 0, R = 1, 1/(A+R) = 0, so their update
-  // is a no-op and the row loop needs no bound test).  Per env: AF[j] = (a_s, f) [the only pair written], BR[j] = (b, R),
-  // RI[j] = 1 / (A_jj + R_j); shared by the wavefront's envs: IC[j] = (1/m, tendon coefficient).  A row is three 16-byte reads + one 8-byte.
+  // The LDS block's regions and what they hold: sg_rows_layout.h (SG_LDS_FIX_*, SG_LDS_NB_*; the first region, AF | AE, starts the block).  Fix-only models: the joint-fix rows are padded to
+  // NR = 8 * NSL per env with neutral rows, so their update is a no-op and the row loop needs no bound test; a row is three 16-byte reads
+  // (AF, BR, IC) + one 8-byte (RI).
   constexpr int NR = 8 * NSL;
-  // NB layout: Ae[NA] slider accelerations per env (word N is a dummy that stays 0: "no second slider"), IC[NA] shared,
   constexpr int NA = NR + 8;     // (static bound of the staging loops)
   const int NAr = SG_ROWS_NA_NB(N);  // words of an env's slider array: N sliders, the zero word, padding to a 16-byte multiple
-  const int GW = (CST ? 4 : 8) * (N + 1);    // doubles of an env's row records: (N + 1) groups of four states g -- or four pairs (g, c)
+  const int GW = SG_ROWS_GW_NB(N, CST);       // doubles of an env's row records: (N + 1) groups of four states g -- or four pairs (g, c)
+  double *const rBR = SG_LDS_FIX_BR(lds, EPW, NR), *const rRI = SG_LDS_FIX_RI(rBR, EPW, NR), *const rIC = SG_LDS_FIX_IC(rRI, EPW, NR);   // the regions' starts
   double2* const AF = (double2*)lds + (size_t)lec * NR;
-  double2* const BR = (double2*)lds + (size_t)EPW * NR + (size_t)lec * NR;
-  double* const RI = lds + (size_t)4 * EPW * NR + (size_t)lec * NR;
-  double2* const IC = (double2*)(lds + (size_t)5 * EPW * NR);  // fix-only models: (1/m, tendon coefficient) per element
-  // NB layout: Ae[NAr] per env: slider accelerations MINUS the env's offset aoff (below); word N is a zero word ("no partner").
-  // GS per env: group e = the states g = b + R f of the four rows of element e's block -- its fix row, then its up to three
-  // neighbour rows; rows that do not exist and group N (idle slots) hold 0 (their step factor in W.cst is 0 too); NB = 1: pairs (g, c)
-  // with c = (1/m) / (A + R) in the same order.  TAB (shared by the
-  // wavefront's envs): the plan's block schedule as LDS offsets per lane of a 16-lane group: lane 2 b + h holds, for the block e
-  // in slot b of the round, x | y << 11 | (2 e + h) << 22 with the sliders' byte offsets (x, y) = 8 (e, p0) for h = 0 and 8 (p1, p2)
-  // for h = 1, and 2 e + h the lane's pair of row states in 16-byte units (NB = 2; NB = 1: two words, x | y << 16 and the byte offset of
-  // the lane's pair of 32-byte records -- TABW below).
+  double2* const BR = (double2*)rBR + (size_t)lec * NR;
+  double* const RI = rRI + (size_t)lec * NR;
+  double2* const IC = (double2*)rIC;
+  // Neighbour-row models: Ae holds the slider accelerations MINUS the env's offset aoff (below).  GS: group e = the states g = b + R f of the
+  // four rows of element e's block -- its fix row, then its up to three neighbour rows; rows that do not exist and group N (idle slots) hold
+  // 0 (their step factor in W.cst is 0 too); NB = 1: pairs (g, c) with c = (1/m) / (A + R) in the same order.  TAB (shared by the
+  // wavefront's envs): the plan's block schedule as table words (sg_tab1_* | sg_tab2_*), TABW per lane of a 16-lane group and round.
+  double *const rGS = SG_LDS_NB_GS(lds, EPW, N), *const rTAB = SG_LDS_NB_TAB(rGS, EPW, N, CST);
   double* const Ae = lds + (size_t)lec * NAr;
-  double* const GS = lds + (size_t)EPW * NAr + (size_t)lec * GW;
-  unsigned* const TAB = (unsigned*)(lds + (size_t)EPW * NAr + (size_t)EPW * GW);
-  // (NB = 1, the box scene: TWO words per lane and round, (x | y << 16, record offset) -- halves and a plain word decode inside the address
-  //  additions; the packed word costs four more integer instructions per round: the 8 us per launch that r04 lost against r03 on one box,
-  //  profiles/r05_ab_rounds.txt.  NB = 2 keeps the packed word: its LDS block has no 2.5 KB to spare)
+  double* const GS = rGS + (size_t)lec * GW;
+  unsigned* const TAB = (unsigned*)rTAB;
   constexpr int TABW = CST ? 1 : 2;
-  double* const Lnb = lds + (size_t)EPW * NAr + (size_t)EPW * GW + (size_t)8 * TABW * (H.eq_rounds + 8);  // [72 + 2 EPW]
-  double* Lzero = NB ? Lnb : lds + (size_t)(5 * EPW + 2) * NR;  // [0]: a word that stays 0 (reads of "no slider"), [1 + lane]: write sink
-  double* const Lenv = Lnb + 72;  // NB: [e2] sum of the env's slider accelerations at the start, [EPW + e2] its final offset aoff
+  double* const Lnb = SG_LDS_NB_ZERO(rTAB, H.eq_rounds, CST);
+  double* Lzero = NB ? Lnb : SG_LDS_FIX_ZERO(rIC, NR);  // [0]: a word that stays 0 (reads of "no slider"), [1 + lane]: write sink
+  double* const Lenv = SG_LDS_NB_ENV(Lnb);  // NB: [e2] sum of the env's slider accelerations at the start, [EPW + e2] its final offset aoff
   double* const ASb = NB ? Ae : (double*)AF;  // slider acceleration of element j: ASb[ASS * j]
   constexpr int ASS = NB ? 1 : 2;
   if (lane == 0) Lzero[0] = 0.0;
@@ -138,8 +132,8 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
       const int env2 = blockIdx.x * EPW + e2;
       const bool v2 = ((pendmask >> e2) & 1u) != 0;  // uniform
       double2* const AF2 = (double2*)lds + (size_t)e2 * NR;
-      double2* const BR2 = (double2*)lds + (size_t)EPW * NR + (size_t)e2 * NR;
-      double* const RI2 = lds + (size_t)4 * EPW * NR + (size_t)e2 * NR;
+      double2* const BR2 = (double2*)rBR + (size_t)e2 * NR;
+      double* const RI2 = rRI + (size_t)e2 * NR;
 #pragma unroll
       for (int j0 = 0; j0 < NR; j0 += 64) {
         const int j = j0 + lane;
@@ -160,15 +154,15 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
   // the neutral values.  Fix-only models: loaded behind those two predicates, as ever.
   const bool sv = valid && g < 8;  // lanes of the env's two finger quads
   const int envl = env < a.nenv ? env : a.nenv - 1;
-  const size_t st = 2 * (size_t)envl + (c & 1);
+  const size_t st = SG_STREAM(envl, c & 1);
   int ns, lim_active, shared, ngen;  // ngen: contacts of an env on the general contact path (sg_general.h); 0 on the fast path
   // lane r of the quad owns finger acceleration aF[r]; of M^-1 it needs row r (its share of a limit row's push) and the diagonal
   double Mrow[SG_CD], Mdiag[SG_CD], aFo;
   double tb, tR, tA, tf;
   double lsign[SG_MAXLIM], lR[SG_MAXLIM], lb[SG_MAXLIM], lf[SG_MAXLIM];
   auto env_loads = [&]() {
-    tb = W.envh[(size_t)0 * a.nenv + envl]; tR = W.envh[(size_t)1 * a.nenv + envl];
-    tA = W.envh[(size_t)2 * a.nenv + envl]; tf = W.envh[(size_t)3 * a.nenv + envl];
+    tb = W.envh[SG_ENVH_INDEX(SG_ENVH_TB, envl, a.nenv)]; tR = W.envh[SG_ENVH_INDEX(SG_ENVH_TR, envl, a.nenv)];
+    tA = W.envh[SG_ENVH_INDEX(SG_ENVH_TA, envl, a.nenv)]; tf = W.envh[SG_ENVH_INDEX(SG_ENVH_TF, envl, a.nenv)];
     shared = W.shared[envl];
     ngen = W.gen[envl];
   };
@@ -176,12 +170,12 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
     ns = W.ns[st];
     lim_active = W.lim_active[st];
 #pragma unroll
-    for (int d = 0; d < SG_CD; d++) { Mrow[d] = W.sMinv[(size_t)(4 * r + d) * S + st]; Mdiag[d] = W.sMinv[(size_t)(5 * d) * S + st]; }
-    aFo = W.saF[(size_t)r * S + st];
+    for (int d = 0; d < SG_CD; d++) { Mrow[d] = W.sMinv[SG_MINV_INDEX(4 * r + d, st, S)]; Mdiag[d] = W.sMinv[SG_MINV_INDEX(5 * d, st, S)]; }
+    aFo = W.saF[SG_SAF_INDEX(r, st, S)];
 #pragma unroll
     for (int k = 0; k < SG_MAXLIM; k++) {  // the stream's limit rows live in registers, the same values on the four lanes of its quad
-      lsign[k] = W.lim[((size_t)0 * SG_MAXLIM + k) * S + st]; lR[k] = W.lim[((size_t)1 * SG_MAXLIM + k) * S + st];
-      lb[k] = W.lim[((size_t)2 * SG_MAXLIM + k) * S + st]; lf[k] = W.lim[((size_t)3 * SG_MAXLIM + k) * S + st];
+      lsign[k] = W.lim[SG_LIM_INDEX(SG_LIM_SIGN, k, st, S)]; lR[k] = W.lim[SG_LIM_INDEX(SG_LIM_R, k, st, S)];
+      lb[k] = W.lim[SG_LIM_INDEX(SG_LIM_B, k, st, S)]; lf[k] = W.lim[SG_LIM_INDEX(SG_LIM_F, k, st, S)];
     }
   };
   // the neutral values by selects, behind unconditional loads: ve the lane's env is pending, vq ... and the lane in a finger quad.  (Not the two
@@ -275,7 +269,7 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
       const int us = sg_eq_rec_stored(u, N) ? u : 4 * (N + 1) - 1;   // lanes past the records write group N's last zero again: no predicate
 #pragma unroll
       for (int e2 = 0; e2 < EPW; e2++) {
-        double* const GS2 = lds + (size_t)EPW * NAr + (size_t)e2 * GW;   // group e = rows 4 e .. 4 e + 3
+        double* const GS2 = rGS + (size_t)e2 * GW;   // group e = rows 4 e .. 4 e + 3
         if constexpr (CST) GS2[us] = live ? gv[e2][t] : 0.0;
         else ((double2*)GS2)[us] = make_double2(live ? gv[e2][t] : 0.0, live ? cv[e2][t] : 0.0);
       }
@@ -305,15 +299,15 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
   // NB: the env's acceleration offset, the tracked sum of its slider accelerations and this lane's not yet reduced share of it
   double aoff = 0.0, Ssum = NB ? Lenv[lec] : 0.0, dS = 0.0;
   const double im0 = NB ? 1.0 / (a.elem[(size_t)SGE_MASS * N] + a.elem[(size_t)SGE_ARMATURE * N]) : 0.0;
-  // my column in the wave's block, biased by 4 field pairs (immediate offsets -4096 .. 3072).  Lanes without an env (idle half of
+  // my column in the wave's block, biased by SG_ROW_BASE_PAIR field pairs (immediate offsets -4096 .. 3072: SG_ROW_IMM).  Lanes without an env (idle half of
   // an EPW = 4 wavefront, ragged tail, env not pending) read and write a block of their own wavefront that holds zeros and
   // never advance: a dummy block shared by all wavefronts made every idle lane of the chip hammer the same 8 KB
   // (profiles/r02: 1024 wavefronts x 32 idle lanes, contact rows 2.3x slower than with 16 streams per wavefront).
   // (the phase kernel writes blocks of 8 envs: env e sits in block e >> 3 at lanes 8 (e & 7) .. + 7, whatever EPW is)
   const bool has_row = sv;
-  const double2* const row0 = has_row ? (const double2*)(W.crow + SG_ROW_INDEX(0, env >> 3, 8, 8 * (env & 7) + g, nwb))
-                                      : (const double2*)(W.cdummy + ((size_t)blockIdx.x * (SG_RK / 2) + 4) * 128 + 2 * lane);
-  const size_t slot_stride = has_row ? (size_t)(nwb + 2) * (SG_RK / 2) * 64 : 0;  // in double2 units (per lane: idle lanes stay put)
+  const double2* const row0 = has_row ? (const double2*)(W.crow + SG_ROW_INDEX(0, env >> 3, 2 * SG_ROW_BASE_PAIR, 8 * (env & 7) + g, nwb))
+                                      : (const double2*)(W.cdummy + sg_row_dummy_index(blockIdx.x, SG_ROW_BASE_PAIR) + 2 * lane);
+  const size_t slot_stride = has_row ? sg_row_slot_stride(nwb) : 0;  // in double2 units (per lane: idle lanes stay put)
   constexpr ptrdiff_t sink_off = 0;
 
   // NB: the equality rows' step factors, round k of my lane: cp0[64 k] -- 64 lanes x 16 bytes contiguous per round, written by the
@@ -362,8 +356,8 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
         struct Off { double sA, wA, sB, wB, ga, gb; };   // what a round leaves for its off-chain part
         auto adr_of = [&](const TabW tt) {
           Adr q;
-          if constexpr (CST) { q.px = (double*)(Ab + (tt & 0x7ffu)); q.py = (double*)(Ab + ((tt >> 11) & 0x7ffu)); q.rec = (double2*)(Gb + ((tt >> 22) << 4)); }
-          else { q.px = (double*)(Ab + (tt.x & 0xffffu)); q.py = (double*)(Ab + (tt.x >> 16)); q.rec = (double2*)(Gb + tt.y); }
+          if constexpr (CST) { q.px = (double*)(Ab + sg_tab1_x(tt)); q.py = (double*)(Ab + sg_tab1_y(tt)); q.rec = (double2*)(Gb + sg_tab1_rec(tt)); }
+          else { q.px = (double*)(Ab + sg_tab2_x(tt.x)); q.py = (double*)(Ab + sg_tab2_y(tt.x)); q.rec = (double2*)(Gb + tt.y); }
           return q;
         };
         // The CHAIN of a round -- slider reads -> two rows on lane 0 -> hand-over -> two rows on lane 1 -> hand-over -> slider writes, which
@@ -526,8 +520,8 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
       if (nsmax == 0) { SG_T(14); continue; }  // no contacts anywhere in the wavefront: no look-ahead loads to wait for, no barrier
       struct Row { double2 j01, j23, jsb, fw, a01, a2s, p12, p3i; };
       auto load_row = [&](Row& w, const double2* p) {
-        w.j01 = p[-4 * 64]; w.j23 = p[-3 * 64]; w.jsb = p[-2 * 64]; w.fw = p[-1 * 64];
-        w.a01 = p[0]; w.a2s = p[1 * 64]; w.p12 = p[2 * 64]; w.p3i = p[3 * 64];
+        w.j01 = p[SG_ROW_IMM(SGR_JF0)]; w.j23 = p[SG_ROW_IMM(SGR_JF2)]; w.jsb = p[SG_ROW_IMM(SGR_JS)]; w.fw = p[SG_ROW_IMM(SGR_F)];
+        w.a01 = p[SG_ROW_IMM(SGR_A0)]; w.a2s = p[SG_ROW_IMM(SGR_A2)]; w.p12 = p[SG_ROW_IMM(SGR_W0)]; w.p3i = p[SG_ROW_IMM(SGR_W2)];
       };
       auto update_row = [&](Row& w, int i, const double2* pl) {
         if (i < nsl) {
@@ -597,83 +591,8 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
             const bool ever = run;
             double x1 = e1, x2 = e2;
             if (run) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(SG_SECTION_COUNT)
-              // the loop by hand (the compiler's lowering of the divergent loop spends 14 of its 41 instructions per evaluation on exec-mask
-              // bookkeeping; a lone wavefront pays ~7 cycles for each, scalar or vector): 28 instructions per evaluation, two evaluations
-              // per trip.  Lanes leave by having their exec bit cleared; exec is restored at the end.  v_rcp_f64 (a transcendental-unit op) has two independent
-              // instructions between it and its first consumer.
-              double y1, y2, xx, ah, bh, yy, nh, dh, rc, nx, er, dl, ox1, ox2;  // ox1, ox2: early-clobber outputs (as read-write
-              unsigned long long sv, m0, m1;                                    // operands initialised with e1, e2 they were given e1's, e2's registers)
-              unsigned cnt;
-              asm volatile(
-                  "s_mov_b64 %[sv], exec\n\t"
-                  "s_mov_b32 %[cnt], 19\n"      // evaluations 1 .. 19 (the fast path did evaluation 0): nine trips of two and one more
-                  "1:\n\t"
-                  "v_add_f64 %[x1], %[e1], %[la]\n\t"
-                  "v_add_f64 %[x2], %[e2], %[la]\n\t"
-                  "v_mul_f64 %[y1], %[x1], %[x1]\n\t"
-                  "v_mul_f64 %[y2], %[x2], %[x2]\n\t"
-                  "v_mul_f64 %[xx], %[x1], %[x2]\n\t"
-                  "v_mul_f64 %[ah], %[C1h], %[y2]\n\t"
-                  "v_mul_f64 %[bh], %[C2h], %[y1]\n\t"
-                  "v_mul_f64 %[yy], %[y1], %[y2]\n\t"
-                  "v_add_f64 %[nh], %[ah], %[bh]\n\t"
-                  "v_mul_f64 %[dh], %[bh], %[x1]\n\t"
-                  "v_fma_f64 %[nh], %[nR2h], %[yy], %[nh]\n\t"
-                  "v_fma_f64 %[dh], %[ah], %[x2], %[dh]\n\t"
-                  "v_cmp_gt_f64_e64 %[m0], %[tol], %[xx]\n\t"
-                  "v_add_f64 %[dh], %[dh], %[dh]\n\t"
-                  "v_mul_f64 %[yy], %[yy], %[tolh]\n\t"
-                  "v_rcp_f64_e32 %[rc], %[dh]\n\t"
-                  "v_mul_f64 %[nx], %[nh], %[xx]\n\t"
-                  "v_cmp_lt_f64_e64 %[m1], %[nh], %[yy]\n\t"
-                  "v_fma_f64 %[er], -%[dh], %[rc], 1.0\n\t"
-                  "s_or_b64 %[m0], %[m0], %[m1]\n\t"
-                  "v_fma_f64 %[rc], %[er], %[rc], %[rc]\n\t"
-                  "v_mul_f64 %[dl], %[nx], %[rc]\n\t"
-                  "v_cmp_gt_f64_e64 %[m1], %[tol], %[dl]\n\t"
-                  "s_or_b64 %[m0], %[m0], %[m1]\n\t"
-                  "s_andn2_b64 exec, exec, %[m0]\n\t"
-                  "s_cbranch_execz 2f\n\t"
-                  "v_add_f64 %[la], %[la], %[dl]\n\t"
-                  "s_cmp_eq_u32 %[cnt], 1\n\t"
-                  "s_cbranch_scc1 2f\n\t"
-                  "v_add_f64 %[x1], %[e1], %[la]\n\t"
-                  "v_add_f64 %[x2], %[e2], %[la]\n\t"
-                  "v_mul_f64 %[y1], %[x1], %[x1]\n\t"
-                  "v_mul_f64 %[y2], %[x2], %[x2]\n\t"
-                  "v_mul_f64 %[xx], %[x1], %[x2]\n\t"
-                  "v_mul_f64 %[ah], %[C1h], %[y2]\n\t"
-                  "v_mul_f64 %[bh], %[C2h], %[y1]\n\t"
-                  "v_mul_f64 %[yy], %[y1], %[y2]\n\t"
-                  "v_add_f64 %[nh], %[ah], %[bh]\n\t"
-                  "v_mul_f64 %[dh], %[bh], %[x1]\n\t"
-                  "v_fma_f64 %[nh], %[nR2h], %[yy], %[nh]\n\t"
-                  "v_fma_f64 %[dh], %[ah], %[x2], %[dh]\n\t"
-                  "v_cmp_gt_f64_e64 %[m0], %[tol], %[xx]\n\t"
-                  "v_add_f64 %[dh], %[dh], %[dh]\n\t"
-                  "v_mul_f64 %[yy], %[yy], %[tolh]\n\t"
-                  "v_rcp_f64_e32 %[rc], %[dh]\n\t"
-                  "v_mul_f64 %[nx], %[nh], %[xx]\n\t"
-                  "v_cmp_lt_f64_e64 %[m1], %[nh], %[yy]\n\t"
-                  "v_fma_f64 %[er], -%[dh], %[rc], 1.0\n\t"
-                  "s_or_b64 %[m0], %[m0], %[m1]\n\t"
-                  "v_fma_f64 %[rc], %[er], %[rc], %[rc]\n\t"
-                  "v_mul_f64 %[dl], %[nx], %[rc]\n\t"
-                  "v_cmp_gt_f64_e64 %[m1], %[tol], %[dl]\n\t"
-                  "s_or_b64 %[m0], %[m0], %[m1]\n\t"
-                  "s_andn2_b64 exec, exec, %[m0]\n\t"
-                  "v_add_f64 %[la], %[la], %[dl]\n\t"   // (with every lane masked off this adds nothing)
-                  "s_sub_u32 %[cnt], %[cnt], 2\n\t"
-                  "s_cbranch_execnz 1b\n"
-                  "2:\n\t"
-                  "s_mov_b64 exec, %[sv]"
-                  : [x1] "=&v"(ox1), [x2] "=&v"(ox2), [la] "+v"(la), [y1] "=&v"(y1), [y2] "=&v"(y2), [xx] "=&v"(xx), [ah] "=&v"(ah), [bh] "=&v"(bh),
-                    [yy] "=&v"(yy), [nh] "=&v"(nh), [dh] "=&v"(dh), [rc] "=&v"(rc), [nx] "=&v"(nx), [er] "=&v"(er), [dl] "=&v"(dl),
-                    [sv] "=&s"(sv), [m0] "=&s"(m0), [m1] "=&s"(m1), [cnt] "=&s"(cnt)
-                  : [e1] "v"(e1), [e2] "v"(e2), [C1h] "v"(C1h), [C2h] "v"(C2h), [nR2h] "v"(-R2h), [tol] "s"(1e-10), [tolh] "s"(0.5e-10)
-                  : "vcc", "scc");
-              x1 = ox1; x2 = ox2;
+#ifdef SG_NEWTON_BY_HAND
+              SG_QCQP_NEWTON_BY_HAND(e1, e2, C1h, C2h, R2h, la, x1, x2);   // (sg_math.h; in place, not behind qcqp_newton_by_hand: see there)
 #else
 #pragma unroll 1
               for (int it = 1; it < 20; it++) {
@@ -723,7 +642,7 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
           aFo += (W0 * sg_qb<0>(dr) + W1 * sg_qb<1>(dr)) + W2 * sg_qb<2>(dr);
           w.fw = make_double2(fn, wn);
         }
-        ((double2*)pl)[sink_off - 1 * 64] = w.fw;
+        ((double2*)pl)[sink_off + SG_ROW_IMM(SGR_F)] = w.fw;
       };
 #ifdef SG_SECTION_PROF
       if (lane == 0) { atomicAdd(&a.w.secprof[28], (unsigned long long)nsmax); atomicAdd(&a.w.secprof[29], 1ull); }
@@ -770,12 +689,12 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
 #pragma unroll
         for (int q = 0; q < SG_CD; q++) aF2[cc][q] = __shfl(aFo, gbase + 4 * cc + q);
       if (ngen > 0 && g == 0 && running) {
-        const size_t st0 = 2 * (size_t)env;
+        const size_t st0 = SG_STREAM(env, 0);
         double Mi[SG_MAXCH][16];
 #pragma unroll
         for (int cc = 0; cc < SG_MAXCH; cc++)
 #pragma unroll
-          for (int i = 0; i < 16; i++) Mi[cc][i] = W.sMinv[(size_t)i * S + st0 + cc];
+          for (int i = 0; i < 16; i++) Mi[cc][i] = W.sMinv[SG_MINV_INDEX(i, st0, S) + cc];   // (stream st0 + cc)
         const double mu[2] = {mu0, mu1};
 #pragma unroll 1
         for (int i = 0; i < ngen; i++) {
@@ -826,7 +745,7 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
   //      ~10^3 additions (parity against the oracle, which multiplies out the final forces: 9e-12 over the episode).  Recomputing
   //      them from the forces cost one more pass over all contact rows, 3.3 % of the kernel (until r01 v11)
   __syncthreads();
-  if (sv) W.saF[(size_t)r * S + st] = aFo;
+  if (sv) W.saF[SG_SAF_INDEX(r, st, S)] = aFo;
   if (valid && g == 0) W.iters[env] = iters;
   if constexpr (NB) {
     if (valid && g == 0) Lenv[EPW + le] = aoff;
@@ -846,19 +765,13 @@ __global__ __launch_bounds__(64) void sg_pgs_rows_kernel(SgPgsArgs a) {
 }
 
 
-// ---- launchers ----
-static const int sg_nsl_set[] = {8, 14, 20, 26, 29, 32};
-int sg_rows_nsl(int nelem) {
-  for (int v : sg_nsl_set)
-    if (v * 8 >= nelem) return v;
-  return 32;
-}
+// ---- launchers: one instantiation set per NSL of SG_NSL_LIST (sg_rows_layout.h) ----
 hipError_t sg_rows_prepare() {
   hipError_t e = hipSuccess;
 #define SG_ATTR1(v, nb, ep)                                                                                                        \
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)sg_pgs_rows_kernel<v, nb, ep>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-#define SG_ATTR(v) SG_ATTR1(v, 0, 8); SG_ATTR1(v, 0, 4); SG_ATTR1(v, 1, 4); SG_ATTR1(v, 2, 4)
-  SG_ATTR(8); SG_ATTR(14); SG_ATTR(20); SG_ATTR(26); SG_ATTR(29); SG_ATTR(32);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)sg_pgs_rows_kernel<v, nb, ep>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+#define SG_ATTR(v) SG_ATTR1(v, 0, 8) SG_ATTR1(v, 0, 4) SG_ATTR1(v, 1, 4) SG_ATTR1(v, 2, 4)
+  SG_NSL_LIST(SG_ATTR)
 #undef SG_ATTR
 #undef SG_ATTR1
   return e;
@@ -871,11 +784,10 @@ hipError_t sg_launch_rows(const SgPgsArgs& ga, int nsl, int nb, int epw, int nen
     if (nb == 2) SG_ROWS1(v, 2, 4);                                                   \
     else if (nb == 1) SG_ROWS1(v, 1, 4);                                              \
     else { if (epw == 8) SG_ROWS1(v, 0, 8); else SG_ROWS1(v, 0, 4); }                 \
-    break
+    break;
   switch (nsl) {
-    SG_ROWS(8); SG_ROWS(14); SG_ROWS(20); SG_ROWS(26); SG_ROWS(29);
-    default:
-    SG_ROWS(32);
+    SG_NSL_LIST(SG_ROWS)
+    default: return hipErrorInvalidValue;   // not a value of sg_rows_nsl: no such kernel
   }
 #undef SG_ROWS
 #undef SG_ROWS1

@@ -1,7 +1,7 @@
 // sg_rows_host.h -- the host side of the rows pipeline (sg_phase.hip, sg_rows.hip), in one place and free of device calls: which models
 // the solver admits, the shape of its launch, the solver's tables as the kernels decode them, and the size of every buffer of SgWork.
-// sg_api.hip's rows_alloc and launch_split are its users in the library; tests/emu/sg_rows_host_test.cpp holds it against the kernels'
-// indexing rules (SG_ROW_INDEX, SG_CST_INDEX, the table decode of sg_pgs_rows_kernel) on the host.
+// sg_api.hip's rows_alloc and launch_split are its users in the library.  Every layout rule it sizes and packs by is sg_rows_layout.h's, the
+// kernels' own; tests/emu/sg_rows_host_test.cpp runs those rules over blocks of the sizes made here.
 #pragma once
 #include <string>
 #include <vector>
@@ -9,21 +9,9 @@
 #include "sg_plan.h"
 #include "sg_work.h"
 
-// ---- the solver's table words (sg_pgs_rows_kernel: adr_of) ----
-// Lane 2 b + h of an env's 16-lane group holds, for the block e in slot b of a round, the byte offsets (x, y) of two slider words in the
-// env's slider array -- (x, y) = 8 (e, p0) for h = 0 and 8 (p1, p2) for h = 1 -- and where the lane's pair of row states sits:
-//   streamed step factors (NB = 2): ONE word   x | y << SG_TAB1_YSH | (2 e + h) << SG_TAB1_RSH    the pair of states in 16-byte units
-//   step factors in LDS   (NB = 1): TWO words  x | y << SG_TAB2_YSH,  64 e + 32 h                   the byte offset of two 32-byte records
-constexpr int SG_TAB1_YSH = 11, SG_TAB1_RSH = 22, SG_TAB2_YSH = 16;
-// what the narrowest field admits: an env's slider array -- nelem sliders, the zero word and a word of padding -- within reach of an
-// 11-bit byte offset
-constexpr int SG_ROWS_MAX_NELEM = (1 << SG_TAB1_YSH) / 8 - 2;
-static_assert(SG_ROWS_MAX_NELEM == 254 && 2 * SG_ROWS_MAX_NELEM + 1 < (1 << (32 - SG_TAB1_RSH)) && SG_TAB1_RSH - SG_TAB1_YSH >= SG_TAB1_YSH &&
-              8 * (SG_ROWS_MAX_NELEM + 2) <= (1 << SG_TAB2_YSH), "every field of a table word holds its largest value");
-
 // does the rows solver run a two-finger model?  (neighbour-row models: the kernel keeps every equality row of its envs in LDS)
 inline bool sg_rows_admits(const SgPlanHeader& H, std::string* err) {
-  if (H.nnb > 0 && (sizeof(double) * SG_ROWS_LDS_NB(4, H.nelem, H.eq_rounds, 1) > 160 * 1024 || H.nelem > SG_ROWS_MAX_NELEM)) {
+  if (H.nnb > 0 && (H.nelem > SG_ROWS_MAX_NELEM || sizeof(double) * SG_ROWS_LDS_NB(4, H.nelem, H.eq_rounds, 1) > 160 * 1024)) {
     if (err) *err = "too many neighbour equality rows for the PGS kernel's LDS";
     return false;
   }
@@ -39,7 +27,7 @@ struct SgRowsShape {
   size_t tab_words = 0;    // the table: 16 lanes x (1 | 2) words x (eq_rounds + 8) rounds, 0 without neighbour rows
   // the kernel's LDS block in doubles: epw envs per wavefront; nsl (sg_rows_nsl) pads the joint-fix rows of a model without neighbour rows
   size_t lds_doubles(int epw, int nsl) const {
-    return nb_mode ? SG_ROWS_LDS_NB(epw, nelem, eq_rounds, nb_mode == 2) : SG_ROWS_LDS_FIX(epw, 8 * (size_t)nsl);
+    return nb_mode ? SG_ROWS_LDS_NB(epw, nelem, eq_rounds, nb_mode == 2) : SG_ROWS_LDS_FIX(epw, 8 * nsl);
   }
 };
 inline SgRowsShape sg_rows_shape(const SgPlanHeader& H) {
@@ -48,7 +36,7 @@ inline SgRowsShape sg_rows_shape(const SgPlanHeader& H) {
   s.nb_mode = H.nnb > 0 ? SG_ROWS_NB_MODE(H.nelem, H.eq_rounds) : 0;
   s.two_words = s.nb_mode == 1;
   s.cst_rounds = s.nb_mode == 2 ? H.eq_rounds + 8 : 0;
-  s.tab_words = s.nb_mode ? (size_t)16 * (s.two_words ? 2 : 1) * (H.eq_rounds + 8) : 0;
+  s.tab_words = s.nb_mode ? sizeof(double) / sizeof(unsigned) * SG_LDS_NB_ZERO((size_t)0, H.eq_rounds, s.nb_mode == 2) : 0;
   return s;
 }
 
@@ -71,8 +59,8 @@ inline void sg_rows_tables(const SgPlan& P, SgRowsTables* T) {
     const SgEqSlot& sl = sch[i >> 1];
     const int h = (int)(i & 1);
     const unsigned x = h ? sl.p[1] : sl.e, y = h ? sl.p[2] : sl.p[0];
-    if (two_words) { T->tab[2 * i] = (8u * x) | ((8u * y) << SG_TAB2_YSH); T->tab[2 * i + 1] = 64u * (unsigned)sl.e + 32u * (unsigned)h; }
-    else T->tab[i] = (8u * x) | ((8u * y) << SG_TAB1_YSH) | ((2u * (unsigned)sl.e + (unsigned)h) << SG_TAB1_RSH);
+    if (two_words) { T->tab[2 * i] = sg_tab2_pack(x, y); T->tab[2 * i + 1] = sg_tab2_rec((unsigned)sl.e, (unsigned)h); }
+    else T->tab[i] = sg_tab1_pack(x, y, (unsigned)sl.e, (unsigned)h);
   }
   // round r, slot g of the schedule = lanes 2 g, 2 g + 1 of the env's 16-lane group, two doubles each (SG_CST_INDEX): doubles from the
   // start of the env's group in round 0
@@ -91,14 +79,14 @@ bool sg_rows_work_each(SgWork& w, const SgPlanHeader& H, int rounds, size_t n, b
   const bool slim = SG_PHASE_SLIM(rounds);
   return f(&w.crec, legacy ? SG_CAP * ((n + SG_EPW - 1) / SG_EPW + 1) * SG_RF * SG_SPW : 0) &&   // [SG_CAP][nwb + 1][SG_RF][16]
          f(&w.ns, S) &&                                                       // [S]
-         f(&w.crow, (SG_CAP + 2) * ((n + 7) / 8 + 2) * SG_RK * 64) &&         // [SG_CAP + 2][nwb + 2][SG_RK / 2][64][2]
-         f(&w.cdummy, ((n + 3) / 4) * SG_RK * 64) &&                          // [ceil(n / 4)][SG_RK / 2][64][2]
-         f(&w.envh, 4 * n) &&                                                 // [4][n]
+         f(&w.crow, SG_ROW_INDEX(SG_CAP + 2, 0, 0, 0, (n + 7) / 8)) &&       // [SG_CAP + 2][nwb + 2][SG_RK / 2][64][2]
+         f(&w.cdummy, sg_row_dummy_index((n + 3) / 4, 0)) &&               // [ceil(n / 4)][SG_RK / 2][64][2]
+         f(&w.envh, SG_ENVH_ROWS * n) &&                                      // [SG_ENVH_ROWS][n]
          f(&w.shared, n) && f(&w.pending, n) && f(&w.status, n) && f(&w.iters, n) && f(&w.ncon, n) && f(&w.nefc, n) && f(&w.touch, n) &&   // [n]
-         f(&w.sMinv, 16 * S) &&                                               // [16][S]
-         f(&w.saF, 4 * S) &&                                                  // [4][S]
+         f(&w.sMinv, SGH_N_M * S) &&                                          // [16][S]
+         f(&w.saF, SG_CD * S) &&                                              // [4][S]
          f(&w.lim_active, S) &&                                               // [S]
-         f(&w.lim, 4 * SG_MAXLIM * S) &&                                      // [4][SG_MAXLIM][S]
+         f(&w.lim, SGH_N_LIM * S) &&                                          // [SG_LIM_ROWS][SG_MAXLIM][S]
          f(&w.as, n * N) && f(&w.eqf, n * N) && f(&w.eqb, n * N) && f(&w.eqR, n * N) && f(&w.asme, n * N) && f(&w.fsm, n * N) &&   // [n][N]
          f(&w.chh, n * 2 * SG_CHW) &&                                         // [n][2][SG_CHW]
          f(&w.nbf, n * (3 * N + 1)) && f(&w.nbb, n * (3 * N + 1)) && f(&w.nbR, n * (3 * N + 1)) &&   // [n][3 N] (+ 1 each)

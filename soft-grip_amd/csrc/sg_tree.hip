@@ -27,23 +27,26 @@ __global__ __launch_bounds__(64) void sg_tree_kernel(sgt::TreeArgs a) {
 }
 
 // ---- launchers (declared in sg_tree.h) ----
+// the instantiations: the one whose capacity IS the model's padded chain stride CS runs it (sg_plan.cpp pads to 8, 20 or SGT_CHD)
+#define SG_TREE_CHD_LIST(X) X(8) X(20) X(SGT_CHD)
 hipError_t sg_tree_prepare() {
-  hipError_t e = hipFuncSetAttribute((const void*)sg_tree_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)sg_tree_kernel<20>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)sg_tree_kernel<SGT_CHD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipError_t e = hipSuccess;
+#define SG_TREE_ATTR(c) if (e == hipSuccess) e = hipFuncSetAttribute((const void*)sg_tree_kernel<c>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  SG_TREE_CHD_LIST(SG_TREE_ATTR)
+#undef SG_TREE_ATTR
   return e;
 }
 int sg_tree_occupancy(int CS, size_t lds_bytes) {
   int n = 0;
-  hipError_t e = CS == 8    ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sg_tree_kernel<8>, 64, lds_bytes)
-                 : CS == 20 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sg_tree_kernel<20>, 64, lds_bytes)
-                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sg_tree_kernel<SGT_CHD>, 64, lds_bytes);
+  hipError_t e = hipErrorInvalidValue;
+#define SG_TREE_OCC(c) if (CS == c) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sg_tree_kernel<c>, 64, lds_bytes);
+  SG_TREE_CHD_LIST(SG_TREE_OCC)
+#undef SG_TREE_OCC
   return e == hipSuccess ? n : -1;
 }
-// the instantiation whose capacity IS the model's padded chain stride CS (sg_plan.cpp pads to 8, 20 or SGT_CHD)
 hipError_t sg_launch_tree(const sgt::TreeArgs& a, int CS, size_t lds_bytes, hipStream_t s) {
-  if (CS == 8) hipLaunchKernelGGL(sg_tree_kernel<8>, dim3(a.nenv), dim3(64), lds_bytes, s, a);
-  else if (CS == 20) hipLaunchKernelGGL(sg_tree_kernel<20>, dim3(a.nenv), dim3(64), lds_bytes, s, a);
-  else hipLaunchKernelGGL(sg_tree_kernel<SGT_CHD>, dim3(a.nenv), dim3(64), lds_bytes, s, a);
-  return hipGetLastError();
+#define SG_TREE_LAUNCH(c) if (CS == c) { hipLaunchKernelGGL(sg_tree_kernel<c>, dim3(a.nenv), dim3(64), lds_bytes, s, a); return hipGetLastError(); }
+  SG_TREE_CHD_LIST(SG_TREE_LAUNCH)
+#undef SG_TREE_LAUNCH
+  return hipErrorInvalidValue;   // a stride without an instantiation: no such kernel
 }

@@ -1,5 +1,5 @@
-// sg_work.h -- what the kernels of the two-finger class share: the batch's device work space (SgWork), the kernel argument blocks,
-// the layouts of the contact rows (SG_ROW_INDEX) and of the solver's stream of step factors (SG_CST_INDEX), and the LAUNCHERS.
+// sg_work.h -- what the kernels of the two-finger class share: the batch's device work space (SgWork), the kernel argument blocks
+// and the LAUNCHERS; the layouts of what the kernels pass each other through that work space are sg_rows_layout.h's.
 //
 // One translation unit per kernel family -- sg_phase.hip (sg_chain_kernel, sg_phase_kernel), sg_rows.hip (sg_pgs_rows_kernel: the
 // solver), sg_tree.hip (the tree pipeline) and, in test builds only (-DSG_LEGACY_PIPELINES), sg_legacy.hip (r01's fused and split
@@ -11,6 +11,7 @@
 #include "../../include/softgrip.h"
 #include "sg_math.h"
 #include "sg_general.h"
+#include "sg_rows_layout.h"
 
 using namespace sgm;
 
@@ -26,7 +27,6 @@ using namespace sgm;
 #define SG_EPW (64 / SG_G)   // envs per PGS wavefront
 #define SG_SPW (2 * SG_EPW)  // finger streams per PGS wavefront
 #define SG_GEN_GRID 256  // blocks of the general contact pass (they stride over the listed envs: no limit on how many there are)
-#define SG_CHW 160       // doubles of chain hand-off per stream (layout: see sg_chain_kernel)
 
 struct SgWork {          // device workspace of one batch (all pointers device memory; every member's element count: sg_rows_work_each, sg_rows_host.h)
   double* crec;          // [SG_CAP][nwb + 1][SG_RF][16]   nwb = ceil(nenv / 8) PGS wavefronts (+1 dummy block)
@@ -85,49 +85,10 @@ struct SgPhaseArgs {
   double timestep;
 };
 
-// chain hand-off record (doubles): written by the chain stage (phase kernel or sg_chain_kernel), read by FINISH and by BEGIN
-// Row layout of the contact records for sg_pgs_rows_kernel: a finger stream is a QUAD of lanes, lane r < 3 holds row r
-// (normal, tangent 1, tangent 2) of every contact, lane 3 what the rows share; lane q also OWNS finger acceleration aF[q].
-// Block per (slot, wavefront): 8 field PAIRS x 64 lanes x 2 doubles, so a lane fetches two fields with one 16-byte load.
-// Field k of lane (8 * env_in_wave + 4 * chain + r), r < 3:
-//   0..3 Jf[r][0..3] | 4 Js[r] | 5 b[r] | 6 f[r] | 7 (A f)[r] | 8..10 A[r][0..2] | 11 invm * Js[r] | 12..14 W_0[r] W_1[r] W_2[r] | 15 R
-// of lane r = 3:
-//   0..2 inverse friction block P11 P12 P22 | 3 zero | 4 slider index | 5..7 zero | 8..11 eigen-decomposition of the friction-scaled
-//   block S = Q diag(e1, e2) Q': e1 e2 cos sin (for the QCQP Newton iteration) | 12..14 W_0[3] W_1[3] W_2[3] | 15 zero
-// W_k = M^-1 J_F[k]' (4 values per row k; lane q keeps the q-th of each): the finger update aF[q] += sum_k W_k[q] df_k is three
-// multiply-adds on lane q after broadcasting the three force changes, instead of four more quad sums and a 4 x 4 product on
-// every lane.  f and A f (fields 6, 7: one pair) are the only fields the solver writes.  Blocks nwb and nwb + 1 of every slot
-// are dummies: lanes of envs that do not exist read block nwb (all zero, never written) and write to block nwb + 1.
-#define SG_RK 16
-// the solver's stream of step factors (SgWork::cst), in doubles: wavefront w (four envs), round k of its equality block, lane l
-#define SG_CST_INDEX(w, k, l, rounds) ((((size_t)(w) * (rounds) + (k)) * 64 + (l)) * 2)
-// the equality block as the phase kernel exports it to the rows solver (neighbour-row models): element-major and dense, no look-up by row id.
-// Fix row of element e: SgWork::eqb / eqR [nenv][N]; its neighbour row d = 0 .. 2: SgWork::nbb / nbR [nenv][N][3]
-__host__ __device__ constexpr size_t sg_eq_fix_index(size_t env, int e, int N) { return env * (size_t)N + (size_t)e; }
-__host__ __device__ constexpr size_t sg_eq_nb_index(size_t env, int e, int d, int N) { return (env * (size_t)N + (size_t)e) * 3 + (size_t)d; }
-// The solver stages an env's 4 (N + 1) row records in trips of 64 lanes: lane l of trip t holds row u = 4 e + d -- d = 0 the fix row of
-// element e, d = 1 .. 3 its neighbour rows; group e = N is the idle slots' and stays zero, as does the padding behind it
-__host__ __device__ constexpr int sg_eq_rec_trips(int nr) { return (4 * (nr + 1) + 63) / 64; }   // nr >= N: the instantiation's padded row count
-__host__ __device__ constexpr int sg_eq_rec_row(int lane, int trip) { return lane + 64 * trip; }
-__host__ __device__ constexpr bool sg_eq_rec_stored(int u, int N) { return u < 4 * (N + 1); }      // the row has a record in LDS
-__host__ __device__ constexpr bool sg_eq_rec_live(int u, int N) { return u < 4 * N; }              // ... and is read from memory (else it is zero)
-// where row u of an env is read from: the fix rows' array (d = 0) or the neighbour rows' -- clamped, so that every lane of every trip and
-// every env slot of a ragged last wavefront forms an address inside the batch's arrays and the loads need no predicate
-__host__ __device__ constexpr size_t sg_eq_rec_index(size_t env, int u, int N, size_t nenv) {
-  const size_t envc = env < nenv ? env : nenv - 1;
-  const int uc = u < 4 * N ? u : 4 * N - 1, e = uc >> 2, d = uc & 3;
-  return d == 0 ? sg_eq_fix_index(envc, e, N) : sg_eq_nb_index(envc, e, d - 1, N);
-}
-#define SG_ROW_INDEX(slot, wave, k, lane, nwb) \
-  ((((((size_t)(slot)) * ((nwb) + 2) + (wave)) * (SG_RK / 2) + (k) / 2) * 64 + (lane)) * 2 + ((k) & 1))
-
 // The solver's look-ahead over a wavefront's contact slots 0 .. nsmax - 1 (sg_rows.hip, the contact pass): while slot i is updated the rows
 // of slot i + ahead are loaded into registers -- or nothing is (-1) where that slot is past the end of the wavefront's longest stream.
 // Whatever (i, ahead) a caller passes, a slot that comes back lies in [0, nsmax - 1] (tests/test_rows_touch_index.py).
 __host__ __device__ constexpr int sg_rows_load_slot(int i, int ahead, int nsmax) { return i + ahead < nsmax ? i + ahead : -1; }
-
-enum { SGH_QSM = 0, SGH_QFRC = 4, SGH_ACTDOT = 8, SGH_M = 9, SGH_K = 25, SGH_MINV = 73, SGH_V = 89, SGH_W = 93, SGH_BOX = 97,
-       SGH_LIMACT = 121, SGH_LIMSIGN = 122, SGH_LIMR = 130, SGH_LIMB = 138, SGH_LIMF = 146 };
 
 struct StageRec2 {
   double dist, pos[3], n[3];
@@ -139,6 +100,10 @@ struct ChainLds2 {  // what the phase kernel needs of a finger chain (imported f
   int lim_active, pad;
   double lim_sign[SG_MAXLIM], lim_R[SG_MAXLIM], lim_b[SG_MAXLIM], lim_f[SG_MAXLIM];  // contiguous, in the hand-off record's order
 };
+// (the phase kernel imports SGH_LIMSIGN .. and exports SgWork::lim as ONE run of SGH_N_LIM doubles from lim_sign on)
+static_assert(offsetof(ChainLds2, lim_R) - offsetof(ChainLds2, lim_sign) == (SGH_LIMR - SGH_LIMSIGN) * sizeof(double) &&
+              offsetof(ChainLds2, lim_b) - offsetof(ChainLds2, lim_sign) == (SGH_LIMB - SGH_LIMSIGN) * sizeof(double) &&
+              offsetof(ChainLds2, lim_f) - offsetof(ChainLds2, lim_sign) == (SGH_LIMF - SGH_LIMSIGN) * sizeof(double), "ChainLds2's limit rows lie as the hand-off record's");
 
 #define SG_PHASE_SLIM(R) ((R) >= 4)   // the pair list and the slot pushes live in the work space (SgWork::gpairs16, gcval), not in LDS
 #define SG_PAIRS_CAP(R) (SG_MAXCH * SG_CG * ((R) * 64 + 2))
@@ -203,21 +168,11 @@ struct SgPgsArgs {
   int nenv;
 };
 
-// LDS of sg_pgs_rows_kernel in doubles (kernel and host use the same expressions): EPW envs per wavefront
-#define SG_ROWS_LDS_FIX(EPW, NR) ((size_t)(5 * (EPW) + 2) * (NR) + 72)
-// neighbour-row models: slider words [EPW][N + 2] | row states g [EPW][4 (N + 1)] | table: 16 lanes x 4 B per round | 72 + 2 EPW.  (Until r04 the rows'
-// step factors c sat beside g -- 16 bytes a row, 70 KB for the ball's 218 elements: two workgroups per CU, i.e. the 1024 wavefronts of
-// a 4096-env batch in TWO rounds.  They now stream from memory in round-major order, SgWork::cst: 38 KB, four per CU, one round.)
-#define SG_ROWS_NA_NB(N) (((N) + 2) & ~1)
-#define SG_ROWS_LDS_NB(EPW, N, ROUNDS, CST) ((size_t)(EPW) * SG_ROWS_NA_NB(N) + (size_t)((CST) ? 4 : 8) * (EPW) * ((N) + 1) + (size_t)((CST) ? 8 : 16) * ((ROUNDS) + 8) + 72 + 2 * (EPW))
-// the step factors stay in LDS beside the states (NB = 1) while four workgroups of the solver still share a CU's 160 KB that way
-#define SG_ROWS_NB_MODE(N, ROUNDS) (sizeof(double) * SG_ROWS_LDS_NB(4, N, ROUNDS, 0) <= 40 * 1024 ? 1 : 2)
 // ---- launchers (defined next to their kernels) ----
 hipError_t sg_launch_chain(const SgPhaseArgs& p, int nenv, hipStream_t s);
 // the main pass over all envs and, when genpass, the general contact pass behind it (SG_GEN_GRID blocks striding over the listed envs; sg_general.h)
 hipError_t sg_launch_phase(const SgPhaseArgs& p, int rounds, bool nb, bool genpass, int nenv, hipStream_t s);
 hipError_t sg_rows_prepare();                 // once per device: dynamic-LDS limits of every solver instantiation
-int sg_rows_nsl(int nelem);                   // the instantiated joint-fix rows per lane (template parameter NSL) that holds nelem
 hipError_t sg_launch_rows(const SgPgsArgs& a, int nsl, int nb /* 0 | 1 | 2: template parameter NB of sg_pgs_rows_kernel */, int epw, int nenv, size_t lds_bytes, hipStream_t s);
 #ifdef SG_LEGACY_PIPELINES   // test builds only (build_native.py --legacy): r01's fused kernel and the split pipeline's stream-per-lane solver
 struct SgKArgs;

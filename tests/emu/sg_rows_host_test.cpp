@@ -1,12 +1,13 @@
-// Host test of the rows pipeline's host side (soft-grip_amd/csrc/sg_rows_host.h) against the rules by which the KERNELS index what it
+// Host test of the rows pipeline's host side (soft-grip_amd/csrc/sg_rows_host.h) by the rules by which the KERNELS index what it
 // makes; tests/test_rows_host.py builds this with the host sanitizers (address, undefined), runs it over the committed two-finger
 // models and holds its digest lines against tests/golden/rows_host_digests.json.
 //   usage: sg_rows_host_test MODEL.sgmodel...
 // Per model one digest line -- FNV-1a hashes and lengths of the padded schedule, the table and cpos, and every work-space count at
 // 1, 9 and 4096 envs -- then the checks, at 1, 3, 4, 5, 8 and 9 envs (where (n + 3) / 4, (n + 7) / 8 and the ragged last wavefront
-// differ).  The table, an env's LDS arrays and every work-space buffer are heap blocks of exactly the size sg_rows_host.h gives, and
-// every address a kernel forms is READ from them: under the sanitizer an index outside a block stops the program.  The decode rules
-// below are written from the kernels' text (sg_rows.hip adr_of and row0, sg_phase.hip's store of the step factors), not shared with the packer.
+// differ).  The table, the solver's LDS block and every work-space buffer are heap blocks of exactly the size sg_rows_host.h gives, and
+// every address a kernel forms is READ from them: under the sanitizer an index outside a block stops the program.  The index rules are
+// sg_rows_layout.h's functions, the ones the kernels call (adr_of, row0 and load_row of sg_rows.hip, the exports of sg_phase.hip); what is
+// stated here on its own is what the kernels NEED of each region -- how many words of which size they put there.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -88,42 +89,91 @@ static void digest_line(const std::string& label, const SgPlan& P, int rounds) {
   std::printf("\n");
 }
 
-// 1. the table decodes back to the schedule, by the kernel's rule, into an env's LDS arrays
-static void check_tables(const std::string& label, const SgPlan& P, const SgRowsShape& sh, const SgRowsTables& T) {
+// 0. layouts that depend on no model: the contact row's fields and the chain hand-off record
+static void check_static_layouts() {
+  int slot[SG_RK] = {};
+  for (int k = 0; k < SG_RK; k++) {
+    const int pr = sg_row_pair(k), h = sg_row_half(k);
+    CHECK(pr >= 0 && pr < SG_RK / 2 && (h == 0 || h == 1), "field %d: pair %d half %d", k, pr, h);
+    if (pr >= 0 && pr < SG_RK / 2 && (h == 0 || h == 1)) slot[2 * pr + h]++;
+    CHECK(sg_row_imm(k) == (pr - SG_ROW_BASE_PAIR) * 64 && SG_ROW_INDEX(0, 0, k, 0, 1) == (size_t)(128 * pr + h), "field %d: immediate %d", k, sg_row_imm(k));
+  }
+  for (int q = 0; q < SG_RK; q++) CHECK(slot[q] == 1, "slot %d of a contact row holds %d fields", q, slot[q]);
+  int cell[SG_CHW] = {};
+  for (const SgHandoffField& f : SG_HANDOFF_FIELDS)
+    for (int j = f.off; j < f.off + f.len; j++) {
+      CHECK(j >= 0 && j < SG_CHW, "hand-off field at %d leaves the record", f.off);
+      if (j >= 0 && j < SG_CHW) cell[j]++;
+    }
+  static_assert(SGH_END == SGH_LIMF + SG_MAXLIM, "the limit rows' forces end the record");
+  for (int j = 0; j < SG_CHW; j++) CHECK(cell[j] == (j < SGH_END ? 1 : 0), "hand-off word %d belongs to %d fields", j, cell[j]);
+}
+
+// 1. the solver's LDS block: the regions' starts off[0 .. nregion - 1] in order, what the kernel puts into each (`need`) ending before the next
+// begins, the last region's end off[nregion] at lds_doubles.  Returns a block of exactly that size.
+static double* lds_block(Heap& heap, const std::string& label, int nregion, const size_t* off, const size_t* need, size_t total) {
+  CHECK(off[0] == 0 && off[nregion] == total, "%s: the LDS regions end at %zu of %zu doubles", label.c_str(), off[nregion], total);
+  for (int r = 0; r < nregion; r++)
+    CHECK(need[r] > 0 && off[r] + need[r] <= off[r + 1], "%s: LDS region %d at %zu, the kernel needs %zu, next at %zu", label.c_str(), r, off[r], need[r], off[r + 1]);
+  double* lds = nullptr;
+  heap(&lds, total);
+  double sum = 0;
+  for (int r = 0; r < nregion; r++) sum += lds[off[r]] + lds[off[r] + need[r] - 1];
+  CHECK(sum == 0.0, "read words");
+  return lds;
+}
+static void check_lds_fix(const std::string& label, const SgRowsShape& sh, int epw, int nsl) {
+  const int NR = 8 * nsl;
+  const size_t z = 0, oBR = SG_LDS_FIX_BR(z, epw, NR), oRI = SG_LDS_FIX_RI(oBR, epw, NR), oIC = SG_LDS_FIX_IC(oRI, epw, NR), oZ = SG_LDS_FIX_ZERO(oIC, NR);
+  const size_t off[6] = {z, oBR, oRI, oIC, oZ, SG_LDS_FIX_END(oZ)};
+  // AF, BR: a pair per env and row; RI: a word; IC: a pair per row; the zero word and 64 sink words
+  const size_t need[5] = {(size_t)2 * epw * NR, (size_t)2 * epw * NR, (size_t)epw * NR, (size_t)2 * NR, 65};
+  Heap heap;
+  lds_block(heap, label + " epw " + std::to_string(epw), 5, off, need, sh.lds_doubles(epw, nsl));
+  CHECK(NR >= sh.nelem, "%s: %d rows for %d elements", label.c_str(), NR, sh.nelem);
+}
+
+// ... of a neighbour-row model, and 2. the table decodes back to the schedule, by the kernel's rule, into that block
+static void check_tables(const std::string& label, const SgPlan& P, const SgRowsShape& sh, const SgRowsTables& T, int epw) {
   const SgPlanHeader& H = P.h;
   const int N = H.nelem, R = H.eq_rounds;
   const bool cst = sh.nb_mode == 2;
   CHECK(T.sched.size() == (size_t)(R + 8) * SG_EQ_SLOTS && P.sched.size() == (size_t)R * SG_EQ_SLOTS, "%s: %zu slots", label.c_str(), T.sched.size());
   CHECK(T.tab.size() == sh.tab_words, "%s: %zu table words, the kernel stages %zu", label.c_str(), T.tab.size(), sh.tab_words);
-  // the kernel's LDS block at 4 envs per wavefront: sliders [4][NA] | row records [4][(4 | 8) (N + 1)] | table | 72 + 2 * 4 doubles
-  const size_t NA = SG_ROWS_NA_NB(N), GW = (size_t)(cst ? 4 : 8) * (N + 1), tabd = (size_t)(cst ? 8 : 16) * (R + 8);
-  CHECK(sh.lds_doubles(4, 0) == 4 * NA + 4 * GW + tabd + 72 + 8 && sh.lds_doubles(4, 0) == SG_ROWS_LDS_NB(4, N, R, cst), "%s: LDS of %zu doubles", label.c_str(),
-        sh.lds_doubles(4, 0));
-  CHECK(sizeof(unsigned) * T.tab.size() == sizeof(double) * tabd, "%s: the table fills its LDS region", label.c_str());
-  CHECK(sizeof(double) * sh.lds_doubles(4, 0) <= 160 * 1024, "%s: LDS", label.c_str());
+  const size_t z = 0, oGS = SG_LDS_NB_GS(z, epw, N), oTAB = SG_LDS_NB_TAB(oGS, epw, N, cst), oZ = SG_LDS_NB_ZERO(oTAB, R, cst), oENV = SG_LDS_NB_ENV(oZ);
+  const size_t off[6] = {z, oGS, oTAB, oZ, oENV, SG_LDS_NB_END(oENV, epw)};
+  // per env N sliders and the zero word | per env N + 1 groups of four states (8 bytes) or records (16) | the table | the zero word and 64 sink
+  // words | two words per env
+  const size_t NA = SG_ROWS_NA_NB(N), GW = SG_ROWS_GW_NB(N, cst);
+  const size_t need[5] = {(epw - 1) * NA + N + 1, (size_t)epw * (cst ? 4 : 8) * (N + 1), T.tab.size() * sizeof(unsigned) / sizeof(double), 65, (size_t)2 * epw};
+  CHECK(NA >= (size_t)N + 1 && NA % 2 == 0 && sizeof(unsigned) * T.tab.size() == sizeof(double) * (oZ - oTAB), "%s: slider words %zu, table region %zu", label.c_str(), NA, oZ - oTAB);
+  CHECK(sizeof(double) * sh.lds_doubles(epw, 0) <= 160 * 1024, "%s: LDS", label.c_str());
   Heap heap;
+  double* const lds = lds_block(heap, label + " epw " + std::to_string(epw), 5, off, need, sh.lds_doubles(epw, 0));
   const unsigned* tab = heap.copy(T.tab);
-  double *Ae = nullptr, *GS = nullptr;
-  heap(&Ae, NA); heap(&GS, GW);
   double sum = 0;
-  for (size_t i = 0; i < T.sched.size(); i++) {
-    const SgEqSlot& sl = T.sched[i];
-    const size_t round = i / SG_EQ_SLOTS, b = i % SG_EQ_SLOTS;
-    if (i >= P.sched.size()) CHECK(sl.e == N && sl.p[0] == N && sl.p[1] == N && sl.p[2] == N, "%s: spare slot %zu is not idle", label.c_str(), i);
-    CHECK(sl.e >= 0 && sl.e <= N, "%s: slot %zu element %d", label.c_str(), i, sl.e);
-    for (int h = 0; h < 2; h++) {
-      const size_t g = 2 * b + h, t = round * 16 + g;   // the lane's word (pair) of the round: TAB + g, + 16 per round
-      unsigned px, py, rec;
-      if (cst) { const unsigned tt = tab[t]; px = tt & 0x7ffu; py = (tt >> 11) & 0x7ffu; rec = (tt >> 22) << 4; }
-      else { const unsigned x = tab[2 * t], y = tab[2 * t + 1]; px = x & 0xffffu; py = x >> 16; rec = y; }
-      const int want_x = h ? sl.p[1] : sl.e, want_y = h ? sl.p[2] : sl.p[0];
-      CHECK(px == 8u * want_x && py == 8u * want_y, "%s: slot %zu h %d decodes to sliders %u %u, wanted %d %d", label.c_str(), i, h, px / 8, py / 8, want_x, want_y);
-      // the lane's rows 2 h, 2 h + 1 of group e: states of 8 bytes (streamed factors) or records (g, c) of 16
-      const unsigned want_rec = (cst ? 8u : 16u) * (4u * sl.e + 2u * h);
-      CHECK(rec == want_rec && rec % 16 == 0, "%s: slot %zu h %d row states at byte %u, wanted %u", label.c_str(), i, h, rec, want_rec);
-      CHECK(px % 8 == 0 && py % 8 == 0 && px + 8 <= 8 * NA && py + 8 <= 8 * NA && rec + (cst ? 16 : 32) <= 8 * GW, "%s: slot %zu h %d leaves its LDS region", label.c_str(), i, h);
-      sum += *(const double*)((const char*)Ae + px) + *(const double*)((const char*)Ae + py);
-      for (unsigned k = 0; k < (cst ? 2u : 4u); k++) sum += ((const double*)((const char*)GS + rec))[k];
+  for (int le = 0; le < epw; le += epw - 1) {   // the first and the last env of the wavefront
+    const char* const Ae = (const char*)(lds + (size_t)le * NA);
+    const char* const GS = (const char*)(lds + oGS + (size_t)le * GW);
+    for (size_t i = 0; i < T.sched.size(); i++) {
+      const SgEqSlot& sl = T.sched[i];
+      const size_t round = i / SG_EQ_SLOTS, b = i % SG_EQ_SLOTS;
+      if (i >= P.sched.size()) CHECK(sl.e == N && sl.p[0] == N && sl.p[1] == N && sl.p[2] == N, "%s: spare slot %zu is not idle", label.c_str(), i);
+      CHECK(sl.e >= 0 && sl.e <= N, "%s: slot %zu element %d", label.c_str(), i, sl.e);
+      for (int h = 0; h < 2; h++) {
+        const size_t g = 2 * b + h, t = round * 16 + g;   // the lane's word (pair) of the round: TAB + g, + 16 per round
+        unsigned px, py, rec;
+        if (cst) { const unsigned tt = tab[t]; px = sg_tab1_x(tt); py = sg_tab1_y(tt); rec = sg_tab1_rec(tt); }
+        else { const unsigned x = tab[2 * t], y = tab[2 * t + 1]; px = sg_tab2_x(x); py = sg_tab2_y(x); rec = y; }
+        const int want_x = h ? sl.p[1] : sl.e, want_y = h ? sl.p[2] : sl.p[0];
+        CHECK(px == 8u * want_x && py == 8u * want_y, "%s: slot %zu h %d decodes to sliders %u %u, wanted %d %d", label.c_str(), i, h, px / 8, py / 8, want_x, want_y);
+        // the lane's rows 2 h, 2 h + 1 of group e: states of 8 bytes (streamed factors) or records (g, c) of 16
+        const unsigned want_rec = (cst ? 8u : 16u) * (4u * sl.e + 2u * h);
+        CHECK(rec == want_rec && rec % 16 == 0, "%s: slot %zu h %d row states at byte %u, wanted %u", label.c_str(), i, h, rec, want_rec);
+        CHECK(px % 8 == 0 && py % 8 == 0 && px + 8 <= 8 * NA && py + 8 <= 8 * NA && rec + (cst ? 16 : 32) <= 8 * GW, "%s: slot %zu h %d leaves its LDS region", label.c_str(), i, h);
+        sum += *(const double*)(Ae + px) + *(const double*)(Ae + py);
+        for (unsigned k = 0; k < (cst ? 2u : 4u); k++) sum += ((const double*)(GS + rec))[k];
+      }
     }
   }
   // the deepest words the solver fetches: two rounds past its padded round count (trips of 4 rounds, of 2 with the factors in LDS)
@@ -131,7 +181,7 @@ static void check_tables(const std::string& label, const SgPlan& P, const SgRows
   CHECK(padded + 1 < R + 8, "%s: look-ahead past the spare rounds", label.c_str());
   for (size_t w = 0; w < (cst ? 1u : 2u); w++) sum += tab[(cst ? 1 : 2) * ((size_t)(padded + 1) * 16 + 15) + w];
   CHECK(sum >= 0, "read words");
-  // 2. cpos: one place per scheduled element, inside the scheduled rounds
+  // 3. cpos: one place per scheduled element, inside the scheduled rounds
   CHECK(T.cpos.size() == (size_t)N, "%s: cpos of %zu", label.c_str(), T.cpos.size());
   std::set<int> seen, elems;
   for (size_t i = 0; i < P.sched.size(); i++) {
@@ -143,7 +193,7 @@ static void check_tables(const std::string& label, const SgPlan& P, const SgRows
   CHECK((int)elems.size() == N, "%s: %zu of %d elements scheduled", label.c_str(), elems.size(), N);
 }
 
-// 2 (per env) and 3: the kernels' addresses into the work space of an n-env batch
+// 3 (per env) and 4: the kernels' addresses into the work space of an n-env batch
 static void check_work(const std::string& label, const SgPlan& P, int rounds, const SgRowsShape& sh, const SgRowsTables& T, int n) {
   const SgPlanHeader& H = P.h;
   const int R = H.eq_rounds, nwb = (n + 7) / 8;
@@ -160,25 +210,29 @@ static void check_work(const std::string& label, const SgPlan& P, int rounds, co
       for (int k = 0; k < SG_RK; k++)
         for (int lane = 0; lane < 64; lane += (slot == 0 || slot == SG_CAP + 1 || wave >= nwb - 1) ? 1 : 63) sum += w.crow[SG_ROW_INDEX(slot, wave, k, lane, nwb)];
   CHECK(SG_ROW_INDEX(SG_CAP + 1, nwb + 1, SG_RK - 1, 63, nwb) + 1 == crow_n, "%s n %d: crow of %zu", label.c_str(), n, crow_n);
-  // a lane's column as the solver forms it (row0, biased by 4 field pairs; immediate offsets -4 .. 3 pairs; slot stride in double2)
-  for (int env = 0; env < n; env++)
-    for (int g = 0; g < 8; g++) {
-      const double* const row0 = w.crow + SG_ROW_INDEX(0, env >> 3, 8, 8 * (env & 7) + g, nwb);
-      const ptrdiff_t slot_stride = (ptrdiff_t)(nwb + 2) * (SG_RK / 2) * 64 * 2;
-      for (int slot : {0, SG_CAP - 1})
-        for (int p = -4; p < 4; p++) sum += row0[slot * slot_stride + p * 128] + row0[slot * slot_stride + p * 128 + 1];
-    }
-  // the private zero block of a wavefront's lanes without an env: 4 envs per wavefront, and 8 where the model has no neighbour rows
+  // a lane's column as the solver forms it: row0 (biased to SG_ROW_BASE_PAIR), a slot stride in 16-byte units, the field pairs by their
+  // immediates -- every slot of the buffer, SG_CAP + 1 included, at 4 envs per wavefront and, where the model has no neighbour rows, at 8.
+  // The env slots of the ragged last wavefront and the lanes outside the finger quads stay on their wavefront's private zero block
   for (int epw : {4, 8}) {
     if (epw == 8 && sh.nb_mode) continue;
+    const int lpe = sh.nb_mode ? 16 : 8;   // lanes per env
     for (int blk = 0; blk < (n + epw - 1) / epw; blk++)
-      for (int lane = 0; lane < 64; lane++)
-        for (int p = -4; p < 4; p++) {
-          const double* const q = w.cdummy + (((ptrdiff_t)blk * (SG_RK / 2) + 4) * 128 + 2 * lane + p * 128);
-          sum += q[0] + q[1];
-        }
+      for (int lane = 0; lane < 64; lane++) {
+        const int le = lane / lpe, g = lane % lpe, env = blk * epw + le;
+        const bool has_row = le < epw && env < n && g < 8;
+        const size_t row0 = has_row ? SG_ROW_INDEX(0, env >> 3, 2 * SG_ROW_BASE_PAIR, 8 * (env & 7) + g, nwb) : sg_row_dummy_index((size_t)blk, SG_ROW_BASE_PAIR) + 2 * lane;
+        const size_t stride = has_row ? 2 * sg_row_slot_stride(nwb) : 0, count = has_row ? crow_n : cdummy_n;
+        const double* const base = has_row ? w.crow : w.cdummy;
+        for (int slot = 0; slot < SG_CAP + 2; slot++)
+          for (int k = 0; k < SG_RK; k++) {
+            const ptrdiff_t at = (ptrdiff_t)(row0 + slot * stride) + 2 * sg_row_imm(k) + sg_row_half(k);
+            CHECK(at >= 0 && (size_t)at < count, "%s n %d epw %d block %d lane %d slot %d field %d: word %td of %zu", label.c_str(), n, epw, blk, lane, slot, k, at, count);
+            if (at >= 0 && (size_t)at < count) sum += base[at];
+            if (has_row) CHECK((size_t)at == SG_ROW_INDEX(slot, env >> 3, k, 8 * (env & 7) + g, nwb), "%s n %d: the solver's field %d of slot %d is not the exporter's", label.c_str(), n, k, slot);
+          }
+      }
   }
-  CHECK((((size_t)((n + 3) / 4 - 1) * (SG_RK / 2) + 7) * 128 + 2 * 63 + 2) == cdummy_n, "%s n %d: cdummy of %zu", label.c_str(), n, cdummy_n);
+  CHECK(sg_row_dummy_index((size_t)((n + 3) / 4 - 1), SG_RK / 2 - 1) + 2 * 63 + 2 == cdummy_n, "%s n %d: cdummy of %zu", label.c_str(), n, cdummy_n);
   if (sh.nb_mode == 2) {
     // the stream of step factors: what the solver's lanes read, up to its deepest prefetched round (the first four rounds, then four ahead
     // inside the padded round count)
@@ -208,6 +262,7 @@ static void check_work(const std::string& label, const SgPlan& P, int rounds, co
 
 int main(int argc, char** argv) {
   int accepted = 0;
+  check_static_layouts();
   for (int a = 1; a < argc; a++) {
     const std::string path = argv[a], label = path.substr(path.find_last_of('/') + 1);
     std::ifstream f(path, std::ios::binary);
@@ -223,10 +278,12 @@ int main(int argc, char** argv) {
     const SgRowsShape sh = sg_rows_shape(P.h);
     CHECK(sh.nb_mode == (P.h.nnb > 0 ? SG_ROWS_NB_MODE(P.h.nelem, P.h.eq_rounds) : 0) && sh.two_words == (sh.nb_mode == 1), "%s: mode %d", label.c_str(), sh.nb_mode);
     SgRowsTables T;
-    if (sh.nb_mode) {
-      sg_rows_tables(P, &T);
-      check_tables(label, P, sh, T);
-    } else CHECK(sh.tab_words == 0 && sh.cst_rounds == 0 && sh.lds_doubles(8, 14) == SG_ROWS_LDS_FIX(8, 112), "%s: shape without neighbour rows", label.c_str());
+    if (sh.nb_mode) sg_rows_tables(P, &T);
+    else CHECK(sh.tab_words == 0 && sh.cst_rounds == 0, "%s: shape without neighbour rows", label.c_str());
+    for (int epw : {4, 8}) {   // (the kernel runs a neighbour-row model at 4 only; its carve holds at 8 all the same)
+      if (sh.nb_mode) check_tables(label, P, sh, T, epw);
+      else check_lds_fix(label, sh, epw, sg_rows_nsl(P.h.nelem));
+    }
     for (int n : {1, 3, 4, 5, 8, 9}) check_work(label, P, rounds, sh, T, n);
     std::printf("checked %s: mode %d, %d elements, %d rounds\n", label.c_str(), sh.nb_mode, P.h.nelem, P.h.eq_rounds);
   }

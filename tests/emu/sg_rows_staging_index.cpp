@@ -1,4 +1,4 @@
-// Host check of the index rules by which the phase kernel hands the equality block to the rows solver (soft-grip_amd/csrc/sg_work.h:
+// Host check of the index rules by which the phase kernel hands the equality block to the rows solver (soft-grip_amd/csrc/sg_rows_layout.h:
 // sg_eq_fix_index, sg_eq_nb_index for the writer; sg_eq_rec_trips, sg_eq_rec_row, sg_eq_rec_stored, sg_eq_rec_live, sg_eq_rec_index for the
 // solver's staging trips), over the committed two-finger models at 1, 5 and 9 envs.
 //   usage: sg_rows_staging_index MODEL.sgmodel...
@@ -46,13 +46,6 @@ struct Heap {
   }
 };
 
-// the solver's instantiated rows per lane (sg_rows.hip: sg_rows_nsl, written again here: the launcher is device code's neighbour)
-static int rows_nsl(int nelem) {
-  for (int v : {8, 14, 20, 26, 29, 32})
-    if (v * 8 >= nelem) return v;
-  return 32;
-}
-
 static void check_model(const std::string& label, const SgPlanHeader& H, int rounds, int n) {
   const int N = H.nelem;
   Heap heap;
@@ -87,7 +80,7 @@ static void check_model(const std::string& label, const SgPlanHeader& H, int rou
     for (size_t q = 0; q < (size_t)n * 3 * N && q < nb_n; q++) CHECK(nb_seen[q], "%s n %d: neighbour word %zu is nobody's (not dense)", label.c_str(), n, q);
   if (H.nnb == 0) { CHECK(sum == (double)reads, "%s n %d: read words", label.c_str(), n); return; }
   // ---- the solver: four env slots per wavefront, trips of 64 lanes over the padded row count of its instantiation
-  const int NR = 8 * rows_nsl(N), trips = sg_eq_rec_trips(NR);
+  const int NR = 8 * sg_rows_nsl(N), trips = sg_eq_rec_trips(NR);
   CHECK(NR >= N && 64 * trips >= 4 * (N + 1), "%s: %d trips for %d elements", label.c_str(), trips, N);
   for (int wave = 0; wave < (n + 3) / 4; wave++)
     for (int e2 = 0; e2 < 4; e2++) {
@@ -130,7 +123,7 @@ int main(int argc, char** argv) {
     if (!sg_plan_build(blob.data(), blob.size(), &P, &err)) { std::printf("%s: refused: %s\n", label.c_str(), err.c_str()); return 1; }
     const int rounds = (P.h.nelem + 63) / 64;
     for (int n : {1, 5, 9}) check_model(label, P.h, rounds, n);
-    std::printf("checked %s: %d elements, %d neighbour rows, %d trips\n", label.c_str(), P.h.nelem, P.h.nnb, P.h.nnb > 0 ? sg_eq_rec_trips(8 * rows_nsl(P.h.nelem)) : 0);
+    std::printf("checked %s: %d elements, %d neighbour rows, %d trips\n", label.c_str(), P.h.nelem, P.h.nnb, P.h.nnb > 0 ? sg_eq_rec_trips(8 * sg_rows_nsl(P.h.nelem)) : 0);
     models++;
   }
   std::printf(fails ? "FAILED (%d)\n" : "PASS %d models\n", fails ? fails : models);

@@ -1,4 +1,4 @@
-"""The solver of a neighbour-row model takes its equality rows READY from the phase kernel (soft-grip_amd/csrc/sg_work.h: sg_eq_fix_index,
+"""The solver of a neighbour-row model takes its equality rows READY from the phase kernel (soft-grip_amd/csrc/sg_rows_layout.h: sg_eq_fix_index,
 sg_eq_nb_index -- per row the state g = b + R f and the step factor c, element-major) and stages them, the slider words, the table and the
 per-stream values in one batch of unconditional loads (sg_rows.hip: the prologue).  The runs below are chosen for what that staging has to
 get right, each against the CPU oracle at tests/test_gpu_parity.py's tolerances -- qpos 1e-9, qvel 1e-7, ncon and sweeps equal:

@@ -1,5 +1,5 @@
 """The index rules by which the phase kernel hands the equality block of a neighbour-row model to the rows solver ready-made
-(soft-grip_amd/csrc/sg_work.h: sg_eq_fix_index, sg_eq_nb_index; the solver's staging trips: sg_eq_rec_*), on the host:
+(soft-grip_amd/csrc/sg_rows_layout.h: sg_eq_fix_index, sg_eq_nb_index; the solver's staging trips: sg_eq_rec_*), on the host:
 tests/emu/sg_rows_staging_index.cpp includes the headers and checks, for the committed two-finger models at 1, 5 and 9 envs, that every
 (env, e, d) index lies inside the count sg_rows_work_each enumerates and that the indices are distinct, that the solver's lane mapping over
 its record trips reaches each of an env's 4 (N + 1) rows exactly once with group N zero, and that the clamped addresses of the lanes
