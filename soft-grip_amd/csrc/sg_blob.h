@@ -1,5 +1,5 @@
-// sg_blob.h -- the one reader of the model blob (include/softgrip_model.h).  Host only, no HIP: sg_plan.cpp, sg_readout.hip
-// and the g++ builds under tests/emu and scripts/sanitize all read blobs through it.
+// sg_blob.h -- the one reader of the model blob (include/softgrip_model.h) and its schema SG_MODEL_ARRAYS, which sg_mjcf.cpp writes from.
+// Host only, no HIP: sg_plan.cpp, sg_readout.hip and the g++ builds under tests/emu and scripts/sanitize all read blobs through it.
 //   sg_blob_valid   magic, version, total_bytes == nbytes, and every one of the nrec records with its padded payload inside the buffer
 //   sg_blob_find    the array (name, dtype): pointer and count.  Checks every record it walks on its own, so it is safe on bytes nobody
 //                   validated: it never reads outside [blob, blob + nbytes)
@@ -53,13 +53,16 @@ inline const void* sg_blob_find(const void* blob, size_t nbytes, const char* nam
   return sg_blob_walk(blob, nbytes, name, dtype, &data, cnt) ? data : nullptr;
 }
 
-// The arrays of the plan builder: X(type, name, items per entry, dimension, part).  The FIRST array of a dimension defines it
-// (count / items), every later one must have items x dimension entries.  `part`: sg_model_view resolves the table in three parts, because
-// the plan builder's checks of the free joint and of the position / dof counts sit between them and refusals keep their order.
+// The blob's schema: every array of a model blob in the container's order (the `names` record follows them).  The native MJCF compiler
+// (sg_mjcf.cpp) writes from this table, sg_model_view reads from it.  The FIRST array of a dimension defines it (count / items), every
+// later one must have items x dimension entries (sg_model_count_fits).
+//   X(type, name, items per entry, dimension, part): read by the plan builder.  sg_model_view resolves the table in three parts, because
+//   the builder's checks of the free joint and of the position / dof counts sit between them and refusals keep their order.
+//   W(type, name, items per entry, dimension, free_only): written only, sg_model_view skips it.  free_only: only blobs with a free joint
+//   carry it (only then do joint, position and dof indices differ).
 //   Relaxed entries (dimension `none`: at least `items` entries): opt_d, and opt_i, which has grown over time (implicit_tendon_damping
-//   is an optional 4th entry; the builder reads it only when n_opt_i says it is there).  The optional jnt_qposadr / jnt_dofadr /
-//   dof_jntid (only blobs with a free joint carry them) are not read by the builder and not listed.
-#define SG_MODEL_ARRAYS(X)                                                                                                                   \
+//   is an optional 4th entry; the builder reads it only when n_opt_i says it is there).
+#define SG_MODEL_ARRAYS(X, W)                                                                                                                \
   X(double, opt_d, 7, none, 0) X(int, opt_i, 1, none, 0)                                                                                     \
   X(double, body_pos, 3, nbody, 0) X(double, body_quat, 4, nbody, 0) X(double, body_ipos, 3, nbody, 0) X(double, body_imat, 9, nbody, 0)     \
   X(double, body_mass, 1, nbody, 0) X(double, body_invweight0, 2, nbody, 0) X(double, jnt_pos, 3, njnt, 0)                                   \
@@ -76,22 +79,34 @@ inline const void* sg_blob_find(const void* blob, size_t nbytes, const char* nam
   X(double, actuator_timeconst, 1, nu, 2) X(double, actuator_gain, 1, nu, 2) X(double, actuator_bias, 3, nu, 2)                              \
   X(double, actuator_gear, 1, nu, 2)                                                                                                         \
   X(int, body_parentid, 1, nbody, 2) X(int, body_weldid, 1, nbody, 2) X(int, body_jntadr, 1, nbody, 2) X(int, body_jntnum, 1, nbody, 2)      \
-  X(int, body_geomadr, 1, nbody, 2) X(int, body_geomnum, 1, nbody, 2) X(int, jnt_type, 1, njnt, 2) X(int, jnt_limited, 1, njnt, 2)           \
+  X(int, body_geomadr, 1, nbody, 2) X(int, body_geomnum, 1, nbody, 2)                                                                        \
+  X(int, jnt_type, 1, njnt, 2) W(int, jnt_bodyid, 1, njnt, 0) X(int, jnt_limited, 1, njnt, 2) W(int, dof_parentid, 1, nv, 0)                 \
   X(int, geom_type, 1, ngeom, 2) X(int, geom_bodyid, 1, ngeom, 2) X(int, geom_contype, 1, ngeom, 2) X(int, geom_conaffinity, 1, ngeom, 2)    \
   X(int, geom_condim, 1, ngeom, 2) X(int, geom_priority, 1, ngeom, 2) X(int, site_bodyid, 1, nsite, 2)                                       \
   X(int, tendon_adr, 1, ntendon, 2) X(int, tendon_num, 1, ntendon, 2) X(int, wrap_type, 1, nwrap, 2) X(int, wrap_objid, 1, nwrap, 2)         \
   X(int, eq_type, 1, neq, 2) X(int, eq_obj1id, 1, neq, 2) X(int, eq_obj2id, 1, neq, 2) X(int, actuator_trnid, 1, nu, 2)                      \
-  X(int, sensor_type, 1, nsensor, 2) X(int, sensor_objid, 1, nsensor, 2) X(int, sensor_adr, 1, nsensor, 2)
+  X(int, sensor_type, 1, nsensor, 2) X(int, sensor_objid, 1, nsensor, 2) X(int, sensor_adr, 1, nsensor, 2)                                   \
+  W(int, jnt_qposadr, 1, njnt, 1) W(int, jnt_dofadr, 1, njnt, 1) W(int, dof_jntid, 1, nv, 1)
+#define SG_SKIP(type, name, per, dim, free_only)
 
-struct SgModelView {
-  const void* blob = nullptr;
-  size_t nbytes = 0;
-  // dimensions (-1 until their first array is resolved): njnt joints, nq positions, nv dofs, nwrap tendon wrap objects
+// the table's dimensions (-1 until their first array defines them): njnt joints, nq positions, nv dofs, nwrap tendon wrap objects
+struct SgModelDims {
   int nbody = -1, njnt = -1, nq = -1, nv = -1, ngeom = -1, nsite = -1, ntendon = -1, nwrap = -1, neq = -1, nu = -1, nsensor = -1;
   int none = -1;             // (the table's dimension of the relaxed entries)
+};
+// the table's rule for an array of cnt entries, `per` items per entry of dimension *dim: does the count fit?  Defines *dim when it is the first
+inline bool sg_model_count_fits(SgModelDims* D, long long cnt, int per, int* dim) {
+  if (dim == &D->none) return cnt >= per;
+  if (*dim < 0 && cnt % per == 0 && cnt / per <= INT32_MAX) *dim = (int)(cnt / per);
+  return cnt == (long long)per * *dim;
+}
+
+struct SgModelView : SgModelDims {
+  const void* blob = nullptr;
+  size_t nbytes = 0;
   long long n_opt_i = 0;     // entries of opt_i
 #define SG_X(type, name, per, dim, part) const type* name = nullptr;
-  SG_MODEL_ARRAYS(SG_X)
+  SG_MODEL_ARRAYS(SG_X, SG_SKIP)
 #undef SG_X
 };
 
@@ -102,10 +117,7 @@ inline bool sg_model_array(SgModelView* V, const char* name, int dtype, int per,
     if (err) *err = std::string("model blob lacks ") + name;
     return false;
   }
-  if (dim == &V->none ? cnt >= per : *dim < 0 ? cnt % per == 0 && cnt / per <= INT32_MAX : cnt == (long long)per * *dim) {
-    if (dim != &V->none && *dim < 0) *dim = (int)(cnt / per);
-    return true;
-  }
+  if (sg_model_count_fits(V, cnt, per, dim)) return true;
   if (err) *err = std::string("model blob: ") + name + " has " + std::to_string(cnt) + " entries, which does not fit the model's dimensions";
   return false;
 }
@@ -118,7 +130,7 @@ inline bool sg_model_view(SgModelView* V, int part, std::string* err) {
     if (!sg_model_array(V, #name, sizeof(type) == 8 ? SG_DT_F64 : SG_DT_I32, per, &V->dim, &p, err)) return false;                         \
     V->name = (const type*)p;                                                                                                              \
   }
-  SG_MODEL_ARRAYS(SG_X)
+  SG_MODEL_ARRAYS(SG_X, SG_SKIP)
 #undef SG_X
   if (part == 0) sg_blob_find(V->blob, V->nbytes, "opt_i", SG_DT_I32, &V->n_opt_i);
   return true;

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/softgrip_model.h"
+#include "sg_blob.h"
 #include "sg_mjcf.h"
 
 namespace {
@@ -717,74 +718,70 @@ void geom_volume_inertia(const Geom& g, double* vol, double* Id) {  // per-unit-
 }
 
 // ------------------------------------------------------------------------------------------------ flat model + blob
-struct Flat {
-  std::vector<std::pair<std::string, std::vector<double>>> f64;
-  std::vector<std::pair<std::string, std::vector<int32_t>>> i32;
-  std::vector<double>& F(const char* n) { f64.emplace_back(n, std::vector<double>()); return f64.back().second; }
-  std::vector<int32_t>& I(const char* n) { i32.emplace_back(n, std::vector<int32_t>()); return i32.back().second; }
+// The blob's arrays, one vector per row of its schema SG_MODEL_ARRAYS (sg_blob.h): filled by the stages below, checked and written by write_blob()
+struct Arrays {
+#define SG_X(type, name, per, dim, part) std::vector<type> name;
+  SG_MODEL_ARRAYS(SG_X, SG_X)
+#undef SG_X
+};
+// The flattened tree: the joints, geoms and sites of all bodies in body order, and the model's dimensions as the table names them (nwrap
+// stays open: the wrap arrays grow with the tendons).  The adr / num arrays and the joints' position and dof addresses are rows of Arrays.
+template <class O> struct Ref { int body; const O* o; };
+struct Tree {
+  std::vector<Ref<Joint>> joints; std::vector<Ref<Geom>> geoms; std::vector<Ref<Site>> sites;
+  SgModelDims n;
+  bool has_free = false;
 };
 
-void put_record(std::string& out, const std::string& name, uint32_t code, int64_t count, const void* data, size_t nbytes) {
-  if (name.size() > 23) fail("field name too long: " + name);
-  sg_blob_record r;
-  memset(&r, 0, sizeof r);
-  memcpy(r.name, name.data(), name.size());
-  r.dtype = code; r.count = count;
-  out.append((const char*)&r, sizeof r);
-  out.append((const char*)data, nbytes);
-  out.append((8 - nbytes % 8) % 8, '\0');
-}
-
-std::string join(const std::vector<std::string>& v) {
-  std::string o;
-  for (size_t i = 0; i < v.size(); i++) { if (i) o += '|'; o += v[i]; }
-  return o;
-}
-
-std::string finalize(Compiler& C, bool implicit_tendon_damping) {
-  std::vector<Body>& B = C.bodies;
+// numbering: the bodies' children flattened, weld ids, joint -> first position / first dof (a free joint: 7 / 6), dof -> joint, dof parents
+void number_tree(const Compiler& C, Arrays& A, Tree& T) {
+  const std::vector<Body>& B = C.bodies;
   const int nbody = (int)B.size();
-  std::vector<int> body_jntadr(nbody), body_jntnum(nbody), body_geomadr(nbody), body_geomnum(nbody), body_weldid(nbody, 0), body_parentid(nbody);
-  struct JRef { int body; const Joint* j; };
-  struct GRef { int body; const Geom* g; };
-  struct SRef { int body; const Site* s; };
-  std::vector<JRef> joints; std::vector<GRef> geoms; std::vector<SRef> sites;
+  A.body_weldid.assign(nbody, 0);
   for (int i = 0; i < nbody; i++) {
-    body_parentid[i] = B[i].parent > 0 ? B[i].parent : 0;
-    body_jntadr[i] = B[i].joints.empty() ? -1 : (int)joints.size();
-    body_jntnum[i] = (int)B[i].joints.size();
-    body_geomadr[i] = B[i].geoms.empty() ? -1 : (int)geoms.size();
-    body_geomnum[i] = (int)B[i].geoms.size();
-    for (auto& j : B[i].joints) joints.push_back({i, &j});
-    for (auto& g : B[i].geoms) geoms.push_back({i, &g});
-    for (auto& s : B[i].sites) sites.push_back({i, &s});
+    A.body_parentid.push_back(B[i].parent > 0 ? B[i].parent : 0);
+    A.body_jntadr.push_back(B[i].joints.empty() ? -1 : (int)T.joints.size());
+    A.body_jntnum.push_back((int)B[i].joints.size());
+    A.body_geomadr.push_back(B[i].geoms.empty() ? -1 : (int)T.geoms.size());
+    A.body_geomnum.push_back((int)B[i].geoms.size());
+    for (auto& j : B[i].joints) T.joints.push_back({i, &j});
+    for (auto& g : B[i].geoms) T.geoms.push_back({i, &g});
+    for (auto& s : B[i].sites) T.sites.push_back({i, &s});
   }
-  const int nj = (int)joints.size(), ng = (int)geoms.size(), ns = (int)sites.size();
-  for (int i = 1; i < nbody; i++) body_weldid[i] = B[i].joints.empty() ? body_weldid[B[i].parent] : i;
-  // joint -> first position / first dof (a free joint: 7 / 6), dof -> joint
-  std::vector<int> jnt_qposadr(nj), jnt_dofadr(nj), dof_jntid;
+  const int nj = (int)T.joints.size();
+  for (int i = 1; i < nbody; i++) A.body_weldid[i] = B[i].joints.empty() ? A.body_weldid[B[i].parent] : i;
   int nq = 0;
-  bool has_free = false;
   for (int k = 0; k < nj; k++) {
-    const bool fr = joints[k].j->type == SG_JNT_FREE;
-    has_free = has_free || fr;
-    jnt_qposadr[k] = nq; jnt_dofadr[k] = (int)dof_jntid.size();
+    const bool fr = T.joints[k].o->type == SG_JNT_FREE;
+    T.has_free = T.has_free || fr;
+    A.jnt_qposadr.push_back(nq); A.jnt_dofadr.push_back((int)A.dof_jntid.size());
     nq += fr ? 7 : 1;
-    for (int d = 0; d < (fr ? 6 : 1); d++) dof_jntid.push_back(k);
+    for (int d = 0; d < (fr ? 6 : 1); d++) A.dof_jntid.push_back(k);
   }
-  const int nvd = (int)dof_jntid.size();
-  std::vector<int> dof_parentid(nvd, -1), last_dof(nbody, -1);
+  A.dof_parentid.assign(A.dof_jntid.size(), -1);
+  std::vector<int> last_dof(nbody, -1);
   for (int i = 1; i < nbody; i++) {
     int prev = last_dof[B[i].parent];
-    for (int k = 0; k < body_jntnum[i]; k++) {
-      const int jj = body_jntadr[i] + k;
-      for (int d = jnt_dofadr[jj]; d < jnt_dofadr[jj] + (joints[jj].j->type == SG_JNT_FREE ? 6 : 1); d++) { dof_parentid[d] = prev; prev = d; }
+    for (int k = 0; k < A.body_jntnum[i]; k++) {
+      const int jj = A.body_jntadr[i] + k;
+      for (int d = A.jnt_dofadr[jj]; d < A.jnt_dofadr[jj] + (T.joints[jj].o->type == SG_JNT_FREE ? 6 : 1); d++) { A.dof_parentid[d] = prev; prev = d; }
     }
     last_dof[i] = prev;
   }
+  SgModelDims& n = T.n;
+  n.nbody = nbody; n.njnt = nj; n.nq = nq; n.nv = (int)A.dof_jntid.size(); n.ngeom = (int)T.geoms.size(); n.nsite = (int)T.sites.size();
+  n.ntendon = (int)C.tendons.size(); n.neq = (int)C.equalities.size(); n.nu = (int)C.actuators.size(); n.nsensor = (int)C.sensors.size();
+  // every array of a dimension known by now has its size from the table, zero-filled, before the later stages fill it
+#define SG_X(type, name, per, dim, part) if (n.dim >= 0) A.name.resize((size_t)per * n.dim);
+  SG_MODEL_ARRAYS(SG_X, SG_X)
+#undef SG_X
+}
 
-  // inertial properties from the geoms
-  std::vector<double> mass(nbody, 0.0), ipos(3 * nbody, 0.0), imat(9 * nbody, 0.0);
+// inertial properties from the geoms: body_mass, body_ipos, body_imat; <compiler settotalmass>
+void inertia_from_geoms(const Compiler& C, Arrays& A) {
+  const std::vector<Body>& B = C.bodies;
+  const int nbody = (int)B.size();
+  std::vector<double>&mass = A.body_mass, &ipos = A.body_ipos, &imat = A.body_imat;
   for (int i = 0; i < nbody; i++) {
     const auto& G = B[i].geoms;
     std::vector<double> gm(G.size());
@@ -824,127 +821,115 @@ std::string finalize(Compiler& C, bool implicit_tendon_damping) {
     for (auto& v : imat) v *= scale;
   }
   for (int i = 1; i < nbody; i++)
-    if (body_weldid[i] != 0 && body_jntnum[i] > 0 && mass[i] < kMinVal) fail("moving body " + std::to_string(i) + " (" + B[i].name + ") has no mass");
+    if (A.body_weldid[i] != 0 && A.body_jntnum[i] > 0 && mass[i] < kMinVal) fail("moving body " + std::to_string(i) + " (" + B[i].name + ") has no mass");
+}
 
-  // name -> index maps (unnamed objects cannot be referenced)
+// the body, joint (with qpos0, qpos_spring and the dofs' damping and armature), geom and site tables
+void fill_tables(const Compiler& C, Arrays& A, const Tree& T) {
+  const std::vector<Body>& B = C.bodies;
+  const int nbody = T.n.nbody, nj = T.n.njnt, ng = T.n.ngeom, ns = T.n.nsite;
+  for (int i = 0; i < nbody; i++) {
+    for (int a = 0; a < 3; a++) A.body_pos[3 * i + a] = B[i].pos[a];
+    for (int a = 0; a < 4; a++) A.body_quat[4 * i + a] = B[i].quat[a];
+  }
+  for (int k = 0; k < nj; k++) {
+    const Joint& j = *T.joints[k].o;
+    A.jnt_type[k] = j.type; A.jnt_bodyid[k] = T.joints[k].body; A.jnt_limited[k] = j.limited ? 1 : 0;
+    for (int a = 0; a < 3; a++) { A.jnt_pos[3 * k + a] = j.pos[a]; A.jnt_axis[3 * k + a] = j.axis[a]; }
+    A.jnt_range[2 * k] = j.range[0]; A.jnt_range[2 * k + 1] = j.range[1];
+    A.jnt_stiffness[k] = j.stiffness; A.jnt_margin[k] = j.margin;
+    A.jnt_solref[2 * k] = j.solref[0]; A.jnt_solref[2 * k + 1] = j.solref[1];
+    for (int a = 0; a < 5; a++) A.jnt_solimp[5 * k + a] = j.solimp[a];
+    const int qa = A.jnt_qposadr[k], da = A.jnt_dofadr[k];
+    if (j.type == SG_JNT_FREE) {   // the body's pose (a child of the world)
+      const Body& bb = B[T.joints[k].body];
+      for (int a = 0; a < 3; a++) A.qpos0[qa + a] = A.qpos_spring[qa + a] = bb.pos[a];
+      for (int a = 0; a < 4; a++) A.qpos0[qa + 3 + a] = A.qpos_spring[qa + 3 + a] = bb.quat[a];
+      for (int d = 0; d < 6; d++) { A.dof_damping[da + d] = j.damping; A.dof_armature[da + d] = j.armature; }
+    } else {
+      A.qpos0[qa] = j.ref; A.qpos_spring[qa] = j.springref; A.dof_damping[da] = j.damping; A.dof_armature[da] = j.armature;
+    }
+  }
+  for (int k = 0; k < ng; k++) {
+    const Geom& g = *T.geoms[k].o;
+    A.geom_type[k] = g.type; A.geom_bodyid[k] = T.geoms[k].body; A.geom_contype[k] = g.contype; A.geom_conaffinity[k] = g.conaffinity;
+    A.geom_condim[k] = g.condim; A.geom_priority[k] = g.priority;
+    for (int a = 0; a < 3; a++) { A.geom_size[3 * k + a] = g.size[a]; A.geom_pos[3 * k + a] = g.pos[a]; A.geom_friction[3 * k + a] = g.friction[a]; }
+    for (int a = 0; a < 4; a++) A.geom_quat[4 * k + a] = g.quat[a];
+    A.geom_solref[2 * k] = g.solref[0]; A.geom_solref[2 * k + 1] = g.solref[1];
+    for (int a = 0; a < 5; a++) A.geom_solimp[5 * k + a] = g.solimp[a];
+    A.geom_solmix[k] = g.solmix; A.geom_margin[k] = g.margin; A.geom_gap[k] = g.gap;
+    if (g.type == SG_GEOM_SPHERE) A.geom_rbound[k] = g.size[0];
+    else if (g.type == SG_GEOM_CAPSULE) A.geom_rbound[k] = g.size[0] + g.size[1];
+    else if (g.type == SG_GEOM_BOX) A.geom_rbound[k] = norm3(g.size);
+  }
+  for (int k = 0; k < ns; k++) {
+    A.site_bodyid[k] = T.sites[k].body;
+    for (int a = 0; a < 3; a++) A.site_pos[3 * k + a] = T.sites[k].o->pos[a];
+    for (int a = 0; a < 4; a++) A.site_quat[4 * k + a] = T.sites[k].o->quat[a];
+  }
+}
+
+// tendons, equalities, actuators and sensors: their references by name resolved (unnamed objects cannot be referenced)
+void fill_constraints(const Compiler& C, Arrays& A, const Tree& T) {
   std::map<std::string, int> jidx, sidx, tidx;
-  for (int k = 0; k < nj; k++) if (!joints[k].j->name.empty()) jidx[joints[k].j->name] = k;
-  for (int k = 0; k < ns; k++) if (!sites[k].s->name.empty()) sidx[sites[k].s->name] = k;
+  for (size_t k = 0; k < T.joints.size(); k++) if (!T.joints[k].o->name.empty()) jidx[T.joints[k].o->name] = (int)k;
+  for (size_t k = 0; k < T.sites.size(); k++) if (!T.sites[k].o->name.empty()) sidx[T.sites[k].o->name] = (int)k;
   auto need = [&](const std::map<std::string, int>& m, const std::string& n, const char* what) {
     auto it = m.find(n);
     if (it == m.end()) fail(std::string("unknown ") + what + " '" + n + "'");
     return it->second;
   };
-
-  Flat M;
-  // ---- fp64 fields in the container's order (mjcf.py Model._FIELDS_F64); filled below where they need kinematics ----
-  std::vector<double> body_pos(3 * nbody), body_quat(4 * nbody);
-  for (int i = 0; i < nbody; i++) {
-    for (int a = 0; a < 3; a++) body_pos[3 * i + a] = B[i].pos[a];
-    for (int a = 0; a < 4; a++) body_quat[4 * i + a] = B[i].quat[a];
-  }
-  std::vector<double> jnt_pos(3 * nj), jnt_axis(3 * nj), jnt_range(2 * nj), jnt_stiffness(nj), jnt_margin(nj), jnt_solref(2 * nj), jnt_solimp(5 * nj),
-      qpos0(nq), qpos_spring(nq), dof_damping(nvd), dof_armature(nvd);
-  std::vector<int> jnt_type(nj), jnt_bodyid(nj), jnt_limited(nj);
-  for (int k = 0; k < nj; k++) {
-    const Joint& j = *joints[k].j;
-    jnt_type[k] = j.type; jnt_bodyid[k] = joints[k].body; jnt_limited[k] = j.limited ? 1 : 0;
-    for (int a = 0; a < 3; a++) { jnt_pos[3 * k + a] = j.pos[a]; jnt_axis[3 * k + a] = j.axis[a]; }
-    jnt_range[2 * k] = j.range[0]; jnt_range[2 * k + 1] = j.range[1];
-    jnt_stiffness[k] = j.stiffness; jnt_margin[k] = j.margin;
-    jnt_solref[2 * k] = j.solref[0]; jnt_solref[2 * k + 1] = j.solref[1];
-    for (int a = 0; a < 5; a++) jnt_solimp[5 * k + a] = j.solimp[a];
-    const int qa = jnt_qposadr[k], da = jnt_dofadr[k];
-    if (j.type == SG_JNT_FREE) {   // the body's pose (a child of the world)
-      const Body& bb = B[joints[k].body];
-      for (int a = 0; a < 3; a++) qpos0[qa + a] = qpos_spring[qa + a] = bb.pos[a];
-      for (int a = 0; a < 4; a++) qpos0[qa + 3 + a] = qpos_spring[qa + 3 + a] = bb.quat[a];
-      for (int d = 0; d < 6; d++) { dof_damping[da + d] = j.damping; dof_armature[da + d] = j.armature; }
-    } else {
-      qpos0[qa] = j.ref; qpos_spring[qa] = j.springref; dof_damping[da] = j.damping; dof_armature[da] = j.armature;
-    }
-  }
-  std::vector<double> geom_size(3 * ng), geom_pos(3 * ng), geom_quat(4 * ng), geom_friction(3 * ng), geom_solref(2 * ng), geom_solimp(5 * ng),
-      geom_solmix(ng), geom_margin(ng), geom_gap(ng), geom_rbound(ng, 0.0);
-  std::vector<int> geom_type(ng), geom_bodyid(ng), geom_contype(ng), geom_conaffinity(ng), geom_condim(ng), geom_priority(ng);
-  for (int k = 0; k < ng; k++) {
-    const Geom& g = *geoms[k].g;
-    geom_type[k] = g.type; geom_bodyid[k] = geoms[k].body; geom_contype[k] = g.contype; geom_conaffinity[k] = g.conaffinity;
-    geom_condim[k] = g.condim; geom_priority[k] = g.priority;
-    for (int a = 0; a < 3; a++) { geom_size[3 * k + a] = g.size[a]; geom_pos[3 * k + a] = g.pos[a]; geom_friction[3 * k + a] = g.friction[a]; }
-    for (int a = 0; a < 4; a++) geom_quat[4 * k + a] = g.quat[a];
-    geom_solref[2 * k] = g.solref[0]; geom_solref[2 * k + 1] = g.solref[1];
-    for (int a = 0; a < 5; a++) geom_solimp[5 * k + a] = g.solimp[a];
-    geom_solmix[k] = g.solmix; geom_margin[k] = g.margin; geom_gap[k] = g.gap;
-    if (g.type == SG_GEOM_SPHERE) geom_rbound[k] = g.size[0];
-    else if (g.type == SG_GEOM_CAPSULE) geom_rbound[k] = g.size[0] + g.size[1];
-    else if (g.type == SG_GEOM_BOX) geom_rbound[k] = norm3(g.size);
-  }
-  std::vector<double> site_pos(3 * ns), site_quat(4 * ns);
-  std::vector<int> site_bodyid(ns);
-  for (int k = 0; k < ns; k++) {
-    site_bodyid[k] = sites[k].body;
-    for (int a = 0; a < 3; a++) site_pos[3 * k + a] = sites[k].s->pos[a];
-    for (int a = 0; a < 4; a++) site_quat[4 * k + a] = sites[k].s->quat[a];
-  }
-  const int nt = (int)C.tendons.size();
-  std::vector<int> tendon_adr(nt), tendon_num(nt), wrap_type, wrap_objid;
-  std::vector<double> wrap_prm, tendon_stiffness(nt), tendon_damping(nt);
-  for (int t = 0; t < nt; t++) {
-    const Tendon& T = C.tendons[t];
-    tendon_adr[t] = (int)wrap_type.size();
-    if (T.spatial)
-      for (auto& s : T.sites) { wrap_type.push_back(SG_WRAP_SITE); wrap_objid.push_back(need(sidx, s, "site")); wrap_prm.push_back(0.0); }
+  for (int t = 0; t < T.n.ntendon; t++) {
+    const Tendon& Tn = C.tendons[t];
+    A.tendon_adr[t] = (int)A.wrap_type.size();
+    if (Tn.spatial)
+      for (auto& s : Tn.sites) { A.wrap_type.push_back(SG_WRAP_SITE); A.wrap_objid.push_back(need(sidx, s, "site")); A.wrap_prm.push_back(0.0); }
     else
-      for (auto& jc : T.joints) { wrap_type.push_back(SG_WRAP_JOINT); wrap_objid.push_back(need(jidx, jc.first, "joint")); wrap_prm.push_back(jc.second); }
-    tendon_num[t] = (int)wrap_type.size() - tendon_adr[t];
-    tendon_stiffness[t] = T.stiffness; tendon_damping[t] = T.damping;
-    if (!T.name.empty()) tidx[T.name] = t;
+      for (auto& jc : Tn.joints) { A.wrap_type.push_back(SG_WRAP_JOINT); A.wrap_objid.push_back(need(jidx, jc.first, "joint")); A.wrap_prm.push_back(jc.second); }
+    A.tendon_num[t] = (int)A.wrap_type.size() - A.tendon_adr[t];
+    A.tendon_stiffness[t] = Tn.stiffness; A.tendon_damping[t] = Tn.damping;
+    if (!Tn.name.empty()) tidx[Tn.name] = t;
   }
-  const int ne = (int)C.equalities.size();
-  std::vector<int> eq_type(ne), eq_obj1id(ne), eq_obj2id(ne);
-  std::vector<double> eq_solref(2 * ne), eq_solimp(5 * ne), eq_data(5 * ne);
-  for (int e = 0; e < ne; e++) {
+  for (int e = 0; e < T.n.neq; e++) {
     const Equality& E = C.equalities[e];
-    eq_type[e] = E.type;
-    eq_obj1id[e] = E.type == SG_EQ_JOINT ? need(jidx, E.name1, "joint") : need(tidx, E.name1, "tendon");
-    eq_obj2id[e] = E.has2 ? need(jidx, E.name2, "joint") : -1;
-    eq_solref[2 * e] = E.solref[0]; eq_solref[2 * e + 1] = E.solref[1];
-    for (int a = 0; a < 5; a++) { eq_solimp[5 * e + a] = E.solimp[a]; eq_data[5 * e + a] = E.data[a]; }
+    A.eq_type[e] = E.type;
+    A.eq_obj1id[e] = E.type == SG_EQ_JOINT ? need(jidx, E.name1, "joint") : need(tidx, E.name1, "tendon");
+    A.eq_obj2id[e] = E.has2 ? need(jidx, E.name2, "joint") : -1;
+    A.eq_solref[2 * e] = E.solref[0]; A.eq_solref[2 * e + 1] = E.solref[1];
+    for (int a = 0; a < 5; a++) { A.eq_solimp[5 * e + a] = E.solimp[a]; A.eq_data[5 * e + a] = E.data[a]; }
   }
-  const int nu = (int)C.actuators.size();
-  std::vector<int> actuator_trnid(nu);
-  std::vector<double> actuator_timeconst(nu), actuator_gain(nu), actuator_bias(3 * nu), actuator_gear(nu);
-  for (int u = 0; u < nu; u++) {
-    const Actuator& A = C.actuators[u];
-    actuator_trnid[u] = need(tidx, A.tendon, "tendon");
-    actuator_timeconst[u] = A.timeconst; actuator_gain[u] = A.gain; actuator_gear[u] = A.gear;
-    for (int a = 0; a < 3; a++) actuator_bias[3 * u + a] = A.bias[a];
+  for (int u = 0; u < T.n.nu; u++) {
+    const Actuator& Ac = C.actuators[u];
+    A.actuator_trnid[u] = need(tidx, Ac.tendon, "tendon");
+    A.actuator_timeconst[u] = Ac.timeconst; A.actuator_gain[u] = Ac.gain; A.actuator_gear[u] = Ac.gear;
+    for (int a = 0; a < 3; a++) A.actuator_bias[3 * u + a] = Ac.bias[a];
   }
-  const int nsens = (int)C.sensors.size();
-  std::vector<int> sensor_type(nsens), sensor_objid(nsens), sensor_adr(nsens);
-  for (int k = 0; k < nsens; k++) {
-    sensor_type[k] = C.sensors[k].type; sensor_objid[k] = need(sidx, C.sensors[k].site, "site"); sensor_adr[k] = 3 * k;
+  for (int k = 0; k < T.n.nsensor; k++) {
+    A.sensor_type[k] = C.sensors[k].type; A.sensor_objid[k] = need(sidx, C.sensors[k].site, "site"); A.sensor_adr[k] = 3 * k;
   }
+}
 
-  // ---- qpos0-dependent constants (MuJoCo's mj_setConst; mjcf.py Model._set_const) ----
-  const int nv = nvd;
+// the qpos0-dependent constants (MuJoCo's mj_setConst; the twin of mjcf.py's Model._set_const): kinematics at qpos0, the mass matrix and
+// its inverse, dof_invweight0, body_invweight0, tendon_length0 (and the spring length) and tendon_invweight0, meaninertia (opt_d)
+void set_const(const Compiler& C, Arrays& A, const Tree& T) {
+  const int nbody = T.n.nbody, nj = T.n.njnt, ns = T.n.nsite, nt = T.n.ntendon, nv = T.n.nv;
   std::vector<V3> xpos(nbody), xanchor(nv), xaxis(nv);   // anchors / axes by DOF
   std::vector<int> dof_rot(nv, 0);
   std::vector<Q4> xquat(nbody);
   std::vector<M3> xmat(nbody);
   xmat[0] = quat_to_mat(xquat[0]);
   for (int i = 1; i < nbody; i++) {
-    const int p = body_parentid[i];
+    const int p = A.body_parentid[i];
     M3 R = quat_to_mat(xquat[p]);
-    V3 bp; for (int a = 0; a < 3; a++) bp[a] = body_pos[3 * i + a];
+    V3 bp; for (int a = 0; a < 3; a++) bp[a] = A.body_pos[3 * i + a];
     V3 t = mul(R, bp), pos;
     for (int a = 0; a < 3; a++) pos[a] = xpos[p][a] + t[a];
-    Q4 bq; for (int a = 0; a < 4; a++) bq[a] = body_quat[4 * i + a];
+    Q4 bq; for (int a = 0; a < 4; a++) bq[a] = A.body_quat[4 * i + a];
     Q4 quat = quat_mul(xquat[p], bq);
-    for (int k = 0; k < body_jntnum[i]; k++) {
-      const int jn = body_jntadr[i] + k, j = jnt_dofadr[jn];
-      if (jnt_type[jn] == SG_JNT_FREE) {   // at qpos0 the free body sits where the XML puts it; dofs: world translations, body-axis rotations
+    for (int k = 0; k < A.body_jntnum[i]; k++) {
+      const int jn = A.body_jntadr[i] + k, j = A.jnt_dofadr[jn];
+      if (A.jnt_type[jn] == SG_JNT_FREE) {   // at qpos0 the free body sits where the XML puts it; dofs: world translations, body-axis rotations
         R = quat_to_mat(quat_normalize(quat));
         for (int c = 0; c < 3; c++) {
           xanchor[j + c] = pos; xanchor[j + 3 + c] = pos;
@@ -956,12 +941,12 @@ std::string finalize(Compiler& C, bool implicit_tendon_damping) {
         continue;
       }
       R = quat_to_mat(quat);
-      V3 jp, ja; for (int a = 0; a < 3; a++) { jp[a] = jnt_pos[3 * jn + a]; ja[a] = jnt_axis[3 * jn + a]; }
+      V3 jp, ja; for (int a = 0; a < 3; a++) { jp[a] = A.jnt_pos[3 * jn + a]; ja[a] = A.jnt_axis[3 * jn + a]; }
       V3 rj = mul(R, jp);
       for (int a = 0; a < 3; a++) xanchor[j][a] = pos[a] + rj[a];
       xaxis[j] = mul(R, ja);
       const double dq = 0.0;  // at qpos0
-      if (jnt_type[jn] == SG_JNT_SLIDE) {
+      if (A.jnt_type[jn] == SG_JNT_SLIDE) {
         for (int a = 0; a < 3; a++) pos[a] = pos[a] + xaxis[j][a] * dq;
       } else {
         dof_rot[j] = 1;
@@ -980,10 +965,10 @@ std::string finalize(Compiler& C, bool implicit_tendon_damping) {
   struct Jcol { int dof; V3 jp, jr; };
   auto jac_point = [&](int body, const V3& point) {
     std::vector<Jcol> cols;
-    for (int b = body; b > 0; b = body_parentid[b])
-      for (int k = 0; k < body_jntnum[b]; k++) {
-        const int jn = body_jntadr[b] + k;
-        for (int j = jnt_dofadr[jn]; j < jnt_dofadr[jn] + (jnt_type[jn] == SG_JNT_FREE ? 6 : 1); j++) {
+    for (int b = body; b > 0; b = A.body_parentid[b])
+      for (int k = 0; k < A.body_jntnum[b]; k++) {
+        const int jn = A.body_jntadr[b] + k;
+        for (int j = A.jnt_dofadr[jn]; j < A.jnt_dofadr[jn] + (A.jnt_type[jn] == SG_JNT_FREE ? 6 : 1); j++) {
           Jcol c; c.dof = j;
           if (!dof_rot[j]) { c.jp = xaxis[j]; }
           else {
@@ -997,26 +982,26 @@ std::string finalize(Compiler& C, bool implicit_tendon_damping) {
     return cols;
   };
   std::vector<double> Mq((size_t)nv * nv, 0.0);
-  for (int j = 0; j < nv; j++) Mq[(size_t)j * nv + j] = dof_armature[j];
+  for (int j = 0; j < nv; j++) Mq[(size_t)j * nv + j] = A.dof_armature[j];
   std::vector<V3> com(nbody);
   for (int b = 1; b < nbody; b++) {
-    V3 ip; for (int a = 0; a < 3; a++) ip[a] = ipos[3 * b + a];
+    V3 ip; for (int a = 0; a < 3; a++) ip[a] = A.body_ipos[3 * b + a];
     V3 t = mul(xmat[b], ip);
     for (int a = 0; a < 3; a++) com[b][a] = xpos[b][a] + t[a];
-    if (mass[b] <= 0 || body_weldid[b] == 0) continue;
+    if (A.body_mass[b] <= 0 || A.body_weldid[b] == 0) continue;
     M3 Iw;  // R I R'
     for (int a = 0; a < 3; a++)
       for (int c = 0; c < 3; c++) {
         double s = 0;
         for (int d = 0; d < 3; d++)
-          for (int e = 0; e < 3; e++) s += xmat[b].m[a][d] * imat[9 * b + 3 * d + e] * xmat[b].m[c][e];
+          for (int e = 0; e < 3; e++) s += xmat[b].m[a][d] * A.body_imat[9 * b + 3 * d + e] * xmat[b].m[c][e];
         Iw.m[a][c] = s;
       }
     auto cols = jac_point(b, com[b]);
     for (auto& c1 : cols)
       for (auto& c2 : cols) {
         const V3 Ij = mul(Iw, c2.jr);
-        Mq[(size_t)c1.dof * nv + c2.dof] += mass[b] * (c1.jp[0] * c2.jp[0] + c1.jp[1] * c2.jp[1] + c1.jp[2] * c2.jp[2]) +
+        Mq[(size_t)c1.dof * nv + c2.dof] += A.body_mass[b] * (c1.jp[0] * c2.jp[0] + c1.jp[1] * c2.jp[1] + c1.jp[2] * c2.jp[2]) +
                                             (c1.jr[0] * Ij[0] + c1.jr[1] * Ij[1] + c1.jr[2] * Ij[2]);
       }
   }
@@ -1054,17 +1039,17 @@ std::string finalize(Compiler& C, bool implicit_tendon_damping) {
   double tr = 0;
   for (int j = 0; j < nv; j++) tr += Mq[(size_t)j * nv + j];
   const double meaninertia = tr / (nv > 1 ? nv : 1);
-  std::vector<double> dof_invweight0(nv), body_invweight0(2 * nbody, 0.0);
-  for (int j = 0; j < nv; j++) dof_invweight0[j] = Minv[(size_t)j * nv + j];
+  A.opt_d = {C.timestep, C.gravity[0], C.gravity[1], C.gravity[2], C.tolerance, C.impratio, meaninertia};
+  for (int j = 0; j < nv; j++) A.dof_invweight0[j] = Minv[(size_t)j * nv + j];
   for (int k = 0; k < nj; k++)   // mj_setConst: one value for a free joint's three translations, one for its three rotations
-    if (jnt_type[k] == SG_JNT_FREE)
+    if (A.jnt_type[k] == SG_JNT_FREE)
       for (int h3 = 0; h3 < 2; h3++) {
-        const int d0 = jnt_dofadr[k] + 3 * h3;
-        const double av = (dof_invweight0[d0] + dof_invweight0[d0 + 1] + dof_invweight0[d0 + 2]) / 3;
-        dof_invweight0[d0] = dof_invweight0[d0 + 1] = dof_invweight0[d0 + 2] = av;
+        const int d0 = A.jnt_dofadr[k] + 3 * h3;
+        const double av = (A.dof_invweight0[d0] + A.dof_invweight0[d0 + 1] + A.dof_invweight0[d0 + 2]) / 3;
+        A.dof_invweight0[d0] = A.dof_invweight0[d0 + 1] = A.dof_invweight0[d0 + 2] = av;
       }
   for (int b = 1; b < nbody; b++) {
-    if (body_weldid[b] == 0) continue;
+    if (A.body_weldid[b] == 0) continue;
     auto cols = jac_point(b, com[b]);
     double tt = 0, rr = 0;
     for (int a = 0; a < 3; a++) {  // diagonal entries of J M^-1 J' (translation rows, rotation rows)
@@ -1077,96 +1062,100 @@ std::string finalize(Compiler& C, bool implicit_tendon_damping) {
         }
       tt += st; rr += sr;
     }
-    body_invweight0[2 * b] = tt / 3; body_invweight0[2 * b + 1] = rr / 3;
+    A.body_invweight0[2 * b] = tt / 3; A.body_invweight0[2 * b + 1] = rr / 3;
   }
-  std::vector<double> tendon_length0(nt, 0.0), tendon_invweight0(nt, 0.0);
-  {
-    std::vector<V3> sx(ns);
-    for (int k = 0; k < ns; k++) {
-      V3 sp; for (int a = 0; a < 3; a++) sp[a] = site_pos[3 * k + a];
-      V3 t = mul(xmat[site_bodyid[k]], sp);
-      for (int a = 0; a < 3; a++) sx[k][a] = xpos[site_bodyid[k]][a] + t[a];
-    }
-    for (int t = 0; t < nt; t++) {
-      std::vector<double> J(nv, 0.0);
-      const int a0 = tendon_adr[t], n = tendon_num[t];
-      if (wrap_type[a0] == SG_WRAP_JOINT) {
-        for (int w = a0; w < a0 + n; w++) {   // (wrap_objid: a joint id)
-          tendon_length0[t] += wrap_prm[w] * qpos0[jnt_qposadr[wrap_objid[w]]];
-          J[jnt_dofadr[wrap_objid[w]]] = wrap_prm[w];
-        }
-      } else {
-        for (int w = a0; w < a0 + n - 1; w++) {
-          const int s0 = wrap_objid[w], s1 = wrap_objid[w + 1];
-          double d[3];
-          for (int a = 0; a < 3; a++) d[a] = sx[s1][a] - sx[s0][a];
-          const double ln = norm3(d);
-          tendon_length0[t] += ln;
-          if (ln > kMinVal) {
-            for (auto& c : jac_point(site_bodyid[s1], sx[s1])) J[c.dof] += (d[0] * c.jp[0] + d[1] * c.jp[1] + d[2] * c.jp[2]) / ln;
-            for (auto& c : jac_point(site_bodyid[s0], sx[s0])) J[c.dof] -= (d[0] * c.jp[0] + d[1] * c.jp[1] + d[2] * c.jp[2]) / ln;
-          }
+  std::vector<V3> sx(ns);
+  for (int k = 0; k < ns; k++) {
+    V3 sp; for (int a = 0; a < 3; a++) sp[a] = A.site_pos[3 * k + a];
+    V3 t = mul(xmat[A.site_bodyid[k]], sp);
+    for (int a = 0; a < 3; a++) sx[k][a] = xpos[A.site_bodyid[k]][a] + t[a];
+  }
+  for (int t = 0; t < nt; t++) {
+    std::vector<double> J(nv, 0.0);
+    const int a0 = A.tendon_adr[t], n = A.tendon_num[t];
+    if (A.wrap_type[a0] == SG_WRAP_JOINT) {
+      for (int w = a0; w < a0 + n; w++) {   // (wrap_objid: a joint id)
+        A.tendon_length0[t] += A.wrap_prm[w] * A.qpos0[A.jnt_qposadr[A.wrap_objid[w]]];
+        J[A.jnt_dofadr[A.wrap_objid[w]]] = A.wrap_prm[w];
+      }
+    } else {
+      for (int w = a0; w < a0 + n - 1; w++) {
+        const int s0 = A.wrap_objid[w], s1 = A.wrap_objid[w + 1];
+        double d[3];
+        for (int a = 0; a < 3; a++) d[a] = sx[s1][a] - sx[s0][a];
+        const double ln = norm3(d);
+        A.tendon_length0[t] += ln;
+        if (ln > kMinVal) {
+          for (auto& c : jac_point(A.site_bodyid[s1], sx[s1])) J[c.dof] += (d[0] * c.jp[0] + d[1] * c.jp[1] + d[2] * c.jp[2]) / ln;
+          for (auto& c : jac_point(A.site_bodyid[s0], sx[s0])) J[c.dof] -= (d[0] * c.jp[0] + d[1] * c.jp[1] + d[2] * c.jp[2]) / ln;
         }
       }
-      double s = 0;
-      for (int a = 0; a < nv; a++) {
-        if (J[a] == 0) continue;
-        double r = 0;
-        for (int b = 0; b < nv; b++) r += Minv[(size_t)a * nv + b] * J[b];
-        s += J[a] * r;
-      }
-      tendon_invweight0[t] = s;
     }
+    double s = 0;
+    for (int a = 0; a < nv; a++) {
+      if (J[a] == 0) continue;
+      double r = 0;
+      for (int b = 0; b < nv; b++) r += Minv[(size_t)a * nv + b] * J[b];
+      s += J[a] * r;
+    }
+    A.tendon_invweight0[t] = s;
   }
+  A.tendon_lengthspring = A.tendon_length0;   // springlength = -1: the length at qpos0
+}
 
-  // ---- the container ----
-  std::string body;
-  int nrec = 0;
-  auto addF = [&](const char* n, const std::vector<double>& v) { put_record(body, n, SG_DT_F64, (int64_t)v.size(), v.data(), v.size() * 8); nrec++; };
-  auto addI = [&](const char* n, const std::vector<int>& v) { put_record(body, n, SG_DT_I32, (int64_t)v.size(), v.data(), v.size() * 4); nrec++; };
-  addF("opt_d", {C.timestep, C.gravity[0], C.gravity[1], C.gravity[2], C.tolerance, C.impratio, meaninertia});
-  addI("opt_i", {C.iterations, C.nconmax, C.njmax, implicit_tendon_damping ? 1 : 0});
-  addF("body_pos", body_pos); addF("body_quat", body_quat); addF("body_ipos", ipos); addF("body_imat", imat); addF("body_mass", mass);
-  addF("body_invweight0", body_invweight0);
-  addF("jnt_pos", jnt_pos); addF("jnt_axis", jnt_axis); addF("jnt_range", jnt_range); addF("jnt_stiffness", jnt_stiffness);
-  addF("jnt_margin", jnt_margin); addF("jnt_solref", jnt_solref); addF("jnt_solimp", jnt_solimp);
-  addF("qpos0", qpos0); addF("qpos_spring", qpos_spring); addF("dof_damping", dof_damping); addF("dof_armature", dof_armature);
-  addF("dof_invweight0", dof_invweight0);
-  addF("geom_size", geom_size); addF("geom_pos", geom_pos); addF("geom_quat", geom_quat); addF("geom_friction", geom_friction);
-  addF("geom_solref", geom_solref); addF("geom_solimp", geom_solimp); addF("geom_solmix", geom_solmix);
-  addF("geom_margin", geom_margin); addF("geom_gap", geom_gap); addF("geom_rbound", geom_rbound);
-  addF("site_pos", site_pos); addF("site_quat", site_quat);
-  addF("tendon_stiffness", tendon_stiffness); addF("tendon_damping", tendon_damping);
-  addF("tendon_lengthspring", tendon_length0);  // springlength = -1: the length at qpos0
-  addF("tendon_length0", tendon_length0); addF("tendon_invweight0", tendon_invweight0);
-  addF("wrap_prm", wrap_prm); addF("eq_solref", eq_solref); addF("eq_solimp", eq_solimp); addF("eq_data", eq_data);
-  addF("actuator_timeconst", actuator_timeconst); addF("actuator_gain", actuator_gain); addF("actuator_bias", actuator_bias);
-  addF("actuator_gear", actuator_gear);
-  addI("body_parentid", body_parentid); addI("body_weldid", body_weldid); addI("body_jntadr", body_jntadr); addI("body_jntnum", body_jntnum);
-  addI("body_geomadr", body_geomadr); addI("body_geomnum", body_geomnum);
-  addI("jnt_type", jnt_type); addI("jnt_bodyid", jnt_bodyid); addI("jnt_limited", jnt_limited); addI("dof_parentid", dof_parentid);
-  addI("geom_type", geom_type); addI("geom_bodyid", geom_bodyid); addI("geom_contype", geom_contype); addI("geom_conaffinity", geom_conaffinity);
-  addI("geom_condim", geom_condim); addI("geom_priority", geom_priority);
-  addI("site_bodyid", site_bodyid); addI("tendon_adr", tendon_adr); addI("tendon_num", tendon_num); addI("wrap_type", wrap_type);
-  addI("wrap_objid", wrap_objid);
-  addI("eq_type", eq_type); addI("eq_obj1id", eq_obj1id); addI("eq_obj2id", eq_obj2id); addI("actuator_trnid", actuator_trnid);
-  addI("sensor_type", sensor_type); addI("sensor_objid", sensor_objid); addI("sensor_adr", sensor_adr);
-  if (has_free) { addI("jnt_qposadr", jnt_qposadr); addI("jnt_dofadr", jnt_dofadr); addI("dof_jntid", dof_jntid); }   // (only then do the three index spaces differ)
-  std::vector<std::string> bn, jn, gn, sn, tn, sen;
-  for (auto& b : B) bn.push_back(b.name);
-  for (auto& j : joints) jn.push_back(j.j->name);
-  for (auto& g : geoms) gn.push_back(g.g->name);
-  for (auto& s : sites) sn.push_back(s.s->name);
-  for (auto& t : C.tendons) tn.push_back(t.name);
-  for (auto& s : C.sensors) sen.push_back(s.name);
-  const std::string names = join(bn) + "\n" + join(jn) + "\n" + join(gn) + "\n" + join(sn) + "\n" + join(tn) + "\n" + join(sen);
-  put_record(body, "names", SG_DT_U8, (int64_t)names.size(), names.data(), names.size());
-  nrec++;
+void put_record(std::string& out, const std::string& name, uint32_t code, int64_t count, const void* data, size_t nbytes) {
+  if (name.size() > 23) fail("field name too long: " + name);
+  sg_blob_record r;
+  memset(&r, 0, sizeof r);
+  memcpy(r.name, name.data(), name.size());
+  r.dtype = code; r.count = count;
+  out.append((const char*)&r, sizeof r);
+  out.append((const char*)data, nbytes);
+  out.append((8 - nbytes % 8) % 8, '\0');
+}
+// one array of the table: its count held against the table's rule (sg_blob.h: the first array of a dimension defines it), then its record
+template <class E> void put_array(std::string& out, SgModelDims* D, const char* name, const std::vector<E>& v, int per, int* dim) {
+  if (!sg_model_count_fits(D, (long long)v.size(), per, dim)) fail(std::string("compiler self-check: ") + name + " has " + std::to_string(v.size()) + " entries, which does not fit the table");
+  put_record(out, name, sizeof(E) == 8 ? SG_DT_F64 : SG_DT_I32, (int64_t)v.size(), v.data(), v.size() * sizeof(E));
+}
+
+template <class O> const std::string& name_of(const O& o) { return o.name; }
+template <class O> const std::string& name_of(const Ref<O>& r) { return r.o->name; }
+template <class V> std::string join(const V& v) {   // one line of the names record
+  std::string o;
+  for (size_t i = 0; i < v.size(); i++) { if (i) o += '|'; o += name_of(v[i]); }
+  return o;
+}
+
+// the container: the table's arrays in its order (the free_only ones only with a free joint), the names, the header in front
+std::string write_blob(const Compiler& C, const Arrays& A, const Tree& T) {
   sg_blob_header h;
-  h.magic = SG_BLOB_MAGIC; h.version = SG_BLOB_VERSION; h.nrec = (uint32_t)nrec; h.reserved = 0; h.total_bytes = (int64_t)(body.size() + sizeof h);
-  std::string out((const char*)&h, sizeof h);
-  out += body;
+  h.magic = SG_BLOB_MAGIC; h.version = SG_BLOB_VERSION; h.nrec = 0; h.reserved = 0; h.total_bytes = 0;
+  std::string out((const char*)&h, sizeof h);   // (the header's place: written again at the end, complete)
+  SgModelDims D;
+#define SG_X(type, name, per, dim, part) { put_array(out, &D, #name, A.name, per, &D.dim); h.nrec++; }
+#define SG_W(type, name, per, dim, free_only) if (!free_only || T.has_free) SG_X(type, name, per, dim, 0)
+  SG_MODEL_ARRAYS(SG_X, SG_W)
+#undef SG_X
+#undef SG_W
+  const std::string names = join(C.bodies) + "\n" + join(T.joints) + "\n" + join(T.geoms) + "\n" + join(T.sites) + "\n" + join(C.tendons) + "\n" + join(C.sensors);
+  put_record(out, "names", SG_DT_U8, (int64_t)names.size(), names.data(), names.size());
+  h.nrec++;
+  h.total_bytes = (int64_t)out.size();
+  out.replace(0, sizeof h, (const char*)&h, sizeof h);
   return out;
+}
+
+std::string finalize(const Compiler& C, bool implicit_tendon_damping) {
+  Arrays A;
+  Tree T;
+  number_tree(C, A, T);
+  inertia_from_geoms(C, A);
+  fill_tables(C, A, T);
+  fill_constraints(C, A, T);
+  set_const(C, A, T);
+  A.opt_i = {C.iterations, C.nconmax, C.njmax, implicit_tendon_damping ? 1 : 0};
+  return write_blob(C, A, T);
 }
 
 }  // namespace

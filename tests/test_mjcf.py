@@ -358,3 +358,19 @@ def test_native_compiler_matches_python_on_random_scenes(tmp_path):
         _compare_models(py, sg.Model.from_blob(native.compile_mjcf_native(str(path))), rtol=1e-9)
         compiled += 1
     assert compiled >= 25
+
+
+def test_python_field_lists_match_the_blob_schema():
+    """the arrays of a blob, their order and their types are written down twice: mjcf.py's Model.to_blob (opt_d, opt_i, _FIELDS_F64,
+    _FIELDS_I32, the three index arrays of a free joint) and the table SG_MODEL_ARRAYS of csrc/sg_blob.h, which the native compiler writes
+    from and the plan builder reads from (tests/emu/sg_plan_dump --table prints it).  Either side gaining, losing or moving an array fails here."""
+    import subprocess
+    from helpers import ROOT
+    emu = os.path.join(ROOT, "tests", "emu")
+    subprocess.check_call(["make", "-s", "-C", emu, "sg_plan_dump"])
+    rows = [line.split() for line in subprocess.run([os.path.join(emu, "sg_plan_dump"), "--table"], capture_output=True, text=True, check=True).stdout.splitlines()]
+    free = ["jnt_qposadr", "jnt_dofadr", "dof_jntid"]
+    python = ([("opt_d", "f64"), ("opt_i", "i32")] + [(f, "f64") for f in sg.Model._FIELDS_F64] + [(f, "i32") for f in sg.Model._FIELDS_I32]
+              + [(f, "i32") for f in free])
+    assert [(r[0], r[1]) for r in rows] == python
+    assert [r[0] for r in rows if r[4] == "optional"] == free and all(r[4] in ("optional", "required") for r in rows)

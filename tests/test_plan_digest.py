@@ -1,6 +1,7 @@
 """The kernel plans are pinned: tests/emu/sg_plan_dump.cpp builds the plan of every input with both builders (sg_plan_build, sg_tree_plan_build)
 and prints, per builder, the refusal message or a hash of the raw bytes of each part of the plan (SgPlanHeader, elem, elem_geom, elem_dofmap,
-nbtab, sched, gpairs, SgTreeDev).  tests/golden/plan_digests.json holds that output; the comparison is exact.
+nbtab, sched, gpairs, SgTreeDev), and per compiled .xml and composite variant a hash of the blob the native MJCF compiler wrote (`blob:`).
+tests/golden/plan_digests.json holds that output; the comparison is exact.
 
 Inputs: the committed models/*.sgmodel, every tests/data/*.xml in both composite variants, and 32 seeded random grippers of the tree class
 (helpers.random_gripper_xml), every second one on a free joint.
