@@ -78,7 +78,7 @@ static int rows_alloc(sg_batch* b) {
   r.shape = sg_rows_shape(H);
   r.nsl = sg_rows_nsl(H.nelem);
   r.w.secprof = b->secprof;
-  bool ok = A.zeros(&r.H, 1) && hipMemcpy(r.H, &H, sizeof H, hipMemcpyHostToDevice) == hipSuccess && A.upload(&r.elem, m->plan.elem) &&
+  bool ok = A.zeros(&r.H, 1) && hipMemcpy(r.H, &H, sizeof H, hipMemcpyHostToDevice) == hipSuccess && A.upload(&r.elem, sg_rows_elem_table(m->plan)) &&
             A.upload(&r.gpairs, m->plan.gpairs) &&
             sg_rows_work_each(r.w, H, m->rounds, (size_t)b->n, SG_LEGACY_ON != 0, [&A](auto** p, size_t count) { return A.zeros(p, count); });
   if (ok && r.shape.nb_mode) {

@@ -26,14 +26,14 @@ struct GenLds {
   const double (*boxm)[9];
   const ChainKin* K;
   const ChainLds2* cs;
-  const double *qe, *ve, *asme, *we;   // per element (LDS): slider position, velocity, smooth acceleration, warmstart
+  const double *dq, *ve, *asme, *we;   // per element (LDS): slider position - qpos0, velocity, smooth acceleration, warmstart
 };
 
 // geometry of a capsule of the pair table
 __device__ __forceinline__ void sg_gen_capsule(const SgPhaseArgs& a, const GenLds& L, int e, double* cp, double* cax) {
   const int N = a.nelem;
   auto EL = [&](int f, int k) { return a.elem[(size_t)f * N + k]; };
-  const double dq = L.qe[e] - EL(SGE_QPOS0, e);
+  const double dq = L.dq[e];   // (the element's own lane formed q - qpos0: the same subtraction)
   cp[0] = EL(SGE_GX, e) + EL(SGE_AX, e) * dq; cp[1] = EL(SGE_GY, e) + EL(SGE_AY, e) * dq; cp[2] = EL(SGE_GZ, e) + EL(SGE_AZ, e) * dq;
   cax[0] = EL(SGE_CX, e); cax[1] = EL(SGE_CY, e); cax[2] = EL(SGE_CZ, e);
 }
@@ -272,7 +272,7 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
   __shared__ Smem2<R, CPL, NB> Sm;
   const SG_CONSTAS double* const elemc = (const SG_CONSTAS double*)a.elem;
   [[maybe_unused]] const SG_CONSTAS int* const nbtabc = (const SG_CONSTAS int*)a.nbtab;
-  auto EL = [&](int f, int e) { return elemc[(size_t)f * N + e]; };
+  auto EL = [&](int f, int e) { return elemc[sg_elem_table_index(f, e, N)]; };   // the plan's fields (SGE_*) and the host's derived ones (SGD_*)
   const int half = lane >> 5;
   const bool high = half != 0;
   const bool is_chain_lane = (lane & 31) == 0 && half < nchain;
@@ -306,51 +306,87 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
   const int kt0_masked = a.kmask_ten[a.t0_id];
 
   // ---------------- load state ----------------
-  double qe[R], ve[R], we[R], ke[R];
+  // EVERY load of the prologue is unconditional and independent of the others: a lane without an element reads element N - 1's words and
+  // drops them, a launch that resets reads the state it is about to overwrite, a launch without FINISH the work-space words that exist
+  // either way.  Behind a branch (e < N, do_reset, do_finish, the joint mask's word) each group of loads was waited for before the next
+  // was issued -- six round trips in a row where this is ONE batch (profiles/r17_phase_wait_census.txt)
+  bool live[R];
+  int ec[R];
 #pragma unroll
-  for (int r = 0; r < R; r++) {
-    int e = r * 64 + lane;
-    qe[r] = ve[r] = we[r] = ke[r] = 0;
-    if (e < N) {
-      if (a.do_reset) { qe[r] = EL(SGE_QPOS0, e); }
-      else { qe[r] = gq[e0 + e]; ve[r] = gv[e0 + e]; we[r] = gw[e0 + e]; }
-      ke[r] = a.kmask_jnt[e0 + e] ? kenv : EL(SGE_K0, e);
+  for (int r = 0; r < R; r++) { const int e = r * 64 + lane; live[r] = e < N; ec[r] = live[r] ? e : N - 1; }
+  double qe[R], ve[R], we[R], ke[R], eq0[R];
+  {
+    double qs[R], vs[R], ws[R], k0[R];
+    int km[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      qs[r] = gq[e0 + ec[r]]; vs[r] = gv[e0 + ec[r]]; ws[r] = gw[e0 + ec[r]];
+      km[r] = a.kmask_jnt[e0 + ec[r]]; k0[r] = EL(SGE_K0, ec[r]); eq0[r] = EL(SGE_QPOS0, ec[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      qe[r] = live[r] ? (a.do_reset ? eq0[r] : qs[r]) : 0.0;
+      ve[r] = live[r] && !a.do_reset ? vs[r] : 0.0;
+      we[r] = live[r] && !a.do_reset ? ws[r] : 0.0;
+      ke[r] = live[r] ? (km[r] ? kenv : k0[r]) : 0.0;
     }
   }
-  // the loads of FINISH (solver result, smooth acceleration and force of the previous substep) and the import of the chain
-  // hand-off record are issued here, together with the state: one memory latency instead of three in a row (the kernel waits for
-  // memory two thirds of its time, profiles/r02)
+  // the loads of FINISH (solver result, smooth acceleration and force of the previous substep), the element constants FINISH and BEGIN
+  // share -- m + armature and its inverse from the host's derived fields (SGD_MSUM, SGD_INVM: the sum and the division every lane redid
+  // in every substep), damping, tendon coefficient -- and the import of the chain hand-off record are issued here, together with the
+  // state: one memory latency instead of three in a row (the kernel waits for memory two thirds of its time, profiles/r02)
   double ase[R], asme_p[R], fsm_p[R];
+  double msum[R], invm0[R], damp[R], coef[R];
 #pragma unroll
   for (int r = 0; r < R; r++) {
-    const int e = r * 64 + lane;
-    ase[r] = asme_p[r] = fsm_p[r] = 0;
-    if (a.do_finish && e < N) {  // whether a substep is pending is tested below: the workspace words exist either way
-      ase[r] = W.as[(size_t)env * N + e]; asme_p[r] = W.asme[(size_t)env * N + e];
-      if (a.finish_integrate) fsm_p[r] = W.fsm[(size_t)env * N + e];
-    }
+    const size_t o = (size_t)env * N + ec[r];
+    const double as_l = W.as[o], asme_l = W.asme[o], fsm_l = W.fsm[o];  // whether a substep is pending is tested below
+    const bool f = a.do_finish && live[r];
+    ase[r] = f ? as_l : 0.0; asme_p[r] = f ? asme_l : 0.0; fsm_p[r] = f && a.finish_integrate ? fsm_l : 0.0;
+    msum[r] = EL(SGD_MSUM, ec[r]); invm0[r] = EL(SGD_INVM, ec[r]); damp[r] = EL(SGE_DAMPING, ec[r]);
+    const double cf = EL(SGE_COEF, ec[r]);
+    coef[r] = live[r] ? cf : 0.0;
   }
-  if (a.do_begin && half < nchain) {  // the chain stage ran in sg_chain_kernel: import its hand-off record, the 32 lanes of a half sharing the loads
-    const double* ch = W.chh + ((size_t)env * 2 + half) * SG_CHW;
-    double* const kd = (double*)&Sm.K[half];
-    double* const box = &Sm.boxp[half * SG_CG][0];
-    double* const boxm = &Sm.boxm[half * SG_CG][0];
-    double* const lim = CS.lim_sign;  // lim_sign, lim_R, lim_b, lim_f are contiguous, as SGH_LIMSIGN .. SGH_LIMF are (sg_work.h: asserted)
+  // the constants of BEGIN's element stage, in the same batch where the registers allow it (they are dead before the contact rows are built)
+  double eax[R][3], egp[R][3], emass[R], esref[R], eqlo[R], eqhi[R];
+  auto load_begin_consts = [&]() {
 #pragma unroll
-    for (int j0 = 0; j0 < SG_CHW; j0 += 32) {
-      const int j = j0 + (lane & 31);
-      const double v = j < SG_CHW ? ch[j] : 0.0;
-      if (j >= SGH_QSM && j < SGH_QSM + SG_CD) CS.qacc_smooth[j - SGH_QSM] = v;
-      else if (j >= SGH_K && j < SGH_K + SGH_N_K) kd[j - SGH_K] = v;
-      else if (j >= SGH_MINV && j < SGH_MINV + SGH_N_M) CS.Minv[j - SGH_MINV] = v;
-      else if (j >= SGH_V && j < SGH_V + SG_CD) CS.v[j - SGH_V] = v;
-      else if (j >= SGH_W && j < SGH_W + SG_CD) CS.w[j - SGH_W] = v;
-      else if (j >= SGH_BOX && j < SGH_BOX + SGH_N_BOX) {
-        const int g = (j - SGH_BOX) / SGH_N_BOX1, k = (j - SGH_BOX) % SGH_N_BOX1;
-        if (k < 3) box[3 * g + k] = v; else boxm[9 * g + k - 3] = v;
+    for (int r = 0; r < R; r++) {
+      eax[r][0] = EL(SGE_AX, ec[r]); eax[r][1] = EL(SGE_AY, ec[r]); eax[r][2] = EL(SGE_AZ, ec[r]);
+      egp[r][0] = EL(SGE_GX, ec[r]); egp[r][1] = EL(SGE_GY, ec[r]); egp[r][2] = EL(SGE_GZ, ec[r]);
+      emass[r] = EL(SGE_MASS, ec[r]); esref[r] = EL(SGE_SPRINGREF, ec[r]); eqlo[r] = EL(SGE_QLO, ec[r]); eqhi[r] = EL(SGE_QHI, ec[r]);
+    }
+  };
+  constexpr bool CONSTS_EARLY = R <= 2;
+  if constexpr (CONSTS_EARLY) load_begin_consts();
+  {  // the chain stage ran in sg_chain_kernel: import its hand-off record, the 32 lanes of a half sharing the loads (a half without a chain
+     // loads chain 0's record and stores nothing)
+    const double* ch = W.chh + ((size_t)env * 2 + (half < nchain ? half : 0)) * SG_CHW;
+    static_assert(SG_CHW % 32 == 0, "whole trips of a half's 32 lanes");
+    double hv[SG_CHW / 32];
+#pragma unroll
+    for (int t = 0; t < SG_CHW / 32; t++) hv[t] = ch[32 * t + (lane & 31)];
+    if (a.do_begin && half < nchain) {
+      double* const kd = (double*)&Sm.K[half];
+      double* const box = &Sm.boxp[half * SG_CG][0];
+      double* const boxm = &Sm.boxm[half * SG_CG][0];
+      double* const lim = CS.lim_sign;  // lim_sign, lim_R, lim_b, lim_f are contiguous, as SGH_LIMSIGN .. SGH_LIMF are (sg_work.h: asserted)
+#pragma unroll
+      for (int j0 = 0; j0 < SG_CHW; j0 += 32) {
+        const int j = j0 + (lane & 31);
+        const double v = hv[j0 / 32];
+        if (j >= SGH_QSM && j < SGH_QSM + SG_CD) CS.qacc_smooth[j - SGH_QSM] = v;
+        else if (j >= SGH_K && j < SGH_K + SGH_N_K) kd[j - SGH_K] = v;
+        else if (j >= SGH_MINV && j < SGH_MINV + SGH_N_M) CS.Minv[j - SGH_MINV] = v;
+        else if (j >= SGH_V && j < SGH_V + SG_CD) CS.v[j - SGH_V] = v;
+        else if (j >= SGH_W && j < SGH_W + SG_CD) CS.w[j - SGH_W] = v;
+        else if (j >= SGH_BOX && j < SGH_BOX + SGH_N_BOX) {
+          const int g = (j - SGH_BOX) / SGH_N_BOX1, k = (j - SGH_BOX) % SGH_N_BOX1;
+          if (k < 3) box[3 * g + k] = v; else boxm[9 * g + k - 3] = v;
+        }
+        else if (j == SGH_LIMACT) CS.lim_active = (int)v;
+        else if (j >= SGH_LIMSIGN && j < SGH_LIMSIGN + SGH_N_LIM) lim[j - SGH_LIMSIGN] = v;
       }
-      else if (j == SGH_LIMACT) CS.lim_active = (int)v;
-      else if (j >= SGH_LIMSIGN && j < SGH_LIMSIGN + SGH_N_LIM) lim[j - SGH_LIMSIGN] = v;
     }
   }
   const bool dead = (status & (SG_FLAG_BADQPOS | SG_FLAG_BADQVEL | SG_FLAG_BADQACC)) != 0;
@@ -385,10 +421,10 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
         we[r] = qacc_e[r];
         qa[r] = yc[r] = 0;
         if (e < N && a.finish_integrate) {
-          double m = EL(SGE_MASS, e) + EL(SGE_ARMATURE, e);
-          double den = m + h * EL(SGE_DAMPING, e);
+          double m = msum[r];
+          double den = m + h * damp[r];
           qa[r] = (fsm_p[r] + m * ase[r]) / den;
-          if (H.t0_implicit) { const double cf = EL(SGE_COEF, e); yc[r] = cf / den; Sp += cf * qa[r]; }
+          if (H.t0_implicit) { const double cf = coef[r]; yc[r] = cf / den; Sp += cf * qa[r]; }
         }
       }
       if (H.t0_implicit && a.finish_integrate) {
@@ -423,14 +459,11 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
     } else {
       // ---- chains: imported at the top of the kernel ----
       // ---- elements ----
-      double invm[R], asme[R], coef[R];
+      double invm[R], asme[R], dq[R];   // dq = q - qpos0: formed once, for the capsule centre, the fix row and the neighbour rows
       double L0p = 0, Ldp = 0;
+      if constexpr (!CONSTS_EARLY) load_begin_consts();
 #pragma unroll
-      for (int r = 0; r < R; r++) {
-        int e = r * 64 + lane;
-        coef[r] = e < N ? EL(SGE_COEF, e) : 0.0;
-        L0p += coef[r] * qe[r]; Ldp += coef[r] * ve[r];
-      }
+      for (int r = 0; r < R; r++) { L0p += coef[r] * qe[r]; Ldp += coef[r] * ve[r]; }
       const double L0 = wave_sum2(L0p), Ld = wave_sum2(Ldp);
       const double frc_t0 = -kt0 * (L0 - H.t0_lspring) - H.t0_damping * Ld;
       int unsupported = 0, ns0 = 0, ns1 = 0, touch = 0;
@@ -440,21 +473,21 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
 #pragma unroll
         for (int r = 0; r < R; r++) {
           int e = r * 64 + lane;
-          invm[r] = asme[r] = 0;
+          invm[r] = asme[r] = dq[r] = 0;
           cpos[r][0] = cpos[r][1] = cpos[r][2] = 1e30;
-          if (e < N) {
-            double ax[3] = {EL(SGE_AX, e), EL(SGE_AY, e), EL(SGE_AZ, e)}, m = EL(SGE_MASS, e);
+          if (e < N) {   // (no load in here: the constants came with the prologue's batch)
+            double ax[3] = {eax[r][0], eax[r][1], eax[r][2]}, m = emass[r];
             double bias = -m * dot3(H.gravity, ax);
-            double f = -ke[r] * (qe[r] - EL(SGE_SPRINGREF, e)) - EL(SGE_DAMPING, e) * ve[r] + coef[r] * frc_t0 - bias;
-            invm[r] = 1.0 / (m + EL(SGE_ARMATURE, e));
+            double f = -ke[r] * (qe[r] - esref[r]) - damp[r] * ve[r] + coef[r] * frc_t0 - bias;
+            invm[r] = invm0[r];
             asme[r] = f * invm[r];
             W.fsm[(size_t)env * N + e] = f; W.asme[(size_t)env * N + e] = asme[r];
-            double dq = qe[r] - EL(SGE_QPOS0, e);
-            cpos[r][0] = EL(SGE_GX, e) + ax[0] * dq; cpos[r][1] = EL(SGE_GY, e) + ax[1] * dq; cpos[r][2] = EL(SGE_GZ, e) + ax[2] * dq;
-            if (!(qe[r] > EL(SGE_QLO, e) && qe[r] < EL(SGE_QHI, e))) unsupported = 1;
+            dq[r] = qe[r] - eq0[r];
+            cpos[r][0] = egp[r][0] + ax[0] * dq[r]; cpos[r][1] = egp[r][1] + ax[1] * dq[r]; cpos[r][2] = egp[r][2] + ax[2] * dq[r];
+            if (!(qe[r] > eqlo[r] && qe[r] < eqhi[r])) unsupported = 1;
             Sm.ve[e] = ve[r]; Sm.asme[e] = asme[r]; Sm.we[e] = we[r];
             *(unsigned int*)&Sm.eslot[e][0] = 0u;
-            Sm.as[e] = qe[r];  // scratch until recompute_a: the dense narrowphase below reads other lanes' slider positions
+            Sm.as[e] = dq[r];  // scratch until recompute_a: the narrowphase and the neighbour rows below read other lanes' slider offsets
           }
         }
         SG_T(2);
@@ -526,7 +559,7 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
             if (is_center) v0 = sphere_box(H.center_pos, H.center_radius, bp, bm, sz, H.con_margin, r0) && r0.dist < H.con_margin;
           }
           if (have && !is_center) {
-            const double dq = Sm.as[e] - EL(SGE_QPOS0, e);
+            const double dq = Sm.as[e];
             double cp[3] = {EL(SGE_GX, e) + EL(SGE_AX, e) * dq, EL(SGE_GY, e) + EL(SGE_AY, e) * dq, EL(SGE_GZ, e) + EL(SGE_AZ, e) * dq};
             double cax[3] = {EL(SGE_CX, e), EL(SGE_CY, e), EL(SGE_CZ, e)};
             int mk = capsule_box(cp, cax, H.cap_radius, H.cap_hl, bp, bm, sz, H.con_margin, r0, r1);
@@ -571,40 +604,46 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
       {  // envelope checks (same pairs as the fused kernel).  Finger box against static box (lanes 0 .. npairs-1) and finger box
          // against finger box (lanes 32 .. 35) go through ONE separating-axis test: each lane sets up its pair, then all of
          // them run the 15 axes together (two copies of the test, one per kind of pair, ran one after the other before)
-        int nb = nchain * SG_CG, npairs = nb * H.nstatic;
-        const double *p1 = nullptr, *R1 = nullptr, *s1 = nullptr, *p2 = nullptr, *R2 = nullptr, *s2 = nullptr;
-        double bd = 0;
-        bool pair = false;
-        if (lane < npairs) {
-          int b = lane / H.nstatic, s = lane % H.nstatic, c = b / SG_CG, g = b % SG_CG;
-          if (g < H.chain[c].ngeom) {
-            pair = true;
-            p1 = Sm.boxp[b]; R1 = Sm.boxm[b]; s1 = H.chain[c].g_size[g];
-            p2 = H.st_pos[s]; R2 = H.st_mat[s]; s2 = H.st_size[s];
-            bd = H.chain[c].g_rbound[g] + H.st_rbound[s];
-          }
-        } else if (lane >= 32 && lane < 32 + SG_CG * SG_CG && nchain == 2) {
-          int g = (lane - 32) / SG_CG, g2 = (lane - 32) % SG_CG;
-          if (g < H.chain[0].ngeom && g2 < H.chain[1].ngeom) {
-            int b = g, b2 = SG_CG + g2;
-            pair = true;
-            p1 = Sm.boxp[b]; R1 = Sm.boxm[b]; s1 = H.chain[0].g_size[g];
-            p2 = Sm.boxp[b2]; R2 = Sm.boxm[b2]; s2 = H.chain[1].g_size[g2];
-            bd = H.chain[0].g_rbound[g] + H.chain[1].g_rbound[g2];
-          }
+        // Every lane with a test names its operands by INDEX -- its own box b1 (LDS), and a static s (the plan header, constant address
+        // space) or a second box b2 (LDS) -- and loads them all, both candidates for the second operand, in ONE batch of typed loads;
+        // lanes without a test load box 0 and static 0 and drop them.  (Six generic pointers per lane, LDS or constant memory by the
+        // kind of pair, made every operand a flat load behind a full wait, each kind's set-up a round trip of its own.)
+        const int nb = nchain * SG_CG, nst = H.nstatic, npairs = nb * nst, nst1 = nst > 0 ? nst : 1;
+        const bool k_static = lane < npairs, k_boxes = !k_static && lane >= 32 && lane < 32 + SG_CG * SG_CG && nchain == 2;
+        const bool k_plane = lane >= 48 && lane < 48 + SG_MAXCH * SG_CG && H.has_plane;
+        static_assert(SG_MAXSTATIC * SG_MAXCH * SG_CG <= 48, "a plane lane has no pair");
+        const int b1 = k_static ? lane / nst1 : (k_boxes ? (lane - 32) / SG_CG : (k_plane ? lane - 48 : 0));
+        const int b2 = k_boxes ? SG_CG + (lane - 32) % SG_CG : 0, s = k_static ? lane % nst1 : 0;
+        const int c1 = b1 / SG_CG, g1 = b1 % SG_CG, c2 = b2 / SG_CG, g2 = b2 % SG_CG;
+        const SG_CONSTAS SgChain& C1 = H.chain[c1];
+        const SG_CONSTAS SgChain& C2 = H.chain[c2];
+        double p1[3], R1[9], s1[3], p2[3], R2[9], s2[3];
+        const int ng1 = C1.ngeom, ng2 = C2.ngeom;
+        const double rb1 = C1.g_rbound[g1], rb2 = k_boxes ? C2.g_rbound[g2] : H.st_rbound[s];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          p1[k] = Sm.boxp[b1][k]; s1[k] = C1.g_size[g1][k];
+          const double pb = Sm.boxp[b2][k], ps = H.st_pos[s][k], sb = C2.g_size[g2][k], ss = H.st_size[s][k];
+          p2[k] = k_boxes ? pb : ps; s2[k] = k_boxes ? sb : ss;
         }
-        if (pair) {
-          double dif[3] = {p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]};
-          if (dot3(dif, dif) <= bd * bd && box_box_overlap(p1, R1, s1, p2, R2, s2, 0)) unsupported = 1;
+#pragma unroll
+        for (int k = 0; k < 9; k++) {
+          R1[k] = Sm.boxm[b1][k];
+          const double mb = Sm.boxm[b2][k], ms = H.st_mat[s][k];
+          R2[k] = k_boxes ? mb : ms;
         }
-        if (lane >= 48 && lane < 48 + SG_MAXCH * SG_CG && H.has_plane) {
-          int b = lane - 48, c = b / SG_CG, g = b % SG_CG;
-          if (c < nchain && g < H.chain[c].ngeom) {
-            double dif[3] = {Sm.boxp[b][0] - H.plane_pos[0], Sm.boxp[b][1] - H.plane_pos[1], Sm.boxp[b][2] - H.plane_pos[2]}, ext = 0;
-            for (int k = 0; k < 3; k++)
-              ext += H.chain[c].g_size[g][k] * fabs(H.plane_normal[0] * Sm.boxm[b][k] + H.plane_normal[1] * Sm.boxm[b][3 + k] + H.plane_normal[2] * Sm.boxm[b][6 + k]);
-            if (dot3(dif, H.plane_normal) - ext <= 0) unsupported = 1;
-          }
+        const bool pair = (k_static && g1 < ng1) || (k_boxes && g1 < ng1 && g2 < ng2);
+        const double bd = rb1 + rb2;
+        const double dif[3] = {p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]};
+        const bool near = pair && dot3(dif, dif) <= bd * bd;
+        if (__ballot(near)) {   // (the bounding spheres are all that runs while no finger box is near a static box or the other finger's)
+          if (near && box_box_overlap(p1, R1, s1, p2, R2, s2, 0)) unsupported = 1;
+        }
+        if (k_plane && c1 < nchain && g1 < ng1) {
+          double dp[3] = {p1[0] - H.plane_pos[0], p1[1] - H.plane_pos[1], p1[2] - H.plane_pos[2]}, ext = 0;
+          for (int k = 0; k < 3; k++)
+            ext += s1[k] * fabs(H.plane_normal[0] * R1[k] + H.plane_normal[1] * R1[3 + k] + H.plane_normal[2] * R1[6 + k]);
+          if (dot3(dp, H.plane_normal) - ext <= 0) unsupported = 1;
         }
         special = __ballot(unsupported) != 0;
       }
@@ -630,7 +669,7 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
           GL.gas = (double*)&Sm.stage[0][0] + SG_GEN_MAXCON + SG_GEN_MAXCON / 2;
           GL.tmp = (double*)&Sm.stage[0][0] + 8 * SG_GEN_MAXCON; GL.gg = GL.tmp + 96;
           GL.boxp = Sm.boxp; GL.boxm = Sm.boxm; GL.K = Sm.K; GL.cs = Sm.cs;
-          GL.qe = Sm.as; GL.ve = Sm.ve; GL.asme = Sm.asme; GL.we = Sm.we;
+          GL.dq = Sm.as; GL.ve = Sm.ve; GL.asme = Sm.asme; GL.we = Sm.we;
           int gfl = 0, gtouch = 0;
           ngen = sg_gen_phase(a, *a.H, env, GL, &gfl, &gtouch);
           flags |= gfl;
@@ -683,7 +722,7 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
           if (sl >= 0) {
             ax[0] = EL(SGE_AX, sl); ax[1] = EL(SGE_AY, sl); ax[2] = EL(SGE_AZ, sl);
             ve_ = Sm.ve[sl]; as_ = Sm.asme[sl]; we_ = Sm.we[sl];
-            im = 1.0 / (EL(SGE_MASS, sl) + EL(SGE_ARMATURE, sl)); bw = EL(SGE_BINVW, sl);
+            im = EL(SGD_INVM, sl); bw = EL(SGE_BINVW, sl);
           }
           contact_build(c, rec, Sm.K[half], nd, CS.Minv, CS.v, CS.qacc_smooth, CS.w, C.b_invw_tran[bi], sl, ax, ve_, as_, we_, im, bw, *a.H);
           csl_[k] = sl; cinvm[k] = c.invm;
@@ -788,13 +827,31 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
       // ---- equality rows ----
       double eqR[R], eqb[R], eqf[R];
       double tbp = 0, tjp = 0, tAp = 0;
+      // the stage's constants and tables, one batch of unconditional loads at its top: the fix rows' weights and -- neighbour-row models --
+      // per element its rows' partners, ids and summed weights (SGD_NBINVW: the host's sum) and the ids of the rows that have it as second
+      // joint, which recompute_a gathers by.  (Each was a load-then-wait group of its own, the partner's weight and qpos0 a second trip
+      // behind the table's word.)
+      double einvw[R];
+      [[maybe_unused]] int nbe2l[R][3], nbidl[R][3], nbin[R][3];
+      [[maybe_unused]] double nbw[R][3];
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        einvw[r] = EL(SGE_INVW, ec[r]);
+        if constexpr (NB) {
+#pragma unroll
+          for (int d = 0; d < 3; d++) {
+            nbe2l[r][d] = nbtabc[d * N + ec[r]]; nbidl[r][d] = nbtabc[(3 + d) * N + ec[r]]; nbin[r][d] = nbtabc[(6 + d) * N + ec[r]];
+            nbw[r][d] = EL(SGD_NBINVW + d, ec[r]);
+          }
+        }
+      }
 #pragma unroll
       for (int r = 0; r < R; r++) {
         int e = r * 64 + lane;
         eqR[r] = 1; eqb[r] = 0; eqf[r] = 0;
         if (e < N) {
-          double pos = qe[r] - EL(SGE_QPOS0, e), imp = impedance(H.eqj_solimp, pos, 0);
-          eqR[r] = fmax(SG_MINVAL, (1 - imp) / imp * EL(SGE_INVW, e));
+          double pos = dq[r], imp = impedance(H.eqj_solimp, pos, 0);
+          eqR[r] = fmax(SG_MINVAL, (1 - imp) / imp * einvw[r]);
           double aref = -H.eqj_B * ve[r] - H.eqj_K * imp * pos;
           eqb[r] = asme[r] - aref;
           eqf[r] = -(we[r] - aref) / eqR[r];
@@ -817,6 +874,11 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
       // work space instead made ROCm 7.2.0's register allocator crash on that instantiation under the iterative-ilp scheduler)
       [[maybe_unused]] double nbbb[R][3];
       [[maybe_unused]] double* const gnbf = W.nbf + (size_t)env * 3 * N;
+      // ... and, where the LDS block has room for them within eight workgroups per CU (SG_PHASE_NBF_LDS: one and two element rounds),
+      // in LDS by row id for that gather: a store and a dependent round trip to L2 less per recompute_a, which runs twice when the warm start
+      // loses.  The work-space copy stays: the solver takes the forces from there
+      constexpr bool NBF_LDS = SG_PHASE_NBF_LDS(R, NB);
+      static_assert(!NBF_LDS || sizeof(Smem2<R, CPL, NB>) <= SG_PHASE_LDS_BUDGET, "the forces' LDS copy must leave eight workgroups per CU");
 #pragma unroll
       for (int r = 0; r < R; r++)
 #pragma unroll
@@ -827,7 +889,7 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
         // block's lane pair in its round of the wavefront's stream (W.cst) -- the solver reads them as one coalesced 16-byte load per
         // lane and round instead of keeping them in LDS, which is what lets four of its workgroups share a CU for the ball and the
         // cylinder (218 / 192 elements).  Rows that do not exist hold 0: their update is a no-op.
-        const double im0 = 1.0 / (EL(SGE_MASS, 0) + EL(SGE_ARMATURE, 0));
+        const double im0 = EL(SGD_INVM, 0);
         const SG_CONSTAS int* const cposc = (const SG_CONSTAS int*)a.cpos;
         // Rows pipeline: the rows leave READY for the solver, which then stages them without a look-up, a product or a division -- per row its
         // state g = b + R f of the warm-start force (one fma, as the solver contracted it) and its step factor c, element-major and dense
@@ -842,15 +904,16 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
             if (ready) c4[0] = sg_div(im0, im0 + eqR[r]);
 #pragma unroll
             for (int d = 0; d < 3; d++) {
-              const int e2 = nbtabc[d * N + e];
+              const int e2 = nbe2l[r][d];
               if (e2 >= 0) {
-                const int id = nbtabc[(3 + d) * N + e];
-                const double pos = (qe[r] - EL(SGE_QPOS0, e)) - (Sm.as[e2] - EL(SGE_QPOS0, e2)), imp = impedance(H.eqj_solimp, pos, 0);
-                const double Rr = fmax(SG_MINVAL, (1 - imp) / imp * (EL(SGE_INVW, e) + EL(SGE_INVW, e2)));
+                const int id = nbidl[r][d];
+                const double pos = dq[r] - Sm.as[e2], imp = impedance(H.eqj_solimp, pos, 0);   // (Sm.as: the partner's q - qpos0, by its own lane)
+                const double Rr = fmax(SG_MINVAL, (1 - imp) / imp * nbw[r][d]);
                 const double aref = -H.eqj_B * (ve[r] - Sm.ve[e2]) - H.eqj_K * imp * pos;
                 const double bb = (asme[r] - Sm.asme[e2]) - aref, ff = -((we[r] - Sm.we[e2]) - aref) / Rr;
                 nbe2[r][d] = e2; nbid[r][d] = id; nbc0[r][d] = ff * (0.5 * Rr * ff + bb);
                 nbff[r][d] = ff; gnbf[id] = ff;
+                if constexpr (NBF_LDS) Sm.nbf[id] = ff;
                 nbbb[r][d] = bb;
                 if (ready) { g3[d] = fma(Rr, ff, bb); c4[1 + d] = sg_div(im0, 2.0 * im0 + Rr); }
                 else { W.nbb[(size_t)env * 3 * N + id] = bb; W.nbR[(size_t)env * 3 * N + id] = Rr; }
@@ -893,9 +956,13 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
             if constexpr (NB) {  // + its own neighbour rows (J = +1), - the rows that have it as second joint (J = -1), in row order per side
 #pragma unroll
               for (int d = 0; d < 3; d++) if (nbid[r][d] >= 0) fe += nbff[r][d];
-              double fin[3];   // (the three loads go out together: one round trip to L2, behind the barrier that made the stores visible)
+              double fin[3];   // (LDS where the block has room for the forces; else three loads that go out together: one round trip to L2)
 #pragma unroll
-              for (int d = 0; d < 3; d++) { const int ii = nbtabc[(6 + d) * N + e]; fin[d] = ii >= 0 ? gnbf[ii] : 0.0; }
+              for (int d = 0; d < 3; d++) {
+                const int ii = nbin[r][d];
+                if constexpr (NBF_LDS) fin[d] = ii >= 0 ? Sm.nbf[ii] : 0.0;
+                else fin[d] = ii >= 0 ? gnbf[ii] : 0.0;
+              }
 #pragma unroll
               for (int d = 0; d < 3; d++) fe -= fin[d];
             }
@@ -1000,6 +1067,7 @@ __device__ __forceinline__ void sg_phase_env(const SgPhaseArgs& a, const int env
             for (int d = 0; d < ND; d++)
               if (nbid[r][d] >= 0) {
                 nbff[r][d] = 0.0; gnbf[nbid[r][d]] = 0.0;
+                if constexpr (NBF_LDS) Sm.nbf[nbid[r][d]] = 0.0;
                 if (a.rowlayout) W.nbb[sg_eq_nb_index((size_t)env, r * 64 + lane, d, N)] = nbbb[r][d];   // g of f = 0 is b itself
               }
           }

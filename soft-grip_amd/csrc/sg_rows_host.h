@@ -69,6 +69,27 @@ inline void sg_rows_tables(const SgPlan& P, SgRowsTables* T) {
     if (P.sched[i].e < H.nelem) T->cpos[P.sched[i].e] = (int)(i / SG_EQ_SLOTS) * 128 + 4 * (int)(i % SG_EQ_SLOTS);
 }
 
+// The element table as the batch uploads it (SgPhaseArgs::elem): the plan's fields and the derived ones behind them (enum SgElemDerived,
+// sg_rows_layout.h).  The model blob and SgPlan::elem stay as they are; every kernel that indexes the plan's fields by f * nelem + e reads
+// the same words as before.  Each derived value is one operation on doubles held in variables -- nothing a compiler could contract.
+inline std::vector<double> sg_rows_elem_table(const SgPlan& P) {
+  const int N = P.h.nelem;
+  std::vector<double> t(P.elem);
+  t.resize(sg_elem_table_doubles(N), 0.0);
+  for (int e = 0; e < N; e++) {
+    const double m = t[sg_elem_table_index(SGE_MASS, e, N)], arm = t[sg_elem_table_index(SGE_ARMATURE, e, N)];
+    const double msum = m + arm;
+    t[sg_elem_table_index(SGD_MSUM, e, N)] = msum;
+    t[sg_elem_table_index(SGD_INVM, e, N)] = 1.0 / msum;
+    if (P.h.nnb > 0)
+      for (int d = 0; d < 3; d++) {
+        const int e2 = P.nbtab[(size_t)d * N + e];   // out_e2[d][e], -1: no such row
+        if (e2 >= 0) t[sg_elem_table_index(SGD_NBINVW + d, e, N)] = t[sg_elem_table_index(SGE_INVW, e, N)] + t[sg_elem_table_index(SGE_INVW, e2, N)];
+      }
+  }
+  return t;
+}
+
 // Every buffer of SgWork with its element count, in one place: f(&w.member, count) for each, until one call returns false.  rounds =
 // ceil(nelem / 64); legacy: the build has the split pipeline's solver (its contact records, 126 MB at 4096 envs, are otherwise not
 // allocated).  SgWork::secprof is not here: it belongs to the batch, whichever pipeline runs.  A count of 0 is a buffer no kernel of

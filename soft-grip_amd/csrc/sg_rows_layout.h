@@ -133,6 +133,19 @@ __host__ __device__ constexpr size_t sg_eq_rec_index(size_t env, int u, int N, s
   return d == 0 ? sg_eq_fix_index(envc, e, N) : sg_eq_nb_index(envc, e, d - 1, N);
 }
 
+// ---- the element table on the device (SgPhaseArgs::elem, SgPgsArgs::elem): SgPlan::elem's SGE_NFIELD fields of nelem doubles each, then the
+// fields the HOST derives from them once per model (sg_rows_elem_table, sg_rows_host.h) -- per-model arithmetic the phase kernel redid for
+// every element in every substep.  Each is ONE IEEE operation on table values, the operation the kernel performed: the bits are the kernel's
+// (tests/emu/sg_phase_table_test.cpp).  Field f of element e is at f * nelem + e, as in SgPlan::elem.
+enum SgElemDerived : int {
+  SGD_MSUM = SGE_NFIELD,   // SGE_MASS + SGE_ARMATURE: the slider's 1 x 1 mass-matrix block
+  SGD_INVM,                // 1 / SGD_MSUM (element 0's is the step factors' im0: equal masses, sg_plan_build)
+  SGD_NBINVW,              // + d, d = 0 .. 2: SGE_INVW of e + SGE_INVW of the partner of e's d-th neighbour row; 0 where there is no such row
+  SGD_NFIELD = SGD_NBINVW + 3
+};
+__host__ __device__ constexpr size_t sg_elem_table_index(int f, int e, int N) { return (size_t)f * (size_t)N + (size_t)e; }
+__host__ __device__ constexpr size_t sg_elem_table_doubles(int N) { return (size_t)SGD_NFIELD * (size_t)N; }
+
 // ---- chain hand-off record (SgWork::chh, SG_CHW doubles per stream): written by sg_chain_kernel's BEGIN, read by its FINISH and by the phase kernel ----
 #define SG_CHW 160
 enum { SGH_QSM = 0, SGH_QFRC = 4, SGH_ACTDOT = 8, SGH_M = 9, SGH_K = 25, SGH_MINV = 73, SGH_V = 89, SGH_W = 93, SGH_BOX = 97,

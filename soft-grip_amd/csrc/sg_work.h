@@ -107,6 +107,10 @@ static_assert(offsetof(ChainLds2, lim_R) - offsetof(ChainLds2, lim_sign) == (SGH
 
 #define SG_PHASE_SLIM(R) ((R) >= 4)   // the pair list and the slot pushes live in the work space (SgWork::gpairs16, gcval), not in LDS
 #define SG_PAIRS_CAP(R) (SG_MAXCH * SG_CG * ((R) * 64 + 2))
+#define SG_PHASE_LDS_BUDGET (160 * 1024 / 8)   // bytes of LDS per workgroup at eight workgroups per CU (two wavefronts per SIMD)
+// the neighbour rows' warm-start forces by row id (< 3 nelem) also live in LDS, for the gather of recompute_a: where the block stays within the
+// budget with them -- one and two element rounds (the box: 20 064 bytes); three and four (cylinder, ball) gather from the work space
+#define SG_PHASE_NBF_LDS(R, NB) ((NB) && (R) <= 2)
 template <int R, int CPL, bool NB>
 struct Smem2 {
   ChainKin K[SG_MAXCH];
@@ -117,6 +121,7 @@ struct Smem2 {
   unsigned short pairs[SG_PHASE_SLIM(R) ? 4 : SG_PAIRS_CAP(R)];  // broadphase survivors, (box << 12) | element, in contact order
   unsigned char eslot[R * 64][SG_MAXCH * SG_CG];          // per element and box: first contact slot (< 64) | (contact count << 6)
   double cval[SG_PHASE_SLIM(R) ? 1 : SG_MAXCH * 32 * CPL];   // per contact slot [chain][32 CPL]: invm * Js' f (its push on the slider)
+  double nbf[SG_PHASE_NBF_LDS(R, NB) ? 3 * R * 64 : 1];      // neighbour rows' warm-start forces by row id (SG_PHASE_NBF_LDS)
 };
 #define SG_PAIR_CENTER 0xFFF  // element code of the object's centre sphere
 
