@@ -270,6 +270,37 @@ int sg_ray(sg_batch* b, const int32_t* env_ids, int n_ids, int n_rays, const dou
            const int32_t* ray_body, const int32_t* ray_exclude, int cat_mask, double max_dist, int flags,
            double* dist, int32_t* geomid, double* normal, void* stream);
 
+/* ---- velocity, tendon and energy read-outs: replaces reading data.cvel / mj_objectVelocity, data.ten_length / data.ten_velocity and
+ * data.energy after mj_forward.  Pure functions of the batch's CURRENT qpos and qvel and of its per-env stiffness; one kernel walks the
+ * kinematic tree once per call, whichever of the three is asked.  Common to all three: env_ids as in sg_get_poses (HOST, NULL = all);
+ * outputs are device pointers, any may be NULL; the calls read the batch, change nothing in it and do not synchronise the host; an env
+ * whose qpos or qvel holds a NaN or inf gets NaN in every output and disturbs no other env.  No atomics: two calls give the same bits,
+ * and an env's bits do not depend on which envs are listed beside it or in what order.
+ * SG_ERR_INVALID (checked before anything touches the device): NULL batch, n_ids <= 0, an env id out of range.  SG_ERR_MODEL: a model the
+ * pose read-out cannot run, a tendon with wraps other than joints only or sites only, and a model of more than 627 bodies (a body's pose
+ * and twist are 13 doubles of the kernel's LDS block, which stays within 64 KB).
+ *
+ * Velocities: ang, lin, com_lin [n_ids][nbody][3] each, world axes.  ang: the body's angular velocity.  lin: the linear velocity of the
+ *   body frame's origin, the point xpos that sg_get_poses reports.  com_lin: the linear velocity of the body's centre of mass
+ *   xpos + R body_ipos.  Body 0 (the world) is zero.  THE DEFINING PROPERTY: the outputs are the time derivative of what sg_get_poses
+ *   returns when qpos moves the way qvel says (mj_integratePos) -- slide and hinge joints at rate qvel; a free joint's position at its
+ *   three linear components (world frame) and its quaternion at 1/2 q (0, w), w the three angular components in the BODY frame (the
+ *   layout sg_get_state documents).  The joints of a body are taken in joint order, each hinge about its anchor as mj_kinematics places
+ *   it.  The velocity of any point p fixed on a body: lin + ang x (p - xpos).
+ * Tendons: length, velocity [n_ids][ntendon].  A fixed tendon: sum of coef q and of coef qvel over its joint wraps.  A spatial tendon
+ *   (site wraps): the sum of the site-to-site segment lengths at this call's poses and its time derivative, the sum over segments of
+ *   unit segment . (v_next - v_prev); a segment shorter than 1e-15 counts its length and no velocity.
+ * Energy: energy [n_ids][4] = gravity, joint springs, tendon springs, kinetic (MuJoCo's data.energy: the sum of the first three, the
+ *   fourth).  Gravity: minus the sum over bodies >= 1 of m g . xipos.  Joint springs: the sum of 1/2 k (q - qpos_spring)^2 over slide and
+ *   hinge joints (a free joint has none).  Tendon springs: the sum of 1/2 k (L - tendon_lengthspring)^2.  k is what the next sg_step
+ *   would use for this env: its sg_set_stiffness value on the listed joints and tendons, the model's own elsewhere; ordering is stream
+ *   ordering, so a call after sg_set_stiffness with a device k on the same stream sees the new k.  Kinetic:
+ *   1/2 sum over bodies of (m |com_lin|^2 + w' R I R' w), I = body_imat about the centre of mass, plus 1/2 sum of dof_armature qvel^2:
+ *   1/2 qvel' M qvel with the mass matrix of mj_crb. */
+int sg_get_velocities(sg_batch* b, const int32_t* env_ids, int n_ids, double* ang, double* lin, double* com_lin, void* stream);
+int sg_get_tendons(sg_batch* b, const int32_t* env_ids, int n_ids, double* length, double* velocity, void* stream);
+int sg_get_energy(sg_batch* b, const int32_t* env_ids, int n_ids, double* energy, void* stream);
+
 /* The recurrence of one direction of one fp64 LSTM layer with H = 128 hidden units (csrc/sg_lstm.hip), for the Conv-LSTM and
  * Conv-BiLSTM regressors (soft-grip_amd/lstm.py).  Keras' conventions: gate order i, f, g (the candidate), o along the 4H axis, sigmoid
  * for i, f and o, tanh for g and for the cell, row-major kernels.  The caller keeps what is regular -- the input projection

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "sg_readout.h"
+#include "sg_dyn.h"
 #include "sg_skin.h"
 #include "sg_rows_host.h"   // (sg_work.h, sg_plan.h)
 #include "sg_devmem.h"   // SgArena, SgScratch: the owners of every device buffer below (after the HIP runtime's declarations)
@@ -32,6 +33,7 @@ struct sg_model {
   long long tree_cws = 0;    // sgt::cws_doubles: each walks lds_carve, so once per model)
   SgKinHost kin;    // kinematics table of sg_get_poses / sg_render
   SgConHost con;    // candidate pairs, margins and bounding radii of sg_get_contacts
+  SgDynHost dyn;    // masses, springs, sites and tendons of sg_get_velocities / sg_get_tendons / sg_get_energy
   SgSkinHost skin;  // the composite's skin (sg_skin.h; nvert == 0: none): sg_model_set_skin, drawn by sg_render_ex
 };
 
@@ -111,6 +113,9 @@ struct sg_batch {
   SgScratch<double> ray_vtx;                                      // [n_ids][nvert][3] the skin's vertices of the last SG_RAY_SKIN call
   const int* skin_vis = nullptr;                                  // [skin_nvis] the geoms the skin does not replace (in skin_mem, with skin_dev)
   int skin_nvis = 0;
+  // velocity, tendon and energy read-outs: the dynamics table
+  double* dyn_d = nullptr;
+  int* dyn_i = nullptr;
   ~sg_batch() {   // (on the batch's device: sg_batch_destroy.  The arenas and scratch buffers free themselves)
     for (auto& e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (auto& e : ev_pgs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }

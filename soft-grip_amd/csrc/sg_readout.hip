@@ -1,6 +1,6 @@
 // sg_readout.hip -- the read-out half of the C ABI (include/softgrip.h): sg_get_poses, sg_render / sg_render_ex and the skin,
-// sg_get_contacts, sg_ray, with the kernels they launch (the three *_kernel*.h files, whose device assembly is sg_readout.device.s) and
-// the host builders of their per-model tables (sg_readout.h).  None of them writes the state: every pipeline is served.  No CPU fallback.
+// sg_get_contacts, sg_ray, sg_get_velocities / sg_get_tendons / sg_get_energy, with the kernels they launch (the *_kernel*.h files, whose
+// device assembly is sg_readout.device.s) and the host builders of their per-model tables (sg_readout.h, sg_dyn.h).  None of them writes the state: every pipeline is served.  No CPU fallback.
 #include <algorithm>
 #include <cstring>
 #include <type_traits>
@@ -11,6 +11,7 @@
 #include "sg_contacts_kernel.h"
 #include "sg_ray_kernels.h"
 #include "sg_ray_skin_kernels.h"
+#include "sg_dyn_kernel.h"
 
 // ---- the builders sg_model_create calls (sg_readout.h) ----
 // an array of the blob as `var`, its length in c (want >= 0: that many elements), or the builder ends with T->err set
@@ -165,6 +166,72 @@ void sgc_from_blob(const void* blob, size_t nbytes, const SgKinHost& K, SgConHos
   C->gaux.resize(2 * ng);
   for (int g = 0; g < ng; g++) { C->gaux[2 * g] = gmargin[g]; C->gaux[2 * g + 1] = grb[g]; }
   C->ok = true;
+}
+
+// the dynamics table (sg_dyn.h): per body mass, body_ipos, body_imat; per joint its dof, qpos_spring and stiffness; per dof the armature;
+// the sites, the tendons and their wraps; gravity.  Tendons of joint wraps only or of site wraps only: the class the blob allows
+void sgd_build(const void* blob, size_t nbytes, const SgKinHost& K, SgDynHost* T) {
+  if (!K.ok) { T->err = K.err; return; }
+  const long long nb = K.o.nbody, nj = K.o.njnt, nq = K.o.nq;
+  long long c = 0, nv = 0, ns = 0, nt = 0, nw = 0;
+  if (nb > SGD_MAXBODY) { T->err = "more than " + std::to_string(SGD_MAXBODY) + " bodies"; return; }
+  SG_FIELD(T, mass, "body_mass", SG_DT_F64, nb);
+  SG_FIELD(T, ipos, "body_ipos", SG_DT_F64, 3 * nb);
+  SG_FIELD(T, imat, "body_imat", SG_DT_F64, 9 * nb);
+  SG_FIELD(T, jstiff, "jnt_stiffness", SG_DT_F64, nj);
+  SG_FIELD(T, qspring, "qpos_spring", SG_DT_F64, nq);
+  SG_FIELD(T, arm, "dof_armature", SG_DT_F64, -1);
+  nv = c;
+  SG_FIELD(T, sbody, "site_bodyid", SG_DT_I32, -1);
+  ns = c;
+  SG_FIELD(T, spos, "site_pos", SG_DT_F64, 3 * ns);
+  SG_FIELD(T, tadr, "tendon_adr", SG_DT_I32, -1);
+  nt = c;
+  SG_FIELD(T, tnum, "tendon_num", SG_DT_I32, nt);
+  SG_FIELD(T, tstiff, "tendon_stiffness", SG_DT_F64, nt);
+  SG_FIELD(T, tspring, "tendon_lengthspring", SG_DT_F64, nt);
+  SG_FIELD(T, wtype, "wrap_type", SG_DT_I32, -1);
+  nw = c;
+  SG_FIELD(T, wobj, "wrap_objid", SG_DT_I32, nw);
+  SG_FIELD(T, wprm, "wrap_prm", SG_DT_F64, nw);
+  SG_FIELD(T, optd, "opt_d", SG_DT_F64, -1);
+  if (c < 4) { T->err = "model blob lacks opt_d"; return; }
+  long long ca = 0;
+  const int* dadr = (const int*)sg_blob_find(blob, nbytes, "jnt_dofadr", SG_DT_I32, &ca);   // (only blobs with a free joint carry it)
+  if (dadr && ca != nj) dadr = nullptr;
+  const int* jtype = K.ints.data() + K.o.jtype;
+  std::vector<int> jd(nj);
+  std::vector<double> jspring(nj);
+  for (int j = 0; j < nj; j++) {
+    jd[j] = dadr ? dadr[j] : j;
+    if (jd[j] < 0 || jd[j] + (jtype[j] == SG_JNT_FREE ? 6 : 1) > nv) { T->err = "joint dof address out of range"; return; }
+    jspring[j] = qspring[K.ints[K.o.jqadr + j]];
+  }
+  for (int s = 0; s < ns; s++)
+    if (sbody[s] < 0 || sbody[s] >= nb) { T->err = "site body out of range"; return; }
+  for (int t = 0; t < nt; t++) {
+    if (tadr[t] < 0 || tnum[t] < 1 || (long long)tadr[t] + tnum[t] > nw) { T->err = "tendon wrap address out of range"; return; }
+    const int type = wtype[tadr[t]];
+    if (type != SG_WRAP_JOINT && type != SG_WRAP_SITE) { T->err = "tendon wraps other than joints and sites"; return; }
+    for (int w = tadr[t]; w < tadr[t] + tnum[t]; w++) {
+      if (wtype[w] != type) { T->err = "a tendon that mixes joint and site wraps"; return; }
+      if (wobj[w] < 0 || wobj[w] >= (type == SG_WRAP_JOINT ? nj : ns)) { T->err = "tendon wrap object out of range"; return; }
+      if (type == SG_WRAP_JOINT && jtype[wobj[w]] == SG_JNT_FREE) { T->err = "a fixed tendon over a free joint"; return; }
+    }
+  }
+  SgDynOff& o = T->o;
+  o.nv = (int)nv; o.nsite = (int)ns; o.ntendon = (int)nt; o.nwrap = (int)nw;
+  std::vector<double>& D = T->dbl;
+  auto putd = [&](const double* p, size_t n) { int at = (int)D.size(); D.insert(D.end(), p, p + n); return at; };
+  o.bmass = putd(mass, nb); o.bipos = putd(ipos, 3 * nb); o.bimat = putd(imat, 9 * nb); o.jspring = putd(jspring.data(), nj);
+  o.jstiff = putd(jstiff, nj); o.arm = putd(arm, nv); o.spos = putd(spos, 3 * ns); o.wprm = putd(wprm, nw); o.tstiff = putd(tstiff, nt);
+  o.tspring = putd(tspring, nt); o.grav = putd(optd + 1, 3);
+  std::vector<int>& I = T->ints;
+  auto puti = [&](const int* p, size_t n) { int at = (int)I.size(); I.insert(I.end(), p, p + n); return at; };
+  o.jdof = puti(jd.data(), nj); o.sbody = puti(sbody, ns); o.tadr = puti(tadr, nt); o.tnum = puti(tnum, nt); o.wtype = puti(wtype, nw);
+  o.wobj = puti(wobj, nw);
+  if (I.empty()) I.push_back(0);   // (a model without joints, sites and tendons: the upload still has something to hold)
+  T->ok = true;
 }
 
 // ---- the entry points' common prologue ----
@@ -512,6 +579,49 @@ int sg_ray(sg_batch* b, const int32_t* env_ids, int n_ids, int n_rays, const dou
   }
   HIPCHK(hipGetLastError());
   return SG_OK;
+}
+
+// ---- velocity, tendon and energy read-outs: one walk (sg_dyn_kernel), whichever outputs the entry point fn passes ----
+static int dyn(const char* fn, sg_batch* b, const int32_t* env_ids, int n_ids, double* ang, double* lin, double* com_lin, double* ten_len, double* ten_vel,
+               double* energy, void* stream) {
+  // (argument checks first, in an order that lets each be reached without a device)
+  if (n_ids <= 0) return fail(SG_ERR_INVALID, std::string(fn) + ": n_ids must be positive");
+  if (!b) return fail(SG_ERR_INVALID, std::string(fn) + ": null batch");
+  const SgKinHost& K = b->m->kin;
+  const SgDynHost& Dn = b->m->dyn;
+  const SgPlanHeader& H = b->m->plan.h;
+  if (K.ok && !Dn.ok) return fail(SG_ERR_MODEL, std::string(fn) + ": " + Dn.err);
+  if (K.ok && (Dn.o.nv != H.nv || K.o.nq != H.nq || K.o.njnt != H.njnt || Dn.o.ntendon != H.ntendon))   // (the strides of qpos / qvel and the masks' lengths)
+    return fail(SG_ERR_MODEL, std::string(fn) + ": the blob's joint, dof or tendon counts differ from the plan's");
+  Readout r{b, fn, (hipStream_t)stream};
+  if (int rc = r.prepare(env_ids, n_ids)) return rc;
+  if (!ang && !lin && !com_lin && !ten_len && !ten_vel && !energy) return SG_OK;
+  if (!b->dyn_d) {   // (on the side, as the pose tables)
+    SgArena A;
+    double* dd = nullptr;
+    int* di = nullptr;
+    if (!(A.upload(&dd, Dn.dbl) && A.upload(&di, Dn.ints))) return devmem_fail(A.nomem, std::string(fn) + " (dynamics tables)");
+    A.give_to(b->mem);
+    b->dyn_d = dd; b->dyn_i = di;
+  }
+  SgDynArgs a;
+  a.D = b->kin_d; a.I = b->kin_i; a.o = K.o; a.DD = b->dyn_d; a.DI = b->dyn_i; a.d = Dn.o;
+  a.qpos = b->qpos; a.qvel = b->qvel; a.kenv = b->kenv; a.kmask_jnt = b->kmask_jnt; a.kmask_ten = b->kmask_ten;
+  a.env_ids = r.dids; a.n_ids = n_ids;
+  a.ang = ang; a.lin = lin; a.com_lin = com_lin; a.ten_len = ten_len; a.ten_vel = ten_vel; a.energy = energy;
+  hipLaunchKernelGGL(sg_dyn_kernel, dim3(n_ids), dim3(64), sizeof(double) * SGD_REC * K.o.nbody, r.s, a);   // (<= 64 KB: SGD_MAXBODY)
+  HIPCHK(hipGetLastError());
+  return SG_OK;
+}
+
+int sg_get_velocities(sg_batch* b, const int32_t* env_ids, int n_ids, double* ang, double* lin, double* com_lin, void* stream) {
+  return dyn("sg_get_velocities", b, env_ids, n_ids, ang, lin, com_lin, nullptr, nullptr, nullptr, stream);
+}
+int sg_get_tendons(sg_batch* b, const int32_t* env_ids, int n_ids, double* length, double* velocity, void* stream) {
+  return dyn("sg_get_tendons", b, env_ids, n_ids, nullptr, nullptr, nullptr, length, velocity, nullptr, stream);
+}
+int sg_get_energy(sg_batch* b, const int32_t* env_ids, int n_ids, double* energy, void* stream) {
+  return dyn("sg_get_energy", b, env_ids, n_ids, nullptr, nullptr, nullptr, nullptr, nullptr, energy, stream);
 }
 
 }  // extern "C"

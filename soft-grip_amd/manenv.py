@@ -402,6 +402,22 @@ class ManEnv(Env):
         out["geom_names"] = [n or "" for n in self.model.geom_names]
         return out
 
+    def get_velocities(self, env_ids=None):
+        """body velocities of the listed envs (None: all) at the current state, world axes: NativeBatch.velocities' dict of device
+        tensors ang, lin, com_lin [k, nbody, 3] -- the time derivative of the poses when qpos moves as qvel says (data.cvel /
+        mj_objectVelocity).  A point p fixed on body i moves at lin[:, i] + cross(ang[:, i], p - xpos[:, i])."""
+        return self.env.velocities(env_ids=env_ids)
+
+    def get_tendons(self, env_ids=None):
+        """tendon travel and its rate of the listed envs (None: all) at the current state (data.ten_length, data.ten_velocity):
+        NativeBatch.tendons' dict of device tensors length, velocity [k, ntendon]"""
+        return self.env.tendons(env_ids=env_ids)
+
+    def get_energy(self, env_ids=None):
+        """[k, 4] device tensor of the listed envs (None: all) at the current state: gravity, joint-spring and tendon-spring potential
+        (at each env's own stiffness) and kinetic energy; data.energy is (the sum of the first three, the fourth)"""
+        return self.env.energy(env_ids=env_ids)
+
     def raycast(self, origin, direction, body=None, exclude=None, env_ids=None, cat_mask=native.SG_RAY_ALL, max_dist=0.0, normals=False, skin=False):
         """ray queries on the current state (mj_ray; sg_ray): NativeBatch.raycast's arguments and dict of device tensors (dist [k, R],
         geom [k, R], normal [k, R, 3] with normals=True).  skin=True (SG_RAY_SKIN): the soft object is seen as its skin (the scene's
@@ -459,10 +475,12 @@ class ManEnv(Env):
         return res_
 
     # ---- fused episode: the create_dataset.py schedule without a host round trip per step ----
-    def rollout(self, schedule, out=None, reset=True):
+    def rollout(self, schedule, out=None, reset=True, energy_out=None):
         """Runs ``len(schedule)`` env steps; ``schedule[t]`` is the broadcast ctrl (or None = unchanged) applied
         before step t.  Writes sensordata into ``out[n, T, 12]`` (allocated when None) and returns
-        ``(out, flags_or[n])``.  Envs that fail are NOT reset here (their flags are returned)."""
+        ``(out, flags_or[n])``.  Envs that fail are NOT reset here (their flags are returned).
+        ``energy_out``: a ``[n, T, 4]`` float64 device tensor that receives get_energy() of the state after every env step (one
+        sg_get_energy per step, on the same stream); None: no such call is made."""
         import torch
         T = len(schedule)
         dev = self.env.device
@@ -471,6 +489,9 @@ class ManEnv(Env):
             out = torch.empty(self.n_envs, T, nsd, dtype=torch.float64, device=dev)
         assert out.shape == (self.n_envs, T, nsd) and out.is_contiguous()
         flags_or = torch.zeros(self.n_envs, dtype=torch.int32, device=dev)
+        if energy_out is not None:
+            assert energy_out.shape == (self.n_envs, T, 4) and energy_out.dtype == torch.float64 and energy_out.device == dev
+            e_row = torch.empty(self.n_envs, 4, dtype=torch.float64, device=dev)
         if reset:
             self.env.reset(max(self.sim_start, 0), sens=self._sens, flags=self._flags, touch=self._touch)
             self._ctrl[:] = 0
@@ -481,6 +502,8 @@ class ManEnv(Env):
                 self.env.set_ctrl_broadcast(self._ctrl)
             self.env.step(self.sim_step, sens=out[:, t], sens_stride=T * nsd, flags=self._flags, touch=self._touch)
             flags_or |= self._flags
+            if energy_out is not None:
+                energy_out[:, t] = self.env.energy(out=e_row)
         return out, flags_or
 
     # specs

@@ -24,7 +24,7 @@ SYMBOLS = [
     "sg_get_touch_words", "sg_model_nboxes", "sg_model_nv", "sg_model_njnt", "sg_tree_workgroups_per_cu",
     "sg_get_poses", "sg_model_nbody", "sg_model_ngeom", "sg_model_default_camera", "sg_render",
     "sg_get_contacts", "sg_model_ncollision_pairs", "sg_model_set_skin", "sg_model_skin", "sg_render_ex", "sg_ray",
-    "sg_lstm_forward", "sg_lstm_backward",
+    "sg_lstm_forward", "sg_lstm_backward", "sg_get_velocities", "sg_get_tendons", "sg_get_energy",
 ]
 SG_RENDER_SKIN = 1
 # sg_ray: category bits of cat_mask (ground plane, static, moving finger box, shell element, centre sphere) and flags
@@ -99,6 +99,9 @@ def load_library(path):
     L.sg_model_ncollision_pairs.argtypes = [vp]
     L.sg_ray.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, dp, dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_double, C.c_int,
                          dp, ip, dp, vp]
+    L.sg_get_velocities.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, dp, dp, vp]
+    L.sg_get_tendons.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, dp, vp]
+    L.sg_get_energy.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, vp]
     L.sg_lstm_forward.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int, vp]
     L.sg_lstm_backward.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, vp]
     L.sg_profile_enable.argtypes = [vp, C.c_int]
@@ -280,6 +283,40 @@ class NativeBatch:
                    geom_xmat=t.empty(k, m.ngeom, 9, **kw))
         self._check(self.L.sg_get_poses(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, _ptr(out["xpos"]),
                                         _ptr(out["xquat"]), _ptr(out["geom_xpos"]), _ptr(out["geom_xmat"]), self._stream()))
+        return out
+
+    def velocities(self, env_ids=None):
+        """body velocities of the listed envs (None: all) on the current state (sg_get_velocities), world axes: dict of float64 device
+        tensors [k, nbody, 3]: ang, the angular velocity; lin, the linear velocity of the body frame's origin (the xpos of poses());
+        com_lin, that of the centre of mass.  The time derivative of poses() when qpos moves as qvel says.  A point p fixed on body i
+        moves at ``lin[:, i] + torch.cross(ang[:, i], p - xpos[:, i], dim=-1)``."""
+        t, m = self.torch, self.nmodel
+        ids, k = self._ids(env_ids)
+        out = {name: t.empty(k, m.nbody, 3, dtype=t.float64, device=self.device) for name in ("ang", "lin", "com_lin")}
+        self._check(self.L.sg_get_velocities(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, _ptr(out["ang"]),
+                                             _ptr(out["lin"]), _ptr(out["com_lin"]), self._stream()))
+        return out
+
+    def tendons(self, env_ids=None):
+        """tendon lengths and their rates of the listed envs (None: all) on the current state (sg_get_tendons; data.ten_length,
+        data.ten_velocity): dict of float64 device tensors length, velocity [k, ntendon]"""
+        t, m = self.torch, self.nmodel
+        ids, k = self._ids(env_ids)
+        out = {name: t.empty(k, m.ntendon, dtype=t.float64, device=self.device) for name in ("length", "velocity")}
+        self._check(self.L.sg_get_tendons(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, _ptr(out["length"]),
+                                          _ptr(out["velocity"]), self._stream()))
+        return out
+
+    def energy(self, env_ids=None, out=None):
+        """the energy of the listed envs (None: all) on the current state (sg_get_energy): float64 device tensor [k, 4] = gravity, joint
+        springs, tendon springs (each env at the stiffness its next step uses), kinetic; data.energy is (the sum of the first three,
+        the fourth).  out: a contiguous [k, 4] tensor to fill."""
+        t = self.torch
+        ids, k = self._ids(env_ids)
+        if out is None:
+            out = t.empty(k, 4, dtype=t.float64, device=self.device)
+        assert out.is_cuda and out.dtype == t.float64 and out.is_contiguous() and out.shape == (k, 4)
+        self._check(self.L.sg_get_energy(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, _ptr(out), self._stream()))
         return out
 
     def contacts(self, env_ids=None, max_contacts=256):

@@ -1,0 +1,352 @@
+"""Helpers of the velocity / tendon / energy read-out tests (sg_get_velocities, sg_get_tendons, sg_get_energy; csrc/sg_dyn.h):
+
+  * reference(): a NumPy (fp64) restatement written from the definitions, NOT from the header: Model.kinematics() for the poses, one
+    Jacobian column per dof (axis, anchor, the bodies it moves), velocities as column sums, energies from the bodies' masses and inertias;
+  * build_host() / host(): the g++ build of csrc/sg_dyn.h run serially, body by body and wrap by wrap, as the kernel's lanes run it;
+  * the scenes and states every test uses: a few oracle steps into a squeeze, a seeded perturbation of qvel, a stiffness per env.
+"""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+import softgrip_amd as sg
+from helpers import ROOT, model_path
+from softgrip_amd.mjcf import JNT_FREE, JNT_SLIDE, WRAP_JOINT
+
+# scene -> (tendon damper, joints / tendons that take the per-env stiffness, actuators)
+SCENES = {
+    "mini_gripper": (None, list(range(8, 42)), [0], 2),
+    "softbox_fix": (None, list(range(11, 64)), [0], 2),
+    "softbox": (None, list(range(11, 64)), [0], 2),
+    "fourfinger_softball_fix": ("implicit", list(range(65, 283)), [0], 4),
+    "freeball_fix": ("implicit", list(range(9, 227)), [0], 2),
+}
+KS = [640.0, 300.0, 1400.0]      # a stiffness per env
+REL = 1e-11                       # sums of <= ~300 like-sized terms: n eps ~ 7e-14, two orders of margin
+ARR = 1e-12                       # per array, times max(1, max |value|): ~100 fp64 operations per body at O(1 - 10)
+
+
+def load(scene):
+    damper = SCENES[scene][0]
+    if scene == "mini_gripper":
+        m = sg.compile_mjcf(os.path.join(ROOT, "tests", "data", "mini_gripper.xml"), composite_neighbors=False)
+        m.opt_implicit_tendon_damping = 0
+        return m
+    return sg.load_model(model_path(scene), damper)
+
+
+_STATES = {}
+
+
+def states(scene, nsteps=60):
+    """(model, [dict(qpos, qvel, k)] per env of KS): the oracle's reset; forward; step, ctrl = -0.2, nsteps steps; then qvel gains a
+    seeded perturbation of a tenth of its own scale (never changed afterwards: computed once per scene and shared)"""
+    if scene not in _STATES:
+        from oracle import oracle as O
+        m = load(scene)
+        _, jids, tids, nu = SCENES[scene]
+        om = O.OracleModel(m.to_blob())
+        rs = np.random.RandomState(1234)
+        out = []
+        for k in KS:
+            s = O.OracleSim(om)
+            s.jnt_stiffness[jids] = k
+            s.tendon_stiffness[tids] = k
+            s.reset(); s.forward(); s.step()
+            s.ctrl[:] = -0.2
+            for _ in range(nsteps):
+                assert s.step() == 0, scene
+            scale = max(np.abs(s.qvel).max(), 1e-3)
+            out.append(dict(qpos=s.qpos.copy(), qvel=s.qvel + 0.1 * scale * rs.standard_normal(m.nv), k=k))
+        _STATES[scene] = (m, om, out)
+    return _STATES[scene]
+
+
+def stiffness(m, scene, k):
+    """the stiffness vectors env k's next step uses: (jnt_stiffness [njnt], tendon_stiffness [ntendon])"""
+    _, jids, tids, _ = SCENES[scene]
+    kj, kt = np.array(m.jnt_stiffness, dtype=np.float64), np.array(m.tendon_stiffness, dtype=np.float64)
+    if k is not None:
+        kj[jids] = k
+        kt[tids] = k
+    return kj, kt
+
+
+# ---- the NumPy reference ----
+def dof_columns(m, kin):
+    """per dof: is it a rotation, its world axis, its anchor, the body it belongs to"""
+    nv = m.nv
+    rot, axis, anchor, body = np.zeros(nv, bool), np.zeros((nv, 3)), np.zeros((nv, 3)), np.zeros(nv, int)
+    for b in range(1, m.nbody):
+        for j in range(m.body_jntadr[b], m.body_jntadr[b] + m.body_jntnum[b]):
+            d = m.jnt_dofadr[j]
+            if m.jnt_type[j] == JNT_FREE:
+                R = kin["xmat"][b]
+                for c in range(3):
+                    axis[d + c, c] = 1.0
+                    rot[d + 3 + c], axis[d + 3 + c], anchor[d + 3 + c] = True, R[:, c], kin["xpos"][b]
+                body[d:d + 6] = b
+            else:
+                rot[d], axis[d], anchor[d], body[d] = m.jnt_type[j] != JNT_SLIDE, kin["xaxis"][j], kin["xanchor"][j], b
+    return rot, axis, anchor, body
+
+
+def moved_by(m, body):
+    """[nbody, nv] bool: dof d moves body b (the dof's body is b or one of its ancestors)"""
+    nb = m.nbody
+    anc = np.zeros((nb, nb), bool)      # anc[b, a]: a is b or an ancestor of b
+    for b in range(1, nb):
+        anc[b] = anc[m.body_parentid[b]]
+        anc[b, b] = True
+    return anc[:, body]
+
+
+def point_jac(cols, moved_row, p):
+    """3 x nv translational Jacobian of the world point p on a body whose dofs are moved_row"""
+    rot, axis, anchor, _ = cols
+    jp = np.where(rot[:, None], np.cross(axis, p[None] - anchor), axis)
+    return (jp * moved_row[:, None]).T
+
+
+def reference(m, qpos, qvel, kj=None, kt=None):
+    """dict: ang, lin, com_lin [nbody, 3]; length, velocity [ntendon]; energy [4] (gravity, joint springs, tendon springs, kinetic);
+    and the pieces the oracle pins: xipos, site positions.  kj / kt: the stiffness vectors in force (None: the model's own)"""
+    qpos, qvel = np.asarray(qpos, np.float64), np.asarray(qvel, np.float64)
+    kin = m.kinematics(qpos)
+    cols = dof_columns(m, kin)
+    rot, axis, anchor, body = cols
+    mv = moved_by(m, body)
+    nb = m.nbody
+    ang, lin, com_lin, xipos = np.zeros((nb, 3)), np.zeros((nb, 3)), np.zeros((nb, 3)), np.zeros((nb, 3))
+    for b in range(1, nb):
+        ang[b] = ((axis * rot[:, None] * mv[b][:, None]).T) @ qvel
+        lin[b] = point_jac(cols, mv[b], kin["xpos"][b]) @ qvel
+        xipos[b] = kin["xpos"][b] + kin["xmat"][b] @ m.body_ipos[b]
+        com_lin[b] = point_jac(cols, mv[b], xipos[b]) @ qvel
+    sx = m.site_xpos(kin) if m.nsite else np.zeros((0, 3))
+    sv = np.array([point_jac(cols, mv[m.site_bodyid[s]], sx[s]) @ qvel for s in range(m.nsite)]).reshape(-1, 3)
+    nt = m.ntendon
+    length, velocity = np.zeros(nt), np.zeros(nt)
+    for t in range(nt):
+        a, n = m.tendon_adr[t], m.tendon_num[t]
+        if m.wrap_type[a] == WRAP_JOINT:
+            js = m.wrap_objid[a:a + n]
+            length[t] = np.dot(m.wrap_prm[a:a + n], qpos[m.jnt_qposadr[js]])
+            velocity[t] = np.dot(m.wrap_prm[a:a + n], qvel[m.jnt_dofadr[js]])
+        else:
+            for w in range(a, a + n - 1):
+                s0, s1 = m.wrap_objid[w], m.wrap_objid[w + 1]
+                d = sx[s1] - sx[s0]
+                ln = np.linalg.norm(d)
+                length[t] += ln
+                if ln >= 1e-15:
+                    velocity[t] += np.dot(d / ln, sv[s1] - sv[s0])
+    kj = np.asarray(m.jnt_stiffness, np.float64) if kj is None else kj
+    kt = np.asarray(m.tendon_stiffness, np.float64) if kt is None else kt
+    g = np.asarray(m.opt_gravity, np.float64)
+    e_grav = -float(np.sum(m.body_mass[1:] * (xipos[1:] @ g)))
+    scalar = np.asarray(m.jnt_type) != JNT_FREE
+    qa = np.asarray(m.jnt_qposadr)[scalar]
+    e_jnt = float(np.sum(0.5 * kj[scalar] * (qpos[qa] - m.qpos_spring[qa]) ** 2))
+    e_ten = float(np.sum(0.5 * kt * (length - m.tendon_lengthspring) ** 2))
+    e_kin = 0.5 * float(np.sum(m.dof_armature * qvel ** 2))
+    for b in range(1, nb):
+        R = kin["xmat"][b]
+        Iw = R @ np.reshape(m.body_imat[b], (3, 3)) @ R.T
+        e_kin += 0.5 * (m.body_mass[b] * com_lin[b] @ com_lin[b] + ang[b] @ Iw @ ang[b])
+    return dict(ang=ang, lin=lin, com_lin=com_lin, length=length, velocity=velocity, energy=np.array([e_grav, e_jnt, e_ten, e_kin]),
+                xipos=xipos, site_xpos=sx, kin=kin)
+
+
+def close(got, ref, tol=ARR):
+    """|got - ref| <= tol * max(1, max |ref|) over the array; returns the largest deviation in units of that bound"""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    if ref.size == 0:
+        return 0.0
+    return float(np.abs(got - ref).max() / (tol * max(1.0, np.abs(ref).max())))
+
+
+ALLOW_FIXED_TENDON = ("fourfinger_softball_fix",)      # scenes whose tendon-spring term needs energy_scale's allowance (see there)
+
+
+def energy_scale(m, ref, kj, kt, qpos, qvel, allowance=False):
+    """per energy term what REL is relative to: the sum of the absolute values of its summands (for the tendon springs sum 1/2 |k| x^2,
+    x = L - tendon_lengthspring).
+    allowance=True (the scenes of ALLOW_FIXED_TENDON only) adds, for FIXED tendons, |k| |x| sum |coef q|: what the length's own bound
+    REL sum |coef q| does to 1/2 k x^2.  The four-finger scene needs it: its volume tendon is the only tendon with a stiffness, its
+    length a sum of 218 cancelling coef q terms (sum |coef q| = 3e-3 .. 5e-3 m) that comes to 7e-21 .. 9e-20 m in these states, so the
+    term is 1e-38 .. 6e-36 J and two correct summation orders differ by most of it (measured, g++ build against NumPy: 0.75 and 0.94
+    of the term in two of three states; with the allowance at most 1.2e-17 of the scale)"""
+    g = np.asarray(m.opt_gravity, np.float64)
+    scalar = np.asarray(m.jnt_type) != JNT_FREE
+    qa = np.asarray(m.jnt_qposadr)[scalar]
+    x = ref["length"] - m.tendon_lengthspring
+    e_ten = np.sum(0.5 * np.abs(kt) * x ** 2)
+    if allowance:
+        for t in range(m.ntendon):
+            if m.wrap_type[m.tendon_adr[t]] == WRAP_JOINT:
+                e_ten += abs(kt[t]) * abs(x[t]) * length_scale(m, t, qpos, ref["length"])
+    return np.array([np.sum(np.abs(m.body_mass[1:] * (ref["xipos"][1:] @ g))), np.sum(0.5 * np.abs(kj[scalar]) * (qpos[qa] - m.qpos_spring[qa]) ** 2),
+                     e_ten, max(ref["energy"][3], 0.0)])
+
+
+def length_scale(m, t, qpos, length):
+    """the sum of the absolute values of the terms of tendon t's length: |coef q| over a fixed tendon's wraps, the length itself for a
+    spatial one (its segments are all positive)"""
+    a, n = m.tendon_adr[t], m.tendon_num[t]
+    if m.wrap_type[a] == WRAP_JOINT:
+        return float(np.sum(np.abs(m.wrap_prm[a:a + n] * np.asarray(qpos)[m.jnt_qposadr[m.wrap_objid[a:a + n]]])))
+    return float(length[t])
+
+
+# ---- the g++ build of csrc/sg_dyn.h ----
+HOST_DRIVER = r"""
+#include <cstring>
+#include <vector>
+#include "sg_dyn.h"
+// one env, serially, in the kernel's order: bodies by index (parents precede children), then per tendon its shares, then the energy terms
+extern "C" void dyn_host(const int* ko, const double* D, const int* I, const int* dof, const double* DD, const int* DI, const double* qpos,
+                         const double* qvel, double kenv, const int* kmask_jnt, const int* kmask_ten, double* ang, double* lin, double* com_lin,
+                         double* ten_len, double* ten_vel, double* energy, double* poses) {
+  SgKinOff o;
+  SgDynOff d;
+  static_assert(sizeof(SgKinOff) == 22 * sizeof(int) && sizeof(SgDynOff) == 21 * sizeof(int), "offset blocks are plain ints");
+  memcpy(&o, ko, sizeof o);
+  memcpy(&d, dof, sizeof d);
+  std::vector<double> rec((size_t)SGD_REC * o.nbody, 0.0);
+  rec[3] = 1.0;
+  for (int i = 1; i < o.nbody; i++) sgd_body(D, I, o, DI + d.jdof, qpos, qvel, i, &rec[SGD_REC * I[o.bpar + i]], &rec[SGD_REC * i]);
+  double e[4] = {0, 0, 0, 0};
+  for (int i = 0; i < o.nbody; i++) {
+    double xi[3], vc[3];
+    sgd_com(DD, d, &rec[SGD_REC * i], i, xi, vc);
+    for (int c = 0; c < 3; c++) { ang[3 * i + c] = rec[SGD_REC * i + 7 + c]; lin[3 * i + c] = rec[SGD_REC * i + 10 + c]; com_lin[3 * i + c] = vc[c]; }
+    for (int c = 0; c < 7; c++) poses[7 * i + c] = rec[SGD_REC * i + c];
+    if (i > 0) {
+      double g1, k1;
+      sgd_body_energy(DD, d, &rec[SGD_REC * i], i, &g1, &k1);
+      e[0] += g1; e[3] += k1;
+    }
+  }
+  for (int t = 0; t < d.ntendon; t++) {
+    double L = 0, V = 0;
+    const int w0 = DI[d.tadr + t], n = sgd_nshare(DI, d, t);
+    for (int s = 0; s < n; s++) {
+      double l1, v1;
+      sgd_wrap(D, I, o, DD, DI, d, qpos, qvel, rec.data(), w0 + s, &l1, &v1);
+      L += l1; V += v1;
+    }
+    ten_len[t] = L; ten_vel[t] = V;
+    e[2] += sgd_tendon_spring(DD, d, t, L, kmask_ten[t], kenv);
+  }
+  for (int j = 0; j < o.njnt; j++) e[1] += sgd_joint_spring(I, o, DD, d, qpos, j, kmask_jnt[j], kenv);
+  for (int i = 0; i < d.nv; i++) e[3] += 0.5 * DD[d.arm + i] * qvel[i] * qvel[i];
+  memcpy(energy, e, sizeof e);
+}
+"""
+
+
+def build_host(tmpdir):
+    """compiles sg_dyn.h with g++ into tmpdir -> the ctypes library with dyn_host"""
+    src = os.path.join(str(tmpdir), "dyn_host.cpp")
+    so = os.path.join(str(tmpdir), "libdyn_host.so")
+    with open(src, "w") as f:
+        f.write(HOST_DRIVER)
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(ROOT, "soft-grip_amd", "csrc"), "-o", so, src])
+    return C.CDLL(so)
+
+
+def _tables(m):
+    """the kinematics and dynamics tables as the library lays them out (the sections the header's routines read)"""
+    dbl, ints = [], []
+
+    def put(store, arr, dt):
+        at = sum(len(x) for x in store)
+        store.append(np.ascontiguousarray(arr, dtype=dt).reshape(-1))
+        return at
+
+    f, i = np.float64, np.int32
+    qa = np.asarray(m.jnt_qposadr)
+    ko = dict(nbody=m.nbody, ngeom=0, njnt=m.njnt, nq=m.nq, nlevel=0)
+    for name, arr in (("bpos", m.body_pos), ("bquat", m.body_quat), ("jpos", m.jnt_pos), ("jaxis", m.jnt_axis), ("jq0", np.asarray(m.qpos0)[qa])):
+        ko[name] = put(dbl, arr, f)
+    ko["gpos"] = ko["gmat"] = ko["gsize"] = 0
+    for name, arr in (("bpar", m.body_parentid), ("bjadr", m.body_jntadr), ("bjnum", m.body_jntnum), ("jtype", m.jnt_type), ("jqadr", qa)):
+        ko[name] = put(ints, arr, i)
+    ko["gbody"] = ko["gmeta"] = ko["lstart"] = ko["lbody"] = 0
+    order = ["nbody", "ngeom", "njnt", "nq", "nlevel", "bpos", "bquat", "jpos", "jaxis", "jq0", "gpos", "gmat", "gsize", "bpar", "bjadr", "bjnum", "jtype",
+             "jqadr", "gbody", "gmeta", "lstart", "lbody"]
+    K = (np.array([ko[k] for k in order], i), np.concatenate(dbl), np.concatenate(ints))
+    dbl, ints = [], []
+    do = dict(nv=m.nv, nsite=m.nsite, ntendon=m.ntendon, nwrap=len(m.wrap_type))
+    for name, arr in (("bmass", m.body_mass), ("bipos", m.body_ipos), ("bimat", m.body_imat), ("jspring", np.asarray(m.qpos_spring)[qa]),
+                      ("jstiff", m.jnt_stiffness), ("arm", m.dof_armature), ("spos", m.site_pos), ("wprm", m.wrap_prm), ("tstiff", m.tendon_stiffness),
+                      ("tspring", m.tendon_lengthspring), ("grav", m.opt_gravity)):
+        do[name] = put(dbl, arr, f)
+    for name, arr in (("jdof", m.jnt_dofadr), ("sbody", m.site_bodyid), ("tadr", m.tendon_adr), ("tnum", m.tendon_num), ("wtype", m.wrap_type),
+                      ("wobj", m.wrap_objid)):
+        do[name] = put(ints, arr, i)
+    order = ["nv", "nsite", "ntendon", "nwrap", "bmass", "bipos", "bimat", "jspring", "jstiff", "arm", "spos", "wprm", "tstiff", "tspring", "grav", "jdof",
+             "sbody", "tadr", "tnum", "wtype", "wobj"]
+    Dn = (np.array([do[k] for k in order], i), np.concatenate(dbl), np.concatenate(ints + [np.zeros(1, i)]))
+    return K, Dn
+
+
+def host(L, m, scene, qpos, qvel, k):
+    """the host build's outputs for one env at stiffness k (None: no joint or tendon is listed): reference()'s dict, plus poses [nbody, 7]"""
+    K, Dn = _tables(m)
+    _, jids, tids, _ = SCENES[scene]
+    kmj, kmt = np.zeros(m.njnt, np.int32), np.zeros(max(m.ntendon, 1), np.int32)
+    if k is not None:
+        kmj[jids] = 1
+        kmt[tids] = 1
+    nb, nt = m.nbody, m.ntendon
+    out = dict(ang=np.zeros((nb, 3)), lin=np.zeros((nb, 3)), com_lin=np.zeros((nb, 3)), length=np.zeros(nt), velocity=np.zeros(nt), energy=np.zeros(4),
+               poses=np.zeros((nb, 7)))
+    p = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
+    q, v = np.ascontiguousarray(qpos, np.float64), np.ascontiguousarray(qvel, np.float64)
+    L.dyn_host(p(K[0]), p(K[1]), p(K[2]), p(Dn[0]), p(Dn[1]), p(Dn[2]), p(q), p(v), C.c_double(0.0 if k is None else k), p(kmj), p(kmt), p(out["ang"]),
+               p(out["lin"]), p(out["com_lin"]), p(out["length"]), p(out["velocity"]), p(out["energy"]), p(out["poses"]))
+    return out
+
+
+def oracle_forward(sim, qpos, qvel, kj=None, kt=None):
+    """the oracle's forward pass at (qpos, qvel) with the stiffness vectors in force; its views then hold qM, ten_length, sensordata"""
+    sim.qpos[:], sim.qvel[:] = qpos, qvel
+    if kj is not None:
+        sim.jnt_stiffness[:], sim.tendon_stiffness[:] = kj, kt
+    sim.forward()
+    return sim
+
+
+def gyro_channels(m):
+    """[(sensordata address, site)] of the model's gyros (the velocity-stage sensor)"""
+    from softgrip_amd.mjcf import SENS_GYRO
+    return [(int(m.sensor_adr[s]), int(m.sensor_objid[s])) for s in range(len(m.sensor_type)) if m.sensor_type[s] == SENS_GYRO]
+
+
+def site_xmat(m, kin, site):
+    from softgrip_amd.mjcf import quat_to_mat
+    return kin["xmat"][m.site_bodyid[site]] @ quat_to_mat(m.site_quat[site])
+
+
+def integrate(m, qpos, qvel, h):
+    """qpos moved by h qvel as mj_integratePos does: scalar joints q + h qvel; a free joint's position + h v (world), its quaternion
+    q (x) exp(h w / 2), w the angular components in the body frame"""
+    from softgrip_amd.mjcf import quat_mul
+    q = np.array(qpos, dtype=np.float64)
+    for j in range(m.njnt):
+        qa, da = m.jnt_qposadr[j], m.jnt_dofadr[j]
+        if m.jnt_type[j] == JNT_FREE:
+            q[qa:qa + 3] += h * qvel[da:da + 3]
+            w = h * np.asarray(qvel[da + 3:da + 6])
+            a = np.linalg.norm(w)
+            dq = np.concatenate([[np.cos(a / 2)], (np.sin(a / 2) / a) * w]) if a > 0 else np.array([1.0, 0, 0, 0])
+            quat = quat_mul(q[qa + 3:qa + 7], dq)
+            q[qa + 3:qa + 7] = quat / np.linalg.norm(quat)
+        else:
+            q[qa] += h * qvel[da]
+    return q
