@@ -117,6 +117,66 @@ def test_host_build_matches_oracle_on_random_grippers(host, tmp_path):
     assert (0, 6) in kinds and (6, 6) in kinds and (3, 6) in kinds, kinds     # plane - box, box - box, capsule - box all occurred
 
 
+def test_pose_sweep_of_random_grippers_matches_oracle(host, tmp_path):
+    """the pose sweep of contacts_ref (six random grippers, 64 poses each, turned far out of their joint ranges) on the host build against
+    the oracle, and the conditions the device test of the same sweep (tests/test_gpu_contacts.py) relies on, all from the oracle and
+    the host build alone: every pair type and every box - box class occurs, the queue carries over rounds, more than two passes of the
+    eight-at-a-time box - box loop occur, the model's cap is reached, and knife edges are rare"""
+    rs = np.random.RandomState(3)
+    table, records = {}, {k: set() for k in CR.PAIR_NAMES.values()}
+    edges = []
+    poses = most_surv = most_bb = capped = ties = parallel = 0
+    worst = 0.0
+    for i, xml in enumerate(CR.sweep_gripper_xmls()):
+        path = tmp_path / ("g%d.xml" % i)
+        path.write_text(xml)
+        m = sg.compile_mjcf(str(path), composite_neighbors=False)
+        sim = oracle_sim(m)
+        cap = min(int(m.nconmax), 512)
+        surv_range, most = [10 ** 9, 0], 0
+        for p, q in enumerate(CR.pose_sweep(m, CR.SWEEP_POSES, CR.SWEEP_POSE_SEED + i)):
+            ref = CR.oracle_contacts(sim, q)
+            worst = max(worst, CR.compare(CR.host_contacts(host, m, q), ref, "gripper %d pose %d" % (i, p)))
+            for kind, n, cls in CR.classify(m, q, ref):
+                records[kind].add(n)
+                if cls:
+                    table[cls, n] = table.get((cls, n), 0) + 1
+            par, tie = CR.box_pair_flags(m, q, ref)
+            parallel += par
+            ties += tie
+            nsurv, nbb = CR.host_stats(host, m, q)
+            surv_range = [min(surv_range[0], nsurv), max(surv_range[1], nsurv)]
+            most_bb = max(most_bb, nbb)
+            most = max(most, ref["ncon"])
+            capped += ref["ncon"] == cap
+            if CR.knife_edge(sim, q, ref, rs):
+                edges.append((i, p))
+            poses += 1
+        most_surv = max(most_surv, surv_range[1])
+        print("gripper %d: %d candidate pairs, %d to %d survivors, up to %d contacts (cap %d)" % (i, CR.host_npairs(host, m), surv_range[0], surv_range[1], most, cap))
+    print("box - box contact pairs by class and record count")
+    print("%-8s" % "class" + "".join("%5d" % n for n in range(1, 9)))
+    for cls in ("edge", "face1", "face2"):
+        print("%-8s" % cls + "".join("%5d" % table.get((cls, n), 0) for n in range(1, 9)))
+    faces = {n: table.get(("face1", n), 0) + table.get(("face2", n), 0) for n in range(1, 9)}
+    print("face contacts with 7 records: %d, with 8: %d" % (faces[7], faces[8]))
+    print("%d poses with boxes of parallel axes in contact, %d with a normal that is an axis of both boxes" % (parallel, ties))
+    print("%d poses, knife edges (gripper, pose) %s, most survivors %d, most box - box pairs in a round %d, %d poses at the cap, max deviation %.2e"
+          % (poses, edges, most_surv, most_bb, capped, worst))
+    assert poses == CR.SWEEP_GRIPPERS * CR.SWEEP_POSES
+    assert all(records.values()), records
+    assert records["plane-capsule"] == {1, 2} and records["capsule-box"] == {1, 2}, records
+    for cls in ("edge", "face1", "face2"):
+        assert sum(v for (c, n), v in table.items() if c == cls) >= 20, (cls, table)
+    assert all(faces[n] > 0 for n in range(1, 7)), faces
+    assert records["plane-box"] == {1, 2, 3, 4}, records
+    assert most_surv > 128, most_surv          # the queue's carry runs over more than two rounds
+    assert most_bb > 16, most_bb               # more than two passes of the eight-at-a-time loop
+    assert parallel >= CR.SWEEP_GRIPPERS * CR.SWEEP_ALIGNED, parallel
+    assert capped >= 1                         # the model's own nconmax cuts a list
+    assert len(edges) <= 0.02 * poses, (edges, poses)
+
+
 def test_pair_table_counts(host):
     """candidate pairs after the static filters, by pair_allowed's rule: the host build's table and the library's"""
     from softgrip_amd import native

@@ -1,6 +1,7 @@
 """sg_get_contacts on the GPU: the contact list of the current state against the oracle's forward(); contacts() along whole squeeze
-episodes, the call's interface (env subsets, truncation, NaN envs, NULL outputs, no side effect on a following step), agreement with
-the touch bits where nothing lies between the two, and ManEnv.get_contacts."""
+episodes and over a pose sweep of random grippers (every pair type, every box - box branch, the queue's carry, the model's cap, the
+kernel that keeps its poses in global memory), the call's interface (env subsets, truncation, NaN envs, NULL outputs, no side effect on
+a following step), agreement with the touch bits where nothing lies between the two, and ManEnv.get_contacts."""
 import ctypes as C
 
 import numpy as np
@@ -49,12 +50,9 @@ def _rows(out):
     return res
 
 
-def _oracle_is_on_a_knife_edge(sim, q, ref, rs):
-    """does the oracle's OWN list (count, geom pairs) change under a +-1e-12 perturbation of this qpos?"""
-    for _ in range(4):
-        if not CR.same_list(CR.oracle_contacts(sim, q + rs.choice([-1e-12, 1e-12], size=q.shape)), ref):
-            return True
-    return False
+def _kinds(m, ref):
+    """the pair types of a list, by name"""
+    return {CR.PAIR_NAMES[int(m.geom_type[a]), int(m.geom_type[b])] for a, b in ref["geom"]}
 
 
 @pytest.mark.parametrize("scene", sorted(SCENES))
@@ -72,6 +70,7 @@ def test_episode_lists_match_oracle(scene):
     b.reset(1, sens=sens, flags=flags)
     samples = left_out = most = 0
     worst = 0.0
+    kinds = set()
 
     def sample(t):
         nonlocal samples, left_out, most, worst
@@ -84,11 +83,12 @@ def test_episode_lists_match_oracle(scene):
             samples += 1
             ref = CR.oracle_contacts(sim, qpos[e])
             most = max(most, ref["ncon"])
+            kinds.update(_kinds(m, ref))
             assert ref["ncon"] <= MAXC, (t, e, ref["ncon"])
             try:
                 worst = max(worst, CR.compare(got[e], ref, "%s step %d env %d" % (scene, t, e)))
             except AssertionError:
-                if not _oracle_is_on_a_knife_edge(sim, qpos[e], ref, rs):
+                if not CR.knife_edge(sim, qpos[e], ref, rs):
                     raise
                 left_out += 1
 
@@ -100,6 +100,7 @@ def test_episode_lists_match_oracle(scene):
         if (t + 1) % 10 == 0:
             sample(t + 1)
     print("%s: %d samples, %d left out (knife edges), up to %d contacts, max deviation %.2e" % (scene, samples, left_out, most, worst))
+    print("%s: pair types that produced contacts: %s" % (scene, ", ".join(sorted(kinds))))
     assert samples >= 9 * 21 * 0.9, samples
     assert most >= 10, most
     assert left_out <= 0.02 * samples, (left_out, samples)
@@ -186,6 +187,149 @@ def test_interface_behaviour():
         assert b"sg_get_contacts" in b.L.sg_last_error()
     assert _call(b, None, 0, 0, {}) == native.SG_ERR_INVALID
     assert _call(b, None, len(ks), 0, {"dist": torch.zeros(len(ks), 1, dtype=torch.float64, device=b.device)}) == native.SG_ERR_INVALID
+
+
+# ---- the pose sweep of contacts_ref: random grippers turned far out of their joint ranges, one env per pose, nothing stepped ----
+_SWEEP = {}      # gripper -> (model, poses [n, nq], the oracle's list per pose): computed once, shared, left unchanged
+CAP_GRIPPER = 0          # (its longest list stays below the model's nconmax = 300: the sweep's lists of it are uncapped)
+MANY_GEOMS_GRIPPER = 3   # (the gripper with the most broadphase survivors)
+POSE_LDS_LIMIT = 159 * 1024    # sg_get_contacts keeps an env's poses in LDS up to here (35 328 B of staging + 8 (7 nbody + 12 ngeom))
+
+
+def _compile(tmp_path, name, xml):
+    path = tmp_path / name
+    path.write_text(xml)
+    return sg.compile_mjcf(str(path), composite_neighbors=False)
+
+
+def _sweep(gripper, tmp_path):
+    if gripper not in _SWEEP:
+        m = _compile(tmp_path, "g%d.xml" % gripper, CR.sweep_gripper_xmls()[gripper])
+        qs = CR.pose_sweep(m, CR.SWEEP_POSES, CR.SWEEP_POSE_SEED + gripper)
+        sim = oracle_sim(m)
+        _SWEEP[gripper] = (m, qs, [CR.oracle_contacts(sim, q) for q in qs])
+    return _SWEEP[gripper]
+
+
+def _pose_batch(m, qs):
+    """a batch of the model's default pipeline with one env per pose: one sg_set_state, nothing stepped"""
+    from softgrip_amd import native
+    torch = _torch()
+    b = native.NativeBatch(native.NativeModel(m), len(qs), 0)
+    b.set_state(qpos=torch.tensor(np.ascontiguousarray(qs), dtype=torch.float64, device=b.device))
+    return b
+
+
+def _same_bits(a, b):
+    for key in ("ncon", "geom", "dist", "pos", "frame"):
+        assert a[key].cpu().numpy().tobytes() == b[key].cpu().numpy().tobytes(), key
+
+
+@pytest.mark.parametrize("gripper", range(CR.SWEEP_GRIPPERS))
+def test_pose_sweep_matches_oracle(gripper, tmp_path):
+    """64 poses of a random gripper as 64 envs of one batch, one sg_set_state and one read-out: every env's list against the oracle's
+    forward(); contacts() at that qpos, counts and geom pairs exact, dist / pos / frame within 1e-9.  What the poses reach -- every pair
+    type, box - box contacts off a face of either box and off two edges with 1 to 7 records, more than 128 survivors in an env, up to
+    47 box - box pairs among 64 survivors, a list cut by the model's nconmax -- is asserted on the CPU by
+    tests/test_contacts_host.py::test_pose_sweep_of_random_grippers_matches_oracle.  A pose may be left out only where the device's
+    list differs AND the oracle's own list changes under a +-1e-12 perturbation of that qpos, and at most one per gripper (2 % of 64)."""
+    m, qs, refs = _sweep(gripper, tmp_path)
+    b = _pose_batch(m, qs)
+    out = b.contacts(max_contacts=512)
+    _same_bits(out, b.contacts(max_contacts=512))
+    got = _rows(out)
+    sim, rs = oracle_sim(m), np.random.RandomState(13)
+    left_out, worst, kinds = [], 0.0, set()
+    for e, (q, ref) in enumerate(zip(qs, refs)):
+        kinds |= _kinds(m, ref)
+        try:
+            worst = max(worst, CR.compare(got[e], ref, "gripper %d pose %d" % (gripper, e)))
+        except AssertionError:
+            if not CR.knife_edge(sim, q, ref, rs):
+                raise
+            left_out.append(e)
+    print("gripper %d: %d poses, left out %s (knife edges), up to %d contacts, max deviation %.2e, pair types %s"
+          % (gripper, len(qs), left_out, max(r["ncon"] for r in refs), worst, ", ".join(sorted(kinds))))
+    assert len(qs) == CR.SWEEP_POSES
+    assert len(left_out) <= 1, left_out
+
+
+def _choose_cap(m, refs):
+    """a cap C from the uncapped lists: the C for which the most poses have record C and record C + 1 in one box - box pair, among those
+    that leave at least one pose below C records and one above (the smallest such C on a tie).  C >= 32: a smaller cap would cut every
+    list within the first pairs of the table"""
+    best, where = (0, 0), None
+    counts = [r["ncon"] for r in refs]
+    for c in range(32, max(counts)):
+        if not (min(counts) < c and max(counts) > c):
+            continue
+        cut = [e for e, r in enumerate(refs) if r["ncon"] > c and (r["geom"][c - 1] == r["geom"][c]).all() and m.geom_type[r["geom"][c, 0]] == 6]
+        if len(cut) > best[0]:
+            best, where = (len(cut), c), cut
+    assert best[0] >= 1, "no cap cuts a box - box pair's records"
+    return best[1], where
+
+
+def test_model_cap_cuts_the_list_where_the_oracle_cuts_it(tmp_path):
+    """the model's own nconmax as the cap, chosen from the oracle's uncapped lists so that it falls between two records of one box - box
+    pair in some poses, above the whole list in others and below it in others: ncon = min(records, C), the first ncon slots are the
+    oracle's (built from the capped model), every slot from ncon on and the memory behind the tensors keep their canary.  Then again
+    with max_contacts = C - 3, which cuts first: ncon stays the capped count."""
+    torch = _torch()
+    m, qs, refs = _sweep(CAP_GRIPPER, tmp_path)
+    assert max(r["ncon"] for r in refs) < min(int(m.nconmax), 512)      # (the lists of the sweep's model are uncapped)
+    cap, cut = _choose_cap(m, refs)
+    xml = CR.sweep_gripper_xmls()[CAP_GRIPPER]
+    assert xml.count('nconmax="300"') == 1
+    mc = _compile(tmp_path, "capped.xml", xml.replace('nconmax="300"', 'nconmax="%d"' % cap))
+    assert int(mc.nconmax) == cap
+    sim = oracle_sim(mc)
+    capped = [CR.oracle_contacts(sim, q) for q in qs]
+    below = sum(r["ncon"] < cap for r in refs)
+    print("cap %d: %d poses cut inside a box - box pair, %d poses below the cap, %d above" % (cap, len(cut), below, sum(r["ncon"] > cap for r in refs)))
+    b = _pose_batch(mc, qs)
+    worst = 0.0
+    for mcs in (cap + 5, cap - 3):
+        out, whole = _canary(torch, b, len(qs), mcs)
+        b.contacts_into(out)
+        h = {k: v.cpu().numpy() for k, v in out.items()}
+        for e, (ref, cref) in enumerate(zip(refs, capped)):
+            n = min(ref["ncon"], cap)
+            assert cref["ncon"] == n and h["ncon"][e] == n, (e, mcs, h["ncon"][e], cref["ncon"], ref["ncon"])
+            k = min(n, mcs)
+            row = dict(ncon=n, geom=h["geom"][e, :k], dist=h["dist"][e, :k], pos=h["pos"][e, :k], frame=h["frame"][e, :k])
+            worst = max(worst, CR.compare(row, cref, "cap %d max_contacts %d pose %d" % (cap, mcs, e)))
+            for key, val in (("geom", -77), ("dist", -7.5), ("pos", -7.5), ("frame", -7.5)):
+                assert (h[key][e, k:] == val).all(), (key, e, mcs)
+        for key, buf in whole.items():
+            tail = buf[-64:].cpu().numpy()
+            assert (tail == tail[0]).all() and tail[0] in (-77, -7.5), key
+    print("cap %d: max deviation %.2e" % (cap, worst))
+
+
+def test_poses_in_global_memory_match_oracle(tmp_path):
+    """sg_contacts_kernel<false>: a model whose poses do not fit LDS beside the staging block.  The plan builder bounds the geoms that
+    collide, not the ones that collide with nothing: a gripper of the sweep with 1400 such geoms on its static body is accepted, and
+    its read-out keeps the poses in a per-env block of global memory.  Two envs, the rest pose and the swept pose with the most
+    contacts, against the oracle."""
+    xml = CR.sweep_gripper_xmls()[MANY_GEOMS_GRIPPER]
+    extra = "".join('<geom type="sphere" size="0.01" pos="%.2f %.2f 1.6" contype="0" conaffinity="0" mass="1e-6"/>\n'
+                    % (0.3 + 0.05 * (k % 37), -0.9 + 0.05 * (k // 37)) for k in range(1400))
+    roof = '<geom class="link" name="roof"'
+    assert xml.count(roof) == 1
+    m = _compile(tmp_path, "many_geoms.xml", xml.replace(roof, extra + roof))
+    assert 35328 + 8 * (7 * m.nbody + 12 * m.ngeom) > POSE_LDS_LIMIT, (m.nbody, m.ngeom)
+    sim = oracle_sim(m)
+    swept = max(CR.pose_sweep(m, 16, CR.SWEEP_POSE_SEED + MANY_GEOMS_GRIPPER), key=lambda q: CR.oracle_contacts(sim, q)["ncon"])
+    qs = np.stack([np.array(m.qpos0, dtype=np.float64), swept])
+    refs = [CR.oracle_contacts(sim, q) for q in qs]
+    assert refs[0]["ncon"] >= 10 and refs[1]["ncon"] >= 64, [r["ncon"] for r in refs]
+    b = _pose_batch(m, qs)
+    out = b.contacts(max_contacts=512)
+    _same_bits(out, b.contacts(max_contacts=512))
+    got = _rows(out)
+    worst = max(CR.compare(got[e], refs[e], "many geoms, env %d" % e) for e in range(2))
+    print("%d bodies, %d geoms: ncon %s, max deviation %.2e" % (m.nbody, m.ngeom, [r["ncon"] for r in refs], worst))
 
 
 @pytest.mark.parametrize("scene,pipeline", [("softbox", "rows"), ("softbox", "tree"), ("freeball_fix", "tree")])
