@@ -3,7 +3,8 @@
   * reference(): a NumPy (fp64) restatement written from the definitions, NOT from the header: Model.kinematics() for the poses, one
     Jacobian column per dof (axis, anchor, the bodies it moves), velocities as column sums, energies from the bodies' masses and inertias;
   * build_host() / host(): the g++ build of csrc/sg_dyn.h run serially, body by body and wrap by wrap, as the kernel's lanes run it;
-  * the scenes and states every test uses: a few oracle steps into a squeeze, a seeded perturbation of qvel, a stiffness per env.
+  * the scenes and states every test uses: a few oracle steps into a squeeze, a seeded perturbation of qvel, a stiffness per env;
+  * sweep(): contacts_ref's random grippers and poses with velocities and a stiffness per state, for the g++ build and the device alike.
 """
 import ctypes as C
 import os
@@ -64,14 +65,107 @@ def states(scene, nsteps=60):
     return _STATES[scene]
 
 
-def stiffness(m, scene, k):
-    """the stiffness vectors env k's next step uses: (jnt_stiffness [njnt], tendon_stiffness [ntendon])"""
-    _, jids, tids, _ = SCENES[scene]
+def _ids(scene, jids, tids):
+    """the joints / tendons that take the per-env stiffness: the explicit lists, or the scene's where one is None"""
+    return (SCENES[scene][1] if jids is None else jids), (SCENES[scene][2] if tids is None else tids)
+
+
+def stiffness(m, scene, k, jids=None, tids=None):
+    """the stiffness vectors env k's next step uses: (jnt_stiffness [njnt], tendon_stiffness [ntendon]).  jids / tids: the listed joints
+    and tendons (None: SCENES[scene]'s; with both given, scene may be None)"""
+    jids, tids = _ids(scene, jids, tids)
     kj, kt = np.array(m.jnt_stiffness, dtype=np.float64), np.array(m.tendon_stiffness, dtype=np.float64)
     if k is not None:
         kj[jids] = k
         kt[tids] = k
     return kj, kt
+
+
+# ---- the sweep of the random grippers: contacts_ref's grippers and poses, given velocities and a stiffness per env ----
+SWEEP_VEL = (0.0, 1.0, 30.0)      # pose i moves at SWEEP_VEL[i % 3] N(0, 1) per dof
+SWEEP_QUAT_SCALE = 1.7            # every fourth pose of a gripper on a free joint carries its free quaternion times this
+SWEEP_VEL_SEED = 4100             # gripper i's velocities are drawn with seed SWEEP_VEL_SEED + its pose seed
+
+
+def sweep_ids(model):
+    """the joints and tendons that take the per-env stiffness in the random grippers: the sliders from the first non-hinge joint on
+    (the shell's; the fingers' hinges come first), tendon 0"""
+    jt = np.asarray(model.jnt_type)
+    nchain = int(np.flatnonzero(jt != 3)[0])
+    return [j for j in range(nchain, model.njnt) if jt[j] == JNT_SLIDE], [0]
+
+
+def velocity_sweep(model, n, seed):
+    """(qpos [n, nq], qvel [n, nv], k [n]): contacts_ref.pose_sweep(model, n, seed) with a state of motion.  Pose i gets qvel =
+    SWEEP_VEL[i % 3] N(0, 1) (so every third pose is at rest); every fourth pose (i % 4 == 0) of a model with a free joint gets that
+    joint's quaternion multiplied by SWEEP_QUAT_SCALE (kinematics normalises it; 3 and 4 are coprime, so every velocity scale meets
+    one); env i's stiffness is KS[i % 3]"""
+    import contacts_ref as CR
+    qpos = CR.pose_sweep(model, n, seed).copy()
+    rs = np.random.RandomState(SWEEP_VEL_SEED + seed)
+    qvel = np.stack([SWEEP_VEL[i % 3] * rs.standard_normal(model.nv) for i in range(n)])
+    for j in np.flatnonzero(np.asarray(model.jnt_type) == JNT_FREE):
+        a = int(model.jnt_qposadr[j])
+        qpos[::4, a + 3:a + 7] *= SWEEP_QUAT_SCALE
+    return qpos, qvel, np.array([KS[i % len(KS)] for i in range(n)])
+
+
+_SWEEP = {}
+OFFSET_GRIPPER = 3        # the sweep's gripper that is swept a second time with its hinges' anchors moved off the body origins
+OFFSET_SEED = 515
+
+
+def offset_anchors(xml, seed=OFFSET_SEED):
+    """the gripper's XML with every hinge given a pos of its own, U(-0.05, 0.05) per axis: random_gripper_xml leaves all joints at
+    their body's origin, where a body's second and third hinge have the anchor the first one had, whatever frame it is taken in"""
+    rs = np.random.RandomState(seed)
+    head, parts = '<joint type="hinge" ', xml.split('<joint type="hinge" ')
+    assert len(parts) > 1
+    return parts[0] + "".join(head + 'pos="%.4f %.4f %.4f" ' % tuple(rs.uniform(-0.05, 0.05, 3)) + rest for rest in parts[1:])
+
+
+def sweep(gripper, tmpdir, offset=False):
+    """gripper `gripper` of contacts_ref's sweep and its states: (model, qpos, qvel, k, joint ids, tendon ids) -- compiled and drawn once,
+    shared and left unchanged.  offset=True: the same gripper through offset_anchors(), swept with the same seeds"""
+    import contacts_ref as CR
+    if (gripper, offset) not in _SWEEP:
+        path = os.path.join(str(tmpdir), "sweep_g%d%s.xml" % (gripper, "_offset" if offset else ""))
+        xml = CR.sweep_gripper_xmls()[gripper]
+        with open(path, "w") as f:
+            f.write(offset_anchors(xml) if offset else xml)
+        m = sg.compile_mjcf(path, composite_neighbors=False)
+        _SWEEP[gripper, offset] = (m,) + velocity_sweep(m, CR.SWEEP_POSES, CR.SWEEP_POSE_SEED + gripper) + sweep_ids(m)
+    return _SWEEP[gripper, offset]
+
+
+SWEEP_CASES = [(g, False) for g in range(6)] + [(OFFSET_GRIPPER, True)]      # (gripper, offset anchors): what both sweep tests run
+
+
+def sweep_reach(m, qpos, qvel, refs):
+    """what a gripper's swept states reach, from the model and the reference's outputs alone: a dict of
+    joints_per_body (set of joint counts over the bodies), slider_on_turning_body (some slider's parent body has |ang| > 1e-3 in some
+    state), nonunit_free_quat (some free quaternion's norm is off 1 by more than 0.1), spatial_sites (set of site counts over the
+    spatial tendons), fixed_tendon_wraps (set of wrap counts over the fixed ones), scales (set of max |qvel| per state, rounded to
+    the sweep's scales), later_hinge_off_origin (some body's second or third hinge has its anchor off the body's origin)"""
+    jt = np.asarray(m.jnt_type)
+    out = dict(joints_per_body={int(x) for x in np.asarray(m.body_jntnum)[1:]}, slider_on_turning_body=False, nonunit_free_quat=False,
+               spatial_sites=set(), fixed_tendon_wraps=set(), scales=set(), later_hinge_off_origin=False)
+    for b in range(1, m.nbody):
+        j0, nj = int(m.body_jntadr[b]), int(m.body_jntnum[b])
+        out["later_hinge_off_origin"] |= bool(nj > 1 and (jt[j0 + 1:j0 + nj] == 3).any() and np.abs(np.asarray(m.jnt_pos)[j0 + 1:j0 + nj]).max() > 1e-3)
+    for t in range(m.ntendon):
+        a, n = int(m.tendon_adr[t]), int(m.tendon_num[t])
+        (out["fixed_tendon_wraps"] if m.wrap_type[a] == WRAP_JOINT else out["spatial_sites"]).add(n)
+    slider_parent = [int(m.body_parentid[b]) for b in range(1, m.nbody)
+                     if (jt[m.body_jntadr[b]:m.body_jntadr[b] + m.body_jntnum[b]] == JNT_SLIDE).any()]
+    for q, v, ref in zip(qpos, qvel, refs):
+        out["slider_on_turning_body"] |= bool(slider_parent) and bool((np.abs(ref["ang"][slider_parent]).max(1) > 1e-3).any())
+        for j in np.flatnonzero(jt == JNT_FREE):
+            a = int(m.jnt_qposadr[j])
+            out["nonunit_free_quat"] |= bool(abs(np.linalg.norm(q[a + 3:a + 7]) - 1.0) > 0.1)
+        top = float(np.abs(v).max())
+        out["scales"].add(0.0 if top == 0 else 1.0 if top < 8 else 30.0)
+    return out
 
 
 # ---- the NumPy reference ----
@@ -295,10 +389,11 @@ def _tables(m):
     return K, Dn
 
 
-def host(L, m, scene, qpos, qvel, k):
-    """the host build's outputs for one env at stiffness k (None: no joint or tendon is listed): reference()'s dict, plus poses [nbody, 7]"""
+def host(L, m, scene, qpos, qvel, k, jids=None, tids=None):
+    """the host build's outputs for one env at stiffness k (None: no joint or tendon is listed): reference()'s dict, plus poses [nbody, 7].
+    jids / tids as in stiffness()"""
     K, Dn = _tables(m)
-    _, jids, tids, _ = SCENES[scene]
+    jids, tids = _ids(scene, jids, tids)
     kmj, kmt = np.zeros(m.njnt, np.int32), np.zeros(max(m.ntendon, 1), np.int32)
     if k is not None:
         kmj[jids] = 1

@@ -97,8 +97,9 @@ def map_rays(xpos, xquat, origin, direction, body=None):
     return o, d
 
 
-def cast(gx, gm, types, sizes, origin, direction, keep=None, max_dist=0.0):
-    """world rays against the geoms -> dist [N] (-1), geom [N] int32 (-1), normal [N, 3] (zeros)"""
+def cast(gx, gm, types, sizes, origin, direction, keep=None, max_dist=0.0, per_geom=False):
+    """world rays against the geoms -> dist [N] (-1), geom [N] int32 (-1), normal [N, 3] (zeros); with per_geom=True a fourth entry:
+    the entry distance of every candidate geom on every ray [ngeom, N] (inf: none), what compare()'s coplanar rule reads"""
     o = np.asarray(origin, dtype=np.float64).reshape(-1, 3)
     d = np.asarray(direction, dtype=np.float64).reshape(-1, 3)
     n, ng = len(o), len(types)
@@ -115,12 +116,12 @@ def cast(gx, gm, types, sizes, origin, direction, keep=None, max_dist=0.0):
         T = np.where(keep, T, np.inf)
     T[:, ~live] = np.inf
     if ng == 0:
-        return np.full(n, -1.0), np.full(n, -1, np.int32), np.zeros((n, 3))
+        return (np.full(n, -1.0), np.full(n, -1, np.int32), np.zeros((n, 3))) + ((T,) if per_geom else ())
     gid = np.argmin(T, 0)                    # (first = smallest id among equal distances)
     t = T[gid, np.arange(n)]
     hit = np.isfinite(t) & ((t <= max_dist) if max_dist > 0 else True)
     nw = np.einsum("nij,nj->ni", np.asarray(gm, dtype=np.float64).reshape(ng, 3, 3)[gid], NL[gid, np.arange(n)])
-    return np.where(hit, t, -1.0), np.where(hit, gid, -1).astype(np.int32), np.where(hit[:, None], nw, 0.0)
+    return (np.where(hit, t, -1.0), np.where(hit, gid, -1).astype(np.int32), np.where(hit[:, None], nw, 0.0)) + ((T,) if per_geom else ())
 
 
 def unstable(gx, gm, types, sizes, origin, direction, keep, max_dist, ref, shift=1e-7, tol=1e-5):
@@ -137,13 +138,35 @@ def unstable(gx, gm, types, sizes, origin, direction, keep, max_dist, ref, shift
     return bad
 
 
-def compare(got, ref, edge, what="", tol=1e-9, cap=0.02):
-    """geom ids exact, dist and normals within tol, off the rays of `edge` (at most `cap` of them); -> number left out"""
+COPLANAR = 1e-12      # two candidates of a ray tie when the reference's own distances to them are this close
+
+
+def coplanar_ties(got, ref, per_geom, tol=1e-9):
+    """[N] bool: the returned geom is not the reference's, but the reference's OWN distance to the returned geom is within COPLANAR of
+    its best distance -- two surfaces in one plane (the two boxes of a link with coplanar faces), where the last bits of two correct
+    evaluations pick the winner -- and the returned distance and normal still agree with the reference's within tol"""
     gd, gg, gn = got
-    rd, rg, rn = ref
+    rd, rg, rn = ref[:3]
+    n = len(rd)
+    both = (gg != rg) & (gg >= 0) & (rg >= 0) & (gg < len(per_geom))
+    t_got = np.where(both, per_geom[np.where(both, gg, 0), np.arange(n)], np.inf)
+    tie = both & (np.abs(t_got - rd) <= COPLANAR) & (np.abs(gd - rd) <= tol)
+    if gn is not None:
+        tie &= np.abs(gn - rn).max(-1) <= tol
+    return tie
+
+
+def compare(got, ref, edge, what="", tol=1e-9, cap=0.02, per_geom=None):
+    """geom ids exact, dist and normals within tol, off the rays of `edge` (at most `cap` of them); -> number left out.
+    per_geom (cast(..., per_geom=True)'s fourth entry; None: the rule is off): rays of coplanar_ties() may be left out too, and count
+    against the same cap"""
+    gd, gg, gn = got
+    rd, rg, rn = ref[:3]
     wrong = (gg != rg) | ~(np.abs(gd - rd) <= tol)
     if gn is not None:
         wrong |= ~(np.abs(gn - rn).max(-1) <= tol)
+    if per_geom is not None:
+        edge = edge | coplanar_ties(got, ref, per_geom, tol)
     assert not (wrong & ~edge).any(), "%s: rays %s differ off the knife edges: got %s / %s, want %s / %s" % (
         what, np.flatnonzero(wrong & ~edge)[:5].tolist(), gg[wrong & ~edge][:5], gd[wrong & ~edge][:5], rg[wrong & ~edge][:5], rd[wrong & ~edge][:5])
     left = int((wrong & edge).sum())
@@ -164,6 +187,36 @@ def scene_rays(gx, types, n, seed):
     o = c + 1.5 * half * u + np.array([0.0, 0.0, 0.2])
     tgt = c + rs.uniform(-0.6, 0.6, (n, 3)) * half
     return o, tgt - o
+
+
+# ---- the ray sweep of the random grippers (tests/test_ray_host.py on the host build, tests/test_gpu_ray.py on the device) ----
+SWEEP_POSES = slice(2, None, 4)      # of a gripper's 64 swept poses (dyn_ref.sweep) every fourth: 16, the last one an aligned pose
+SWEEP_RAYS = 256                     # scene_rays per pose
+SWEEP_RAY_SEED = 9000                # pose p of gripper g casts scene_rays(..., SWEEP_RAY_SEED + 100 g + p)
+
+
+def sweep_poses(gripper, tmpdir):
+    """(model, qpos [16, nq]) of a gripper of the sweep"""
+    import dyn_ref
+    s = dyn_ref.sweep(gripper, tmpdir)
+    return s[0], s[1][SWEEP_POSES]
+
+
+def link_rays(model, n, seed):
+    """n rays in the frame of a random finger link (a body with hinges), which they also exclude: origins U(-0.3, 0.3)^3 around the
+    link's origin -- inside the scene, among the fingers -- in random directions -> (origin [n, 3], direction [n, 3], body [n])"""
+    rs = np.random.RandomState(seed)
+    jt, adr, num = np.asarray(model.jnt_type), np.asarray(model.body_jntadr), np.asarray(model.body_jntnum)
+    links = [b for b in range(1, model.nbody) if num[b] > 0 and (jt[adr[b]:adr[b] + num[b]] == 3).all()]
+    body = int(links[rs.randint(len(links))])
+    return rs.uniform(-0.3, 0.3, (n, 3)), rs.normal(size=(n, 3)), np.full(n, body, np.int32)
+
+
+def count_types(types, gid, counts):
+    """adds the hits of gid by geom type to counts (a dict)"""
+    for t in np.asarray(types)[gid[gid >= 0]]:
+        counts[int(t)] = counts.get(int(t), 0) + 1
+    return counts
 
 
 # ---- the g++ build of csrc/sg_ray_walk.h (over sg_ray.h and sg_ray_skin.h): the walk, the reduction and the finish the kernels compile ----

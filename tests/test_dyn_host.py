@@ -1,5 +1,6 @@
 """The velocity / tendon / energy read-outs without a GPU: the NumPy reference (tests/dyn_ref.py) pinned to the oracle and to finite
-differences of the poses, the g++ build of csrc/sg_dyn.h against that reference, the per-env stiffness in the spring terms, and the entry
+differences of the poses, the g++ build of csrc/sg_dyn.h against that reference (on the scenes' states and over the sweep of random
+grippers the device test runs), the per-env stiffness in the spring terms, and the entry
 points' argument checks.
 
 Sign convention found for the gravity term (test 1d): the oracle's qfrc_bias is the left-hand side's bias, M qacc + qfrc_bias = applied
@@ -138,6 +139,57 @@ def test_host_build_matches_the_reference(scene, hostlib):
         print(scene, "energy", got["energy"], "relative deviation", dev)
         assert (dev <= DR.REL).all(), (scene, dev)
         assert (got["ang"][0] == 0).all() and (got["lin"][0] == 0).all() and (got["com_lin"][0] == 0).all()
+
+
+def test_sweep_of_random_grippers_matches_the_reference(hostlib, tmp_path):
+    """the sweep of dyn_ref (contacts_ref's six random grippers, 64 poses each far out of the joint ranges, qvel of scale 0, 1 and 30, a
+    stiffness per state; and gripper 3 once more with every hinge's anchor moved off its body's origin) on the g++ build against the NumPy reference: 1e-12 max(1, max |value|) per array, the energy terms 1e-11 of
+    the PLAIN scale (no fixed-tendon allowance: every pose moves the sliders, the volume tendon's length does not cancel), poses
+    against Model.kinematics().  And what the device test of the same states (tests/test_gpu_dyn.py) relies on the sweep to reach:
+    bodies with 1, 2 and 3 joints, a slider on a turning body, a free quaternion off unit length, spatial tendons of 2 sites and of
+    >= 5, a fixed tendon, a second or third hinge with an anchor off the body's origin, all three velocity scales -- with every
+    velocity output exactly zero at scale 0.
+    Measured: arrays <= 1.3e-2 of their bound, energy terms <= 2.7e-13 of their scale, poses <= 5.6e-16"""
+    import contacts_ref as CR
+    worst = dict(arrays=0.0, energy=0.0, poses=0.0)
+    reach = dict(joints_per_body=set(), slider_on_turning_body=False, nonunit_free_quat=False, spatial_sites=set(), fixed_tendon_wraps=set(), scales=set(),
+                 later_hinge_off_origin=False)
+    states = 0
+    assert len(DR.SWEEP_CASES) == CR.SWEEP_GRIPPERS + 1
+    for g, offset in DR.SWEEP_CASES:
+        m, qpos, qvel, ks, jids, tids = DR.sweep(g, tmp_path, offset)
+        refs = []
+        for q, v, k in zip(qpos, qvel, ks):
+            kj, kt = DR.stiffness(m, None, k, jids, tids)
+            ref = DR.reference(m, q, v, kj, kt)
+            refs.append(ref)
+            got = DR.host(hostlib, m, None, q, v, k, jids, tids)
+            for name in ("ang", "lin", "com_lin", "length", "velocity"):
+                dev = DR.close(got[name], ref[name])
+                worst["arrays"] = max(worst["arrays"], dev)
+                assert dev <= 1.0, (g, states, name, dev)
+                if not v.any():
+                    assert name == "length" or not got[name].any(), (g, states, name)
+            dev = float(np.abs(got["poses"] - np.concatenate([ref["kin"]["xpos"], ref["kin"]["xquat"]], 1)).max())
+            worst["poses"] = max(worst["poses"], dev)
+            assert dev <= 1e-12, (g, states, dev)
+            scale = DR.energy_scale(m, ref, kj, kt, q, v)
+            dev = np.abs(got["energy"] - ref["energy"]) / np.maximum(scale, 1e-300)
+            worst["energy"] = max(worst["energy"], float(dev.max()))
+            assert (dev <= DR.REL).all(), (g, states, dev)
+            assert v.any() or got["energy"][3] == 0.0
+            states += 1
+        r = DR.sweep_reach(m, qpos, qvel, refs)
+        print("gripper %d%s: %d bodies, %d joints, %s" % (g, " with offset anchors" if offset else "", m.nbody, m.njnt, r))
+        for key, val in r.items():
+            reach[key] = reach[key] | val
+    print("%d states, worst deviations: %s" % (states, worst))
+    assert states == (CR.SWEEP_GRIPPERS + 1) * CR.SWEEP_POSES
+    assert {1, 2, 3} <= reach["joints_per_body"], reach
+    assert reach["slider_on_turning_body"] and reach["nonunit_free_quat"] and reach["later_hinge_off_origin"], reach
+    assert 2 in reach["spatial_sites"] and max(reach["spatial_sites"]) >= 5, reach
+    assert reach["fixed_tendon_wraps"], reach
+    assert reach["scales"] == {0.0, 1.0, 30.0}, reach
 
 
 @pytest.mark.parametrize("scene", ["softbox_fix", "freeball_fix"])

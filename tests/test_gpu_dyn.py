@@ -1,5 +1,6 @@
 """sg_get_velocities / sg_get_tendons / sg_get_energy on the GPU: the three entry points against the NumPy reference (tests/dyn_ref.py,
-itself pinned to the oracle by tests/test_dyn_host.py) and straight against the oracle, the calls' interface (env lists, NULL outputs, NaN
+itself pinned to the oracle by tests/test_dyn_host.py) and straight against the oracle, over a sweep of random grippers far out of
+their joint ranges (with sg_get_poses) and at the body limit, the calls' interface (env lists, NULL outputs, NaN
 envs, determinism, no side effect, stream ordering against sg_set_stiffness) and ManEnv.rollout(energy_out=...)."""
 import ctypes as C
 import itertools
@@ -61,20 +62,26 @@ def _same_bits(a, b):
     return a.shape == b.shape and bool(torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64)))
 
 
-def _against_reference(m, scene, got, qpos, qvel, ks, what):
+def _against_reference(m, scene, got, qpos, qvel, ks, what, jids=None, tids=None):
+    """every env of `got` against the NumPy reference at the bounds of dyn_ref; -> the worst deviation per output, the arrays' in units
+    of their bound, the energy terms' relative to their scale.  jids / tids: the listed joints / tendons (None: the scene's)"""
+    worst = dict.fromkeys(VEL + TEN + ("energy",), 0.0)
     for e, k in enumerate(ks):
-        kj, kt = DR.stiffness(m, scene, k)
+        kj, kt = DR.stiffness(m, scene, k, jids, tids)
         ref = DR.reference(m, qpos[e], qvel[e], kj, kt)
         for name in VEL + TEN:
             dev = DR.close(got[name][e], ref[name])
+            worst[name] = max(worst[name], dev)
             assert dev <= 1.0, (what, e, name, dev)
         scale = DR.energy_scale(m, ref, kj, kt, qpos[e], qvel[e], allowance=scene in DR.ALLOW_FIXED_TENDON)
         dev = np.abs(got["energy"][e] - ref["energy"]) / np.maximum(scale, 1e-300)
         plain = DR.energy_scale(m, ref, kj, kt, qpos[e], qvel[e])[2]
         print(what, "env", e, "energy", got["energy"][e], "relative deviation", dev, "tendon term against the plain scale",
               abs(got["energy"][e, 2] - ref["energy"][2]) / max(plain, 1e-300))
+        worst["energy"] = max(worst["energy"], float(dev.max()))
         assert (dev <= DR.REL).all(), (what, e, dev)
         assert (got["ang"][e, 0] == 0).all() and (got["lin"][e, 0] == 0).all() and (got["com_lin"][e, 0] == 0).all()
+    return worst
 
 
 @pytest.mark.parametrize("scene,pipeline", [("softbox", None), ("softbox_fix", None), ("softbox_fix", "tree"), ("fourfinger_softball_fix", None),
@@ -123,6 +130,149 @@ def test_entry_points_match_the_oracle(scene):
         for t in range(m.ntendon):
             scale = DR.length_scale(m, t, st["qpos"], sim.ten_length)
             assert abs(got["length"][e, t] - sim.ten_length[t]) <= DR.REL * scale, (e, t)
+
+
+# ---- the sweep of dyn_ref: random grippers far out of their joint ranges, one env per state, nothing stepped ----
+def _state_batch(m, qpos, qvel, ks, jids, tids):
+    """a batch with one env per state: one sg_set_state(qpos, qvel), one sg_set_stiffness"""
+    from softgrip_amd import native
+    torch = _torch()
+    b = native.NativeBatch(native.NativeModel(m), len(ks), 0)
+    T = lambda a: torch.tensor(np.ascontiguousarray(a), dtype=torch.float64, device=b.device)  # noqa: E731
+    b.set_state(qpos=T(qpos), qvel=T(qvel))
+    b.set_stiffness(np.asarray(ks, dtype=np.float64), jids, tids)
+    return b
+
+
+def _against_kinematics(m, p, qpos, what):
+    """poses() of every env against Model.kinematics() / render_ref.geom_poses at tests/test_gpu_render.py's 1e-12 -> worst deviation"""
+    import render_ref as R
+    worst = 0.0
+    for e, q in enumerate(qpos):
+        kin = m.kinematics(q)
+        gx, gm = R.geom_poses(m, q)
+        for name, want in (("xpos", kin["xpos"]), ("xquat", kin["xquat"]), ("geom_xpos", gx), ("geom_xmat", np.reshape(gm, (-1, 9)))):
+            dev = float(np.abs(p[name][e] - want).max())
+            worst = max(worst, dev)
+            assert dev < 1e-12, (what, e, name, dev)
+    return worst
+
+
+@pytest.mark.parametrize("gripper,offset", DR.SWEEP_CASES)
+def test_sweep_of_random_grippers_matches_the_reference(gripper, offset, tmp_path):
+    """64 states of a random gripper (dyn_ref.sweep: contacts_ref's grippers and poses, links turned up to 3 rad about up to three
+    hinges per body, sliders moved, every second gripper's shell on a free joint -- every fourth of its states with the free
+    quaternion scaled by 1.7 -- qvel of scale 0, 1 and 30, a stiffness per env) as 64 envs of one batch: one sg_set_state, one
+    sg_set_stiffness, then poses(), velocities(), tendons() and energy() once each.  Poses against Model.kinematics() at 1e-12; the
+    rest against the NumPy reference at 1e-12 max(1, max |value|) per array and 1e-11 of the PLAIN scale per energy term.  No state is
+    left out.  The seventh case is gripper 3 with every hinge's anchor moved off its body's origin (dyn_ref.offset_anchors): the
+    generator leaves all joints at the origin, where it does not matter in which frame a body's second hinge takes its anchor.
+    What the states reach is asserted on the CPU by tests/test_dyn_host.py's test of the same name.
+    sg_set_state neither refuses nor normalises a free quaternion off unit length: it stores qpos as given (sg_get_state returns the
+    same bits) and every read-out normalises on the way, as Model.kinematics() does.
+    Measured on the MI355X, worst over the cases: poses 1.0e-15; in units of the arrays' bound ang 9.3e-4, lin 8.7e-4,
+    com_lin 9.9e-4, length 4.9e-4, velocity 3.4e-3; energy terms 2.0e-13 of their scale"""
+    import contacts_ref as CR
+    assert len(DR.SWEEP_CASES) == CR.SWEEP_GRIPPERS + 1
+    m, qpos, qvel, ks, jids, tids = DR.sweep(gripper, tmp_path, offset)
+    b = _state_batch(m, qpos, qvel, ks, jids, tids)
+    p = {k: v.cpu().numpy() for k, v in b.poses().items()}
+    got = _host(_all(b))
+    st = b.get_state()
+    assert st["qpos"].cpu().numpy().tobytes() == np.ascontiguousarray(qpos).tobytes()      # stored as given, non-unit quaternions too
+    free = [int(m.jnt_qposadr[j]) for j in range(m.njnt) if m.jnt_type[j] == 0]
+    assert bool(free) == bool(gripper % 2)
+    for a in free:
+        assert abs(np.linalg.norm(qpos[0, a + 3:a + 7]) - DR.SWEEP_QUAT_SCALE) < 1e-12
+    what = "gripper %d%s" % (gripper, " with offset anchors" if offset else "")
+    wp = _against_kinematics(m, p, qpos, what)
+    worst = _against_reference(m, None, got, qpos, qvel, ks, what, jids, tids)
+    for e in range(len(ks)):
+        if not qvel[e].any():      # at rest: every velocity output is exactly zero
+            assert not any(got[name][e].any() for name in VEL + ("velocity",)) and got["energy"][e, 3] == 0.0, e
+    print("%s: %d bodies, %d states, poses off by at most %.2e; arrays in units of their bound, energy relative: %s"
+          % (what, m.nbody, len(ks), wp, {k: "%.2e" % v for k, v in worst.items()}))
+    assert len(ks) == CR.SWEEP_POSES == 64
+
+
+# ---- the body limit (SGD_MAXBODY, csrc/sg_dyn.h) on the device ----
+MAXBODY = 627
+PAD_GRIPPER = 1      # a gripper of the sweep on a free joint
+
+
+def _padded(tmp_path, nbody):
+    """the sweep's gripper PAD_GRIPPER with jointless child bodies of its static body, each with one sphere of 1 cm that collides with
+    nothing, up to nbody bodies: one wide level of the kernels' depth schedule"""
+    import softgrip_amd as sg
+    import contacts_ref as CR
+    xml = CR.sweep_gripper_xmls()[PAD_GRIPPER]
+    base = DR.sweep(PAD_GRIPPER, tmp_path)[0]
+    roof = '<geom class="link" name="roof"'
+    assert xml.count(roof) == 1
+    extra = "".join('<body pos="%.2f %.2f 1.6"><geom type="sphere" size="0.01" contype="0" conaffinity="0" mass="1e-6"/></body>\n'
+                    % (0.3 + 0.05 * (k % 37), -0.9 + 0.05 * (k // 37)) for k in range(nbody - base.nbody))
+    path = tmp_path / ("padded_%d.xml" % nbody)
+    path.write_text(xml.replace(roof, extra + roof))
+    m = sg.compile_mjcf(str(path), composite_neighbors=False)
+    assert m.nbody == nbody, (m.nbody, nbody)
+    return m
+
+
+def _padded_states(m, tmp_path):
+    """two states of a padded model: a swept pose of the unpadded gripper's sweep and the rest pose, qvel of scale 1.  The padding adds
+    no joint, so the unpadded gripper's qpos and qvel fit"""
+    base, qpos, qvel = DR.sweep(PAD_GRIPPER, tmp_path)[:3]
+    assert m.nq == base.nq and m.nv == base.nv
+    q = np.stack([qpos[4], np.array(m.qpos0, dtype=np.float64)])      # (pose 4: hinges swung by up to 1.5 rad, the free quaternion times 1.7)
+    v = np.stack([qvel[4], qvel[1]])
+    assert abs(np.abs(v[0]).max() - 3) < 3 and abs(np.abs(v[1]).max() - 3) < 3      # (both of scale 1)
+    return q, v, DR.KS[:2]
+
+
+def test_body_limit_is_reached_on_the_device(tmp_path):
+    """627 bodies, SGD_MAXBODY: the launch asks for 65 208 B of dynamic LDS beside the kernel's 256 B of static LDS, and the padded
+    static body's ~575 children are one level of nine 64-strides (the widest level of a committed scene has four).  Two envs -- a
+    swept pose and the rest pose, qvel of scale 1 -- match the reference at the sweep's bounds, and poses() matches
+    Model.kinematics().  Measured on the MI355X: 576 children in the widest level, poses 3.3e-16, arrays <= 4.3e-4 of their bound,
+    energy terms <= 7.1e-16"""
+    m = _padded(tmp_path, MAXBODY)
+    jids, tids = DR.sweep_ids(m)
+    q, v, ks = _padded_states(m, tmp_path)
+    b = _state_batch(m, q, v, ks, jids, tids)
+    got = _host(_all(b))
+    worst = _against_reference(m, None, got, q, v, ks, "%d bodies" % MAXBODY, jids, tids)
+    wp = _against_kinematics(m, {k: x.cpu().numpy() for k, x in b.poses().items()}, q, "%d bodies" % MAXBODY)
+    widest = int(np.bincount(np.asarray(m.body_parentid)[1:]).max())
+    print("%d bodies, %d of them children of one body: poses off by at most %.2e, %s" % (m.nbody, widest, wp, {k: "%.2e" % x for k, x in worst.items()}))
+    assert widest > 8 * 64
+
+
+def test_one_body_beyond_the_limit_is_refused(tmp_path):
+    """628 bodies: each of the three entry points returns SG_ERR_MODEL under its own name with "more than 627 bodies" and writes
+    nothing (canary), and poses() of the same batch still answers correctly"""
+    from softgrip_amd import native
+    from softgrip_amd.native import _ptr
+    torch = _torch()
+    m = _padded(tmp_path, MAXBODY + 1)
+    jids, tids = DR.sweep_ids(m)
+    q, v, ks = _padded_states(m, tmp_path)
+    b = _state_batch(m, q, v, ks, jids, tids)
+    kw = dict(dtype=torch.float64, device=b.device)
+    out = {n: torch.full((2, m.nbody, 3), -7.5, **kw) for n in VEL}
+    out.update({n: torch.full((2, m.ntendon), -7.5, **kw) for n in TEN})
+    out["energy"] = torch.full((2, 4), -7.5, **kw)
+    L, s = b.L, b._stream()
+    calls = (("sg_get_velocities", lambda: L.sg_get_velocities(b.ptr, None, 2, _ptr(out["ang"]), _ptr(out["lin"]), _ptr(out["com_lin"]), s)),
+             ("sg_get_tendons", lambda: L.sg_get_tendons(b.ptr, None, 2, _ptr(out["length"]), _ptr(out["velocity"]), s)),
+             ("sg_get_energy", lambda: L.sg_get_energy(b.ptr, None, 2, _ptr(out["energy"]), s)))
+    for name, call in calls:
+        assert call() == native.SG_ERR_MODEL, name
+        msg = L.sg_last_error()
+        assert msg.startswith(name.encode() + b":") and b"more than %d bodies" % MAXBODY in msg, (name, msg)
+    torch.cuda.synchronize()
+    for n, x in out.items():
+        assert bool((x == -7.5).all()), n
+    _against_kinematics(m, {k: x.cpu().numpy() for k, x in b.poses().items()}, q, "%d bodies" % (MAXBODY + 1))
 
 
 def _raw(b, ids, n_ids, out):

@@ -1,5 +1,5 @@
 """sg_ray on the GPU: world-frame rays against the NumPy reference (tests/ray_ref.py) on the device's own poses, under both kernel
-layouts; body-frame rays and exclusion; the call's interface (shapes around the block and wavefront sizes, per-env rays, env subsets, NULL
+layouts, on the committed scenes and over a pose sweep of random grippers; body-frame rays and exclusion; the call's interface (shapes around the block and wavefront sizes, per-env rays, env subsets, NULL
 outputs, a zero direction, NaN envs, category masks, every argument error); bit-identical layouts; no side effect on a following step;
 the renderer's picture through sg_ray; and ManEnv.tactile_depth."""
 import contextlib
@@ -104,6 +104,64 @@ def test_world_rays_match_reference(scene, nenv, nrays):
     print("%s: %d rays, %d hits on %d distinct geoms, %d left out" % (scene, total, hits, len(seen), left))
     assert hits > 0.8 * total and len(seen) >= 30
     assert left <= 0.02 * total
+
+
+@pytest.mark.parametrize("gripper", range(6))
+def test_sweep_of_random_grippers_matches_reference(gripper, tmp_path):
+    """the ray sweep of ray_ref on the device: 16 swept poses of a random gripper (links turned up to 3 rad about up to three axes,
+    every second gripper's shell on a free joint at a random attitude) as 16 envs of one batch, one sg_set_state, nothing stepped; 256
+    rays of the recipe per env, rays of its own for each.  Both layouts, which agree bit for bit, against the reference on the
+    device's own poses: ids exact, distances and normals within 1e-9.  Then one call of 256 rays in the frame of a random link, that
+    link excluded: origins inside the scene, among the fingers.  Left out, at most 2 % of the gripper's rays of either kind: rays on
+    which the reference's own answer changes under a 1e-7 m shift of the origin, and coplanar ties (ray_ref.coplanar_ties: another
+    geom, to which the reference's own distance is within 1e-12 of its best; distance and normal still within 1e-9).  That the sweep
+    hits planes, boxes and capsules is asserted on the CPU by tests/test_ray_host.py's test of the same sweep.
+    Measured on the MI355X over the six grippers: 24 576 world rays, 23 810 hits (planes 7 914, boxes 14 854, capsules
+    1 039, the centre sphere 3), 3 left out; 24 576 link rays, 16 127 hits (planes 8 736, boxes 6 745, capsules 642, sphere 4), 9 left
+    out, one of the 12 a coplanar tie off the knife edges (gripper 5)"""
+    import torch
+    from softgrip_amd import native
+    m, qs = RR.sweep_poses(gripper, tmp_path)
+    ty, sz, cats, gb = _geoms(m)
+    nenv, nrays = len(qs), RR.SWEEP_RAYS
+    assert nenv == 16
+    b = native.NativeBatch(native.NativeModel(m), nenv, 0)
+    b.set_state(qpos=torch.tensor(np.ascontiguousarray(qs), dtype=torch.float64, device=b.device))
+    p = _poses(b)
+    rays = [RR.scene_rays(p["geom_xpos"][e], ty, nrays, RR.SWEEP_RAY_SEED + 100 * gripper + e) for e in range(nenv)]
+    o = torch.tensor(np.stack([r[0] for r in rays]), device=b.device)
+    d = torch.tensor(np.stack([r[1] for r in rays]), device=b.device)
+    got = {}
+    for lay in LAYOUTS:
+        with layout(lay):
+            got[lay] = _host(b.raycast(o, d, normals=True))
+    for x, y in zip(got["rays"], got["geoms"]):
+        assert x.tobytes() == y.tobytes(), gripper
+    ol, dl, rb = RR.link_rays(m, nrays, RR.SWEEP_RAY_SEED + gripper)
+    link = _host(b.raycast(torch.tensor(ol, device=b.device), torch.tensor(dl, device=b.device), body=rb, exclude=rb, normals=True))
+    keep = RR.candidates(cats, gb, RR.ALL_BITS, rb, nrays)
+    left = lleft = ties = 0
+    kinds, lkinds = {}, {}
+    for e in range(nenv):
+        gx, gm = p["geom_xpos"][e], p["geom_xmat"][e].reshape(-1, 3, 3)
+        ref = RR.cast(gx, gm, ty, sz, *rays[e], per_geom=True)
+        edge = RR.unstable(gx, gm, ty, sz, rays[e][0], rays[e][1], None, 0.0, ref)
+        mine = tuple(x[e] for x in got["rays"])
+        left += RR.compare(mine, ref, edge, "gripper %d env %d" % (gripper, e), cap=1.0, per_geom=ref[3])
+        ties += int((RR.coplanar_ties(mine, ref, ref[3]) & ~edge).sum())
+        RR.count_types(ty, ref[1], kinds)
+        ow, dw = RR.map_rays(p["xpos"][e], p["xquat"][e], ol, dl, rb)
+        ref = RR.cast(gx, gm, ty, sz, ow, dw, keep, per_geom=True)
+        edge = RR.unstable(gx, gm, ty, sz, ow, dw, keep, 0.0, ref)
+        mine = tuple(x[e] for x in link)
+        lleft += RR.compare(mine, ref, edge, "gripper %d env %d link %d" % (gripper, e, rb[0]), cap=1.0, per_geom=ref[3])
+        ties += int((RR.coplanar_ties(mine, ref, ref[3]) & ~edge).sum())
+        assert not (gb[ref[1][ref[1] >= 0]] == rb[0]).any()
+        RR.count_types(ty, ref[1], lkinds)
+    print("gripper %d: %d world rays, hits by geom type %s, %d left out; %d rays of link %d, hits %s, %d left out; coplanar ties off the knife edges: %d"
+          % (gripper, nenv * nrays, kinds, left, nenv * nrays, rb[0], lkinds, lleft, ties))
+    assert sum(kinds.values()) > 0.8 * nenv * nrays and sum(lkinds.values()) > 0.3 * nenv * nrays
+    assert left <= 0.02 * nenv * nrays and lleft <= 0.02 * nenv * nrays, (left, lleft)
 
 
 def test_body_frame_rays_and_exclusion():

@@ -1,6 +1,7 @@
 """Ray queries (sg_ray) without a GPU: the g++ build of csrc/sg_ray.h -- the per-ray math both kernel layouts run -- against the
-independent NumPy caster (tests/ray_ref.py), analytic known answers per primitive, the tie rule, the ABI entry point's checks that need
-no device, the kept assembly of the two kernels and the ray construction of ManEnv.tactile_depth."""
+independent NumPy caster (tests/ray_ref.py) on the committed scenes and over a pose sweep of random grippers, analytic known answers
+per primitive, the tie rule, the ABI entry point's checks that need no device, the kept assembly of the two kernels and the ray
+construction of ManEnv.tactile_depth."""
 import ctypes as C
 import os
 import re
@@ -62,6 +63,63 @@ def test_host_build_matches_numpy_caster(host, scene):
         assert not np.isin(ref2[1], np.flatnonzero((gb == body) | (cats == 0))).any()
     print("%s: %d rays, %d hits, %d left out" % (scene, total, hits, left))
     assert hits > 0.5 * total
+
+
+def test_sweep_of_random_grippers_matches_numpy_caster(host, tmp_path):
+    """the ray sweep of ray_ref: six random grippers, 16 of each one's swept poses (links turned up to 3 rad about up to three axes,
+    every second gripper's shell on a free joint at a random attitude), 256 rays of the recipe per pose.  Ids exact, distances and
+    normals within 1e-9, both reduction orders bit-identical.  Left out, at most 2 % of a gripper's rays: rays on which the
+    reference's own answer changes under a 1e-7 m shift of the origin, and coplanar ties -- the returned geom is another one, the
+    reference's own distance to it is within 1e-12 of its best (the two boxes of a link have coplanar faces), distance and normal
+    still agree.  Also the same sweep with rays in a random link's frame, that link excluded: origins inside the scene.
+    Measured: 24 576 world rays, 23 810 hits (planes 7 914, boxes 14 854, capsules 1 039, the centre sphere 3), 82 rays unstable by
+    the reference alone (0.33 %), 5 left out; 24 576 link rays, 16 662 hits (planes 9 120, boxes 6 632, capsules 899), 16 left out; of
+    the 21 rays left out 8 are coplanar ties off the knife edges: without the rule the comparison fails"""
+    import contacts_ref as CR
+    kinds, total, edges, left_all, ties = {}, 0, 0, 0, 0
+    lkinds, lleft = {}, 0
+    for g in range(CR.SWEEP_GRIPPERS):
+        m, qs = RR.sweep_poses(g, tmp_path)
+        left = lcount = 0
+        for p, q in enumerate(qs):
+            gx, gm, ty, sz, cats, gb = _scene(m, q)
+            o, d = RR.scene_rays(gx, ty, RR.SWEEP_RAYS, RR.SWEEP_RAY_SEED + 100 * g + p)
+            ref = RR.cast(gx, gm, ty, sz, o, d, per_geom=True)
+            got = RR.cast_with(host, gx, gm, ty, sz, cats, gb, o, d)
+            alt = RR.cast_with(host, gx, gm, ty, sz, cats, gb, o, d, layout=1)
+            for x, y in zip(got, alt):
+                assert x.tobytes() == y.tobytes(), (g, p)
+            edge = RR.unstable(gx, gm, ty, sz, o, d, None, 0.0, ref)
+            left += RR.compare(got, ref, edge, "gripper %d pose %d" % (g, p), cap=1.0, per_geom=ref[3])
+            ties += int((RR.coplanar_ties(got, ref, ref[3]) & ~edge).sum())
+            edges += int(edge.sum())
+            total += len(o)
+            RR.count_types(ty, ref[1], kinds)
+            # rays bound to a link, which they do not see
+            kin = m.kinematics(q)
+            ol, dl, rb = RR.link_rays(m, RR.SWEEP_RAYS, RR.SWEEP_RAY_SEED + 100 * g + p)
+            keep = RR.candidates(cats, gb, RR.ALL_BITS, rb, len(ol))
+            ow, dw = RR.map_rays(kin["xpos"], kin["xquat"], ol, dl, rb)
+            ref2 = RR.cast(gx, gm, ty, sz, ow, dw, keep, per_geom=True)
+            edge2 = RR.unstable(gx, gm, ty, sz, ow, dw, keep, 0.0, ref2)
+            for lay in (0, 1):
+                got2 = RR.cast_with(host, gx, gm, ty, sz, cats, gb, ol, dl, kin["xpos"], kin["xquat"], rb, rb, RR.ALL_BITS, 0.0, lay)
+                n2 = RR.compare(got2, ref2, edge2, "gripper %d pose %d link %d layout %d" % (g, p, rb[0], lay), cap=1.0, per_geom=ref2[3])
+            ties += int((RR.coplanar_ties(got2, ref2, ref2[3]) & ~edge2).sum())
+            lcount += n2
+            assert not (gb[ref2[1][ref2[1] >= 0]] == rb[0]).any()
+            RR.count_types(ty, ref2[1], lkinds)
+        print("gripper %d: %d rays, left out %d; link rays: left out %d" % (g, len(qs) * RR.SWEEP_RAYS, left, lcount))
+        assert len(qs) == 16
+        assert left <= 0.02 * len(qs) * RR.SWEEP_RAYS and lcount <= 0.02 * len(qs) * RR.SWEEP_RAYS, (g, left, lcount)
+        left_all += left
+        lleft += lcount
+    print("%d rays, hits by geom type %s, %d knife-edge rays by the reference alone, %d left out; link rays: hits %s, %d left out; coplanar ties off the knife edges, both kinds: %d"
+          % (total, kinds, edges, left_all, lkinds, lleft, ties))
+    assert total == CR.SWEEP_GRIPPERS * 16 * RR.SWEEP_RAYS
+    for t in (RR.PLANE, RR.BOX, RR.CAPSULE):
+        assert kinds.get(t, 0) > 0, kinds
+    assert lkinds.get(RR.BOX, 0) > 0 and lkinds.get(RR.CAPSULE, 0) > 0, lkinds
 
 
 def _single(type_, size, pos=(0.0, 0.0, 0.0), mat=None):
