@@ -146,6 +146,7 @@ int sg_model_create(const void* blob, size_t nbytes, sg_model** out) {
   sgk_build(blob, nbytes, m->has_fast ? m->plan : m->tplan, m->has_tree ? &m->tree : nullptr, m->has_fast, &m->kin);
   sgc_from_blob(blob, nbytes, m->kin, &m->con);
   sgd_build(blob, nbytes, m->kin, &m->dyn);
+  sgs_build(blob, nbytes, m->kin, m->dyn, &m->smooth);
   m->rounds = (m->plan.h.nelem + 63) / 64;
   if (m->rounds > 4) {
     delete m;

@@ -8,6 +8,7 @@
 
 #include "sg_readout.h"
 #include "sg_dyn.h"
+#include "sg_smooth.h"
 #include "sg_skin.h"
 #include "sg_rows_host.h"   // (sg_work.h, sg_plan.h)
 #include "sg_devmem.h"   // SgArena, SgScratch: the owners of every device buffer below (after the HIP runtime's declarations)
@@ -34,6 +35,7 @@ struct sg_model {
   SgKinHost kin;    // kinematics table of sg_get_poses / sg_render
   SgConHost con;    // candidate pairs, margins and bounding radii of sg_get_contacts
   SgDynHost dyn;    // masses, springs, sites and tendons of sg_get_velocities / sg_get_tendons / sg_get_energy
+  SgSmoothHost smooth;   // dampers, actuators, child lists and parent dofs of sg_get_mass_matrix / sg_get_joint_forces / sg_inverse_dynamics
   SgSkinHost skin;  // the composite's skin (sg_skin.h; nvert == 0: none): sg_model_set_skin, drawn by sg_render_ex
 };
 
@@ -116,6 +118,10 @@ struct sg_batch {
   // velocity, tendon and energy read-outs: the dynamics table
   double* dyn_d = nullptr;
   int* dyn_i = nullptr;
+  // mass-matrix, joint-force and inverse-dynamics read-outs: the smooth table
+  double* smooth_d = nullptr;
+  int* smooth_i = nullptr;
+  bool smooth_attr_set = false;
   ~sg_batch() {   // (on the batch's device: sg_batch_destroy.  The arenas and scratch buffers free themselves)
     for (auto& e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (auto& e : ev_pgs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }

@@ -1,6 +1,7 @@
 // sg_readout.hip -- the read-out half of the C ABI (include/softgrip.h): sg_get_poses, sg_render / sg_render_ex and the skin,
-// sg_get_contacts, sg_ray, sg_get_velocities / sg_get_tendons / sg_get_energy, with the kernels they launch (the *_kernel*.h files, whose
-// device assembly is sg_readout.device.s) and the host builders of their per-model tables (sg_readout.h, sg_dyn.h).  None of them writes the state: every pipeline is served.  No CPU fallback.
+// sg_get_contacts, sg_ray, sg_get_velocities / sg_get_tendons / sg_get_energy, sg_get_mass_matrix / sg_get_joint_forces /
+// sg_inverse_dynamics, with the kernels they launch (the *_kernel*.h files, whose
+// device assembly is sg_readout.device.s) and the host builders of their per-model tables (sg_readout.h, sg_dyn.h, sg_smooth.h).  None of them writes the state: every pipeline is served.  No CPU fallback.
 #include <algorithm>
 #include <cstring>
 #include <type_traits>
@@ -12,6 +13,7 @@
 #include "sg_ray_kernels.h"
 #include "sg_ray_skin_kernels.h"
 #include "sg_dyn_kernel.h"
+#include "sg_smooth_kernel.h"
 
 // ---- the builders sg_model_create calls (sg_readout.h) ----
 // an array of the blob as `var`, its length in c (want >= 0: that many elements), or the builder ends with T->err set
@@ -231,6 +233,61 @@ void sgd_build(const void* blob, size_t nbytes, const SgKinHost& K, SgDynHost* T
   o.jdof = puti(jd.data(), nj); o.sbody = puti(sbody, ns); o.tadr = puti(tadr, nt); o.tnum = puti(tnum, nt); o.wtype = puti(wtype, nw);
   o.wobj = puti(wobj, nw);
   if (I.empty()) I.push_back(0);   // (a model without joints, sites and tendons: the upload still has something to hold)
+  T->ok = true;
+}
+
+// the smooth table (sg_smooth.h): per dof its damping, its body and its parent dof (the dof before it on the same body, else the last dof
+// of the nearest ancestor that has one, else -1); per tendon its damping; the actuators on their tendons; the bodies' child lists
+void sgs_build(const void* blob, size_t nbytes, const SgKinHost& K, const SgDynHost& Dn, SgSmoothHost* T) {
+  if (!K.ok) { T->err = K.err; return; }
+  if (K.o.nbody > SGS_MAXBODY) { T->err = "more than " + std::to_string(SGS_MAXBODY) + " bodies"; return; }
+  if (!Dn.ok) { T->err = Dn.err; return; }
+  const long long nb = K.o.nbody, nv = Dn.o.nv, nt = Dn.o.ntendon;
+  if (nv > SGS_MAXDOF) { T->err = "more than " + std::to_string(SGS_MAXDOF) + " dofs"; return; }
+  if (nt > SGS_MAXTENDON) { T->err = "more than " + std::to_string(SGS_MAXTENDON) + " tendons"; return; }
+  long long c = 0, nu = 0;
+  SG_FIELD(T, ddamp, "dof_damping", SG_DT_F64, nv);
+  SG_FIELD(T, tdamp, "tendon_damping", SG_DT_F64, nt);
+  SG_FIELD(T, atrn, "actuator_trnid", SG_DT_I32, -1);
+  nu = c;
+  SG_FIELD(T, again, "actuator_gain", SG_DT_F64, nu);
+  SG_FIELD(T, abias, "actuator_bias", SG_DT_F64, 3 * nu);
+  SG_FIELD(T, agear, "actuator_gear", SG_DT_F64, nu);
+  for (int u = 0; u < nu; u++)
+    if (atrn[u] < 0 || atrn[u] >= nt) { T->err = "actuator tendon out of range"; return; }
+  const int *par = K.ints.data() + K.o.bpar, *jadr = K.ints.data() + K.o.bjadr, *jnum = K.ints.data() + K.o.bjnum, *jtype = K.ints.data() + K.o.jtype;
+  const int* jdof = Dn.ints.data() + Dn.o.jdof;
+  std::vector<int> dbody(nv, -1), dpar(nv, -1), last(nb, -1);   // last[i]: the last dof of body i or of its nearest ancestor with one
+  for (int i = 1; i < nb; i++) {
+    last[i] = last[par[i]];
+    for (int j = jadr[i]; j < jadr[i] + jnum[i]; j++)
+      for (int e = 0; e < (jtype[j] == SG_JNT_FREE ? 6 : 1); e++) {
+        const int dof = jdof[j] + e;
+        if (dbody[dof] >= 0) { T->err = "two joints share a dof"; return; }
+        if (last[i] >= dof) { T->err = "dofs must follow the order of the bodies and their joints"; return; }
+        dbody[dof] = i; dpar[dof] = last[i]; last[i] = dof;
+      }
+  }
+  for (int i = 0; i < nv; i++)
+    if (dbody[i] < 0) { T->err = "a dof without a joint"; return; }
+  std::vector<int> cstart(nb + 1, 0), child;
+  for (int i = 0; i < nb; i++) {
+    cstart[i] = (int)child.size();
+    for (int k = i + 1; k < nb; k++)
+      if (par[k] == i) child.push_back(k);
+  }
+  cstart[nb] = (int)child.size();
+  SgSmoothOff& o = T->o;
+  o.nu = (int)nu; o.nspatial = 0;
+  for (int t = 0; t < nt; t++) o.nspatial += Dn.ints[Dn.o.wtype + Dn.ints[Dn.o.tadr + t]] == SG_WRAP_SITE;
+  std::vector<double>& D = T->dbl;
+  auto putd = [&](const double* p, size_t n) { int at = (int)D.size(); D.insert(D.end(), p, p + n); return at; };
+  o.ddamp = putd(ddamp, nv); o.tdamp = putd(tdamp, nt); o.again = putd(again, nu); o.abias = putd(abias, 3 * nu); o.agear = putd(agear, nu);
+  if (D.empty()) D.push_back(0.0);
+  std::vector<int>& I = T->ints;
+  auto puti = [&](const int* p, size_t n) { int at = (int)I.size(); I.insert(I.end(), p, p + n); return at; };
+  o.dbody = puti(dbody.data(), nv); o.dpar = puti(dpar.data(), nv); o.atrn = puti(atrn, nu); o.cstart = puti(cstart.data(), nb + 1);
+  o.child = puti(child.data(), child.size());
   T->ok = true;
 }
 
@@ -622,6 +679,65 @@ int sg_get_tendons(sg_batch* b, const int32_t* env_ids, int n_ids, double* lengt
 }
 int sg_get_energy(sg_batch* b, const int32_t* env_ids, int n_ids, double* energy, void* stream) {
   return dyn("sg_get_energy", b, env_ids, n_ids, nullptr, nullptr, nullptr, nullptr, nullptr, energy, stream);
+}
+
+// ---- mass matrix, joint forces and inverse dynamics: one kernel (sg_smooth_kernel), whichever outputs the entry point fn passes ----
+static int smooth(const char* fn, sg_batch* b, const int32_t* env_ids, int n_ids, double* M, double* bias, double* passive, double* actuator,
+                  const double* qacc, bool need_qacc, double* inverse, void* stream) {
+  // (argument checks first, in an order that lets each be reached without a device)
+  if (n_ids <= 0) return fail(SG_ERR_INVALID, std::string(fn) + ": n_ids must be positive");
+  if (!b) return fail(SG_ERR_INVALID, std::string(fn) + ": null batch");
+  if (need_qacc && !qacc) return fail(SG_ERR_INVALID, std::string(fn) + ": null qacc");
+  const SgKinHost& K = b->m->kin;
+  const SgDynHost& Dn = b->m->dyn;
+  const SgSmoothHost& Sm = b->m->smooth;
+  const SgPlanHeader& H = b->m->plan.h;
+  if (K.ok && !Sm.ok) return fail(SG_ERR_MODEL, std::string(fn) + ": " + Sm.err);
+  if (K.ok && (Dn.o.nv != H.nv || K.o.nq != H.nq || K.o.njnt != H.njnt || Dn.o.ntendon != H.ntendon || Sm.o.nu != H.nu))   // (the strides of qpos / qvel / act and the masks' lengths)
+    return fail(SG_ERR_MODEL, std::string(fn) + ": the blob's joint, dof, tendon or actuator counts differ from the plan's");
+  Readout r{b, fn, (hipStream_t)stream};
+  if (int rc = r.prepare(env_ids, n_ids)) return rc;
+  if (!M && !bias && !passive && !actuator && !inverse) return SG_OK;
+  if (!b->dyn_d) {   // (on the side, as the pose tables)
+    SgArena A;
+    double* dd = nullptr;
+    int* di = nullptr;
+    if (!(A.upload(&dd, Dn.dbl) && A.upload(&di, Dn.ints))) return devmem_fail(A.nomem, std::string(fn) + " (dynamics tables)");
+    A.give_to(b->mem);
+    b->dyn_d = dd; b->dyn_i = di;
+  }
+  if (!b->smooth_d) {
+    SgArena A;
+    double* sd = nullptr;
+    int* si = nullptr;
+    if (!(A.upload(&sd, Sm.dbl) && A.upload(&si, Sm.ints))) return devmem_fail(A.nomem, std::string(fn) + " (smooth tables)");
+    A.give_to(b->mem);
+    b->smooth_d = sd; b->smooth_i = si;
+  }
+  // nbody <= SGS_MAXBODY, nv <= SGS_MAXDOF, ntendon <= SGS_MAXTENDON (sgs_build): with the kernel's static LDS within SGS_LDS_MAX
+  const size_t lds = sizeof(double) * ((size_t)SGS_REC * K.o.nbody + (size_t)SGS_DOF * Dn.o.nv + 2 * (size_t)Dn.o.ntendon);
+  if (!b->smooth_attr_set) {   // per device, as the contact read-out's attribute: above 64 KB the launch's dynamic LDS must be granted
+    HIPCHK(hipFuncSetAttribute((const void*)sg_smooth_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SGS_LDS_MAX - SGS_STATIC_LDS));
+    b->smooth_attr_set = true;
+  }
+  SgSmoothArgs a;
+  a.D = b->kin_d; a.I = b->kin_i; a.o = K.o; a.DD = b->dyn_d; a.DI = b->dyn_i; a.d = Dn.o; a.SD = b->smooth_d; a.SI = b->smooth_i; a.s = Sm.o;
+  a.qpos = b->qpos; a.qvel = b->qvel; a.act = b->act; a.kenv = b->kenv; a.kmask_jnt = b->kmask_jnt; a.kmask_ten = b->kmask_ten;
+  a.env_ids = r.dids; a.n_ids = n_ids;
+  a.M = M; a.bias = bias; a.passive = passive; a.actuator = actuator; a.qacc = qacc; a.inverse = inverse;
+  hipLaunchKernelGGL(sg_smooth_kernel, dim3(n_ids), dim3(64), lds, r.s, a);
+  HIPCHK(hipGetLastError());
+  return SG_OK;
+}
+
+int sg_get_mass_matrix(sg_batch* b, const int32_t* env_ids, int n_ids, double* M, void* stream) {
+  return smooth("sg_get_mass_matrix", b, env_ids, n_ids, M, nullptr, nullptr, nullptr, nullptr, false, nullptr, stream);
+}
+int sg_get_joint_forces(sg_batch* b, const int32_t* env_ids, int n_ids, double* bias, double* passive, double* actuator, void* stream) {
+  return smooth("sg_get_joint_forces", b, env_ids, n_ids, nullptr, bias, passive, actuator, nullptr, false, nullptr, stream);
+}
+int sg_inverse_dynamics(sg_batch* b, const int32_t* env_ids, int n_ids, const double* qacc, double* qfrc_inverse, void* stream) {
+  return smooth("sg_inverse_dynamics", b, env_ids, n_ids, nullptr, nullptr, nullptr, nullptr, qacc, true, qfrc_inverse, stream);
 }
 
 }  // extern "C"

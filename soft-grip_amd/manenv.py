@@ -418,6 +418,20 @@ class ManEnv(Env):
         (at each env's own stiffness) and kinetic energy; data.energy is (the sum of the first three, the fourth)"""
         return self.env.energy(env_ids=env_ids)
 
+    def get_mass_matrix(self, env_ids=None):
+        """[k, nv, nv] device tensor of the listed envs (None: all) at the current state: the dense joint-space mass matrix
+        (mj_fullM(data.qM)), symmetric to the bit.  nv * nv * 8 bytes per env: list fewer envs per call where memory is short"""
+        return self.env.mass_matrix(env_ids=env_ids)
+
+    def get_joint_forces(self, env_ids=None):
+        """the smooth joint-space forces of the listed envs (None: all) at the current state (data.qfrc_bias, qfrc_passive,
+        qfrc_actuator): NativeBatch.joint_forces' dict of device tensors bias, passive, actuator [k, nv]"""
+        return self.env.joint_forces(env_ids=env_ids)
+
+    def inverse_dynamics(self, qacc, env_ids=None):
+        """mj_inverse at the current state: qacc [k, nv] (device, float64) -> qfrc_inverse [k, nv] = M qacc + bias - passive"""
+        return self.env.inverse_dynamics(qacc, env_ids=env_ids)
+
     def raycast(self, origin, direction, body=None, exclude=None, env_ids=None, cat_mask=native.SG_RAY_ALL, max_dist=0.0, normals=False, skin=False):
         """ray queries on the current state (mj_ray; sg_ray): NativeBatch.raycast's arguments and dict of device tensors (dist [k, R],
         geom [k, R], normal [k, R, 3] with normals=True).  skin=True (SG_RAY_SKIN): the soft object is seen as its skin (the scene's

@@ -25,6 +25,7 @@ SYMBOLS = [
     "sg_get_poses", "sg_model_nbody", "sg_model_ngeom", "sg_model_default_camera", "sg_render",
     "sg_get_contacts", "sg_model_ncollision_pairs", "sg_model_set_skin", "sg_model_skin", "sg_render_ex", "sg_ray",
     "sg_lstm_forward", "sg_lstm_backward", "sg_get_velocities", "sg_get_tendons", "sg_get_energy",
+    "sg_get_mass_matrix", "sg_get_joint_forces", "sg_inverse_dynamics",
 ]
 SG_RENDER_SKIN = 1
 # sg_ray: category bits of cat_mask (ground plane, static, moving finger box, shell element, centre sphere) and flags
@@ -102,6 +103,9 @@ def load_library(path):
     L.sg_get_velocities.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, dp, dp, vp]
     L.sg_get_tendons.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, dp, vp]
     L.sg_get_energy.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, vp]
+    L.sg_get_mass_matrix.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, vp]
+    L.sg_get_joint_forces.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, dp, dp, vp]
+    L.sg_inverse_dynamics.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, dp, vp]
     L.sg_lstm_forward.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int, vp]
     L.sg_lstm_backward.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, vp]
     L.sg_profile_enable.argtypes = [vp, C.c_int]
@@ -317,6 +321,42 @@ class NativeBatch:
             out = t.empty(k, 4, dtype=t.float64, device=self.device)
         assert out.is_cuda and out.dtype == t.float64 and out.is_contiguous() and out.shape == (k, 4)
         self._check(self.L.sg_get_energy(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, _ptr(out), self._stream()))
+        return out
+
+    def mass_matrix(self, env_ids=None):
+        """the joint-space mass matrix of the listed envs (None: all) on the current state (sg_get_mass_matrix; mj_fullM(data.qM)):
+        float64 device tensor [k, nv, nv], dense and symmetric to the bit.  nv * nv * 8 bytes per env: list fewer envs per call
+        where memory is short."""
+        t = self.torch
+        ids, k = self._ids(env_ids)
+        nv = self.nmodel.nv
+        out = t.empty(k, nv, nv, dtype=t.float64, device=self.device)
+        self._check(self.L.sg_get_mass_matrix(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, _ptr(out), self._stream()))
+        return out
+
+    def joint_forces(self, env_ids=None):
+        """the smooth joint-space forces of the listed envs (None: all) on the current state (sg_get_joint_forces): dict of float64
+        device tensors [k, nv]: bias (data.qfrc_bias: Coriolis, centrifugal and gravity terms, on the left-hand side), passive
+        (data.qfrc_passive: springs at the stiffness the env's next step uses, dampers, the tendon damper also where the model
+        integrates it implicitly), actuator (data.qfrc_actuator at the current activation)."""
+        t = self.torch
+        ids, k = self._ids(env_ids)
+        out = {name: t.empty(k, self.nmodel.nv, dtype=t.float64, device=self.device) for name in ("bias", "passive", "actuator")}
+        self._check(self.L.sg_get_joint_forces(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, _ptr(out["bias"]),
+                                               _ptr(out["passive"]), _ptr(out["actuator"]), self._stream()))
+        return out
+
+    def inverse_dynamics(self, qacc, env_ids=None):
+        """mj_inverse of the listed envs (None: all) on the current state (sg_inverse_dynamics): qacc, a float64 device tensor [k, nv]
+        (row i: the i-th listed env's acceleration) -> qfrc_inverse [k, nv] = M qacc + bias - passive, one Newton-Euler pass.
+        ``inverse_dynamics(qacc) - joint_forces()["actuator"]`` is the generalised force the constraints must have applied."""
+        t = self.torch
+        ids, k = self._ids(env_ids)
+        nv = self.nmodel.nv
+        assert qacc.is_cuda and qacc.dtype == t.float64 and qacc.is_contiguous() and qacc.shape == (k, nv)
+        out = t.empty(k, nv, dtype=t.float64, device=self.device)
+        self._check(self.L.sg_inverse_dynamics(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, _ptr(qacc), _ptr(out),
+                                               self._stream()))
         return out
 
     def contacts(self, env_ids=None, max_contacts=256):
