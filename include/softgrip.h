@@ -339,6 +339,55 @@ int sg_get_mass_matrix(sg_batch* b, const int32_t* env_ids, int n_ids, double* M
 int sg_get_joint_forces(sg_batch* b, const int32_t* env_ids, int n_ids, double* bias, double* passive, double* actuator, void* stream);
 int sg_inverse_dynamics(sg_batch* b, const int32_t* env_ids, int n_ids, const double* qacc, double* qfrc_inverse, void* stream);
 
+/* ---- point motion and point Jacobians: replaces mj_jac / mj_jacBody / mj_jacSite, reading data.cacc or calling mj_objectVelocity /
+ * mj_objectAcceleration, and declaring a gyro or an accelerometer at a site in the MJCF: both can be asked of ANY body-fixed point, at
+ * run time, without touching the model.
+ * A POINT (probe) is pt_body[p] in [0, nbody) -- body 0, the world, is allowed --, pt_pos[p][3], a position in that body's frame, and
+ * optionally pt_quat[p][4], the probe's frame relative to the body's (a NULL array: identity; the call normalises each quaternion).  A
+ * point given a site's site_bodyid, site_pos and site_quat IS that site: sg_model_nsite / sg_model_sites hand the model's sites out in
+ * that form (host arrays of nsite, nsite x 3 and nsite x 4 entries, any may be NULL).  The point arrays are HOST pointers, as sg_ray's
+ * ray_body: they are read before the call returns and reach the device by a copy on `stream`.
+ * State: env_ids as in sg_get_poses (HOST, NULL = all).  qpos [n_ids][nq], qvel [n_ids][nv] and qacc [n_ids][nv] are DEVICE pointers,
+ * row k belonging to the k-th listed env; a NULL qpos or qvel means the batch's CURRENT qpos or qvel, a NULL qacc means zero.  The
+ * calls read the batch, change nothing in it and do not synchronise the host; free quaternions are normalised on the way in.
+ * Outputs: device pointers, any may be NULL, world axes unless stated.
+ *   pos   [n_ids][n_pts][3]  the point; mat [n_ids][n_pts][9] the probe's frame, row-major: R(xquat[body]) R(pt_quat).
+ *   vel   [n_ids][n_pts][6]  the body's angular velocity, then the linear velocity of the material point: lin + ang x (p - xpos) in
+ *                            sg_get_velocities' terms.
+ *   acc   [n_ids][n_pts][6]  the body's angular acceleration, then the acceleration of the material point; kinematic, WITHOUT
+ *                            gravity: J qacc + Jdot qvel.
+ *   gyro  [n_ids][n_pts][3]  mat' ang; accel [n_ids][n_pts][3] = mat' (a_point - gravity): what MuJoCo's gyro and accelerometer at a
+ *                            site of that pose read.  A probe on the world reads minus gravity.
+ *   jacp, jacr [n_ids][n_pts][3][nv]  mj_jac's layout: column d is dof d's effect on the point under sg_get_velocities' dof
+ *                            conventions -- a slide dof gives (u, 0), a hinge dof (u x (p - anchor), u), a free joint's linear dofs act
+ *                            along the WORLD axes, its angular dofs about the BODY's own axes through xpos.  EVERY entry is written,
+ *                            the zeros included (a dof whose body is neither the point's body nor one of its ancestors), so the
+ *                            buffers need not be cleared.  vel = (jacr qvel, jacp qvel).
+ * No atomics: two calls give the same bits; an env's bits depend neither on the env list, nor on its order, nor on which outputs are
+ * NULL; a point's bits depend neither on n_pts nor on its place in the list.  An env whose qpos, qvel or qacc row -- those the call
+ * uses: the given one, or the batch's current one where none is given; sg_get_jacobians uses qpos alone -- holds a NaN or inf gets NaN
+ * in every output of the call (every entry of its Jacobians) and disturbs no other env.
+ * SG_ERR_INVALID (checked before anything touches the device; nothing is written): NULL batch, n_ids <= 0, an env id out of range,
+ * n_pts <= 0, NULL pt_body or pt_pos, a body id outside [0, nbody), a non-finite pt_pos or pt_quat, a pt_quat of zero length.
+ * SG_ERR_MODEL, with the limit named in the message: a model the velocity read-out cannot run -- its tables are walked here, so its
+ * 627 bodies are the body limit a caller meets -- and a model of more than 1024 dofs.  (The kernel's own LDS block, 19 doubles a body,
+ * 7 doubles and an int a dof within the 160 KB a workgroup can have, would hold 672 bodies: a check that stands behind the first and
+ * is reached only if that one is ever raised.)
+ *
+ * THE EXACT VIRTUAL IMU.  After sg_step, sensordata belongs to the LAST substep's forward pass; the batch's qpos and qvel are one
+ * integration past that pass, and qacc_warmstart is that pass's qacc.  So, for an env step of n substeps:
+ *   sg_step(n - 1); sg_get_state(qpos, qvel) into buffers of the caller; sg_step(1);
+ *   sg_get_state(qacc_warmstart); sg_get_point_motion(qpos = saved, qvel = saved, qacc = qacc_warmstart)
+ * gives gyro / accel of the same forward pass as that step's sensordata -- at the model's own sites they equal it -- at any point.
+ * No sg_set_state is involved and the batch is never written. */
+int sg_get_point_motion(sg_batch* b, const int32_t* env_ids, int n_ids, int n_pts, const int32_t* pt_body, const double* pt_pos, const double* pt_quat,
+                        const double* qpos, const double* qvel, const double* qacc, double* pos, double* mat, double* vel, double* acc, double* gyro,
+                        double* accel, void* stream);
+int sg_get_jacobians(sg_batch* b, const int32_t* env_ids, int n_ids, int n_pts, const int32_t* pt_body, const double* pt_pos, const double* qpos, double* jacp,
+                     double* jacr, void* stream);
+int sg_model_nsite(const sg_model* m);
+int sg_model_sites(const sg_model* m, int32_t* body, double* pos, double* quat);   /* host pointers, any may be NULL */
+
 /* The recurrence of one direction of one fp64 LSTM layer with H = 128 hidden units (csrc/sg_lstm.hip), for the Conv-LSTM and
  * Conv-BiLSTM regressors (soft-grip_amd/lstm.py).  Keras' conventions: gate order i, f, g (the candidate), o along the 4H axis, sigmoid
  * for i, f and o, tanh for g and for the cell, row-major kernels.  The caller keeps what is regular -- the input projection

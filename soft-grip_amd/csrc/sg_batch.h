@@ -9,6 +9,7 @@
 #include "sg_readout.h"
 #include "sg_dyn.h"
 #include "sg_smooth.h"
+#include "sg_point.h"
 #include "sg_skin.h"
 #include "sg_rows_host.h"   // (sg_work.h, sg_plan.h)
 #include "sg_devmem.h"   // SgArena, SgScratch: the owners of every device buffer below (after the HIP runtime's declarations)
@@ -36,6 +37,7 @@ struct sg_model {
   SgConHost con;    // candidate pairs, margins and bounding radii of sg_get_contacts
   SgDynHost dyn;    // masses, springs, sites and tendons of sg_get_velocities / sg_get_tendons / sg_get_energy
   SgSmoothHost smooth;   // dampers, actuators, child lists and parent dofs of sg_get_mass_matrix / sg_get_joint_forces / sg_inverse_dynamics
+  SgPointHost point;     // the dof-parent chain's entries and the sites of sg_get_point_motion / sg_get_jacobians / sg_model_sites
   SgSkinHost skin;  // the composite's skin (sg_skin.h; nvert == 0: none): sg_model_set_skin, drawn by sg_render_ex
 };
 
@@ -122,6 +124,12 @@ struct sg_batch {
   double* smooth_d = nullptr;
   int* smooth_i = nullptr;
   bool smooth_attr_set = false;
+  // point motion and Jacobians: the point table, and the last call's points (body ids; positions [n_pts][3] then quaternions [n_pts][4])
+  int* point_i = nullptr;
+  double* point_zero = nullptr;   // [nv] zeros
+  bool point_attr_set = false;
+  SgScratch<int> pt_ids;
+  SgScratch<double> pt_d;
   ~sg_batch() {   // (on the batch's device: sg_batch_destroy.  The arenas and scratch buffers free themselves)
     for (auto& e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (auto& e : ev_pgs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }

@@ -1,7 +1,7 @@
 // sg_readout.hip -- the read-out half of the C ABI (include/softgrip.h): sg_get_poses, sg_render / sg_render_ex and the skin,
 // sg_get_contacts, sg_ray, sg_get_velocities / sg_get_tendons / sg_get_energy, sg_get_mass_matrix / sg_get_joint_forces /
-// sg_inverse_dynamics, with the kernels they launch (the *_kernel*.h files, whose
-// device assembly is sg_readout.device.s) and the host builders of their per-model tables (sg_readout.h, sg_dyn.h, sg_smooth.h).  None of them writes the state: every pipeline is served.  No CPU fallback.
+// sg_inverse_dynamics, sg_get_point_motion / sg_get_jacobians, with the kernels they launch (the *_kernel*.h files, whose
+// device assembly is sg_readout.device.s) and the host builders of their per-model tables (sg_readout.h, sg_dyn.h, sg_smooth.h, sg_point.h).  None of them writes the state: every pipeline is served.  No CPU fallback.
 #include <algorithm>
 #include <cstring>
 #include <type_traits>
@@ -14,6 +14,7 @@
 #include "sg_ray_skin_kernels.h"
 #include "sg_dyn_kernel.h"
 #include "sg_smooth_kernel.h"
+#include "sg_point_kernel.h"
 
 // ---- the builders sg_model_create calls (sg_readout.h) ----
 // an array of the blob as `var`, its length in c (want >= 0: that many elements), or the builder ends with T->err set
@@ -288,6 +289,40 @@ void sgs_build(const void* blob, size_t nbytes, const SgKinHost& K, const SgDynH
   auto puti = [&](const int* p, size_t n) { int at = (int)I.size(); I.insert(I.end(), p, p + n); return at; };
   o.dbody = puti(dbody.data(), nv); o.dpar = puti(dpar.data(), nv); o.atrn = puti(atrn, nu); o.cstart = puti(cstart.data(), nb + 1);
   o.child = puti(child.data(), child.size());
+  T->ok = true;
+}
+
+// the point table (sg_point.h): per body where it enters the dof-parent chain, per dof its parent dof; and the model's sites for
+// sg_model_sites.  Its own walk over the bodies, as the smooth table's limits (bodies, tendons) are not the point read-outs'
+void sgp_build(const void* blob, size_t nbytes, const SgKinHost& K, const SgDynHost& Dn, SgPointHost* T) {
+  if (!K.ok) { T->err = K.err; return; }
+  if (!Dn.ok) { T->err = Dn.err; return; }
+  const long long nb = K.o.nbody, nv = Dn.o.nv, ns = Dn.o.nsite;
+  if (nb > SGP_MAXBODY) { T->err = "more than " + std::to_string(SGP_MAXBODY) + " bodies"; return; }
+  if (nv > SGP_MAXDOF) { T->err = "more than " + std::to_string(SGP_MAXDOF) + " dofs"; return; }
+  long long c = 0;
+  SG_FIELD(T, squat, "site_quat", SG_DT_F64, 4 * ns);
+  const int *par = K.ints.data() + K.o.bpar, *jadr = K.ints.data() + K.o.bjadr, *jnum = K.ints.data() + K.o.bjnum, *jtype = K.ints.data() + K.o.jtype;
+  const int* jdof = Dn.ints.data() + Dn.o.jdof;
+  std::vector<int> bdof(nb, -1), dpar(nv, -2);
+  for (int i = 1; i < nb; i++) {
+    bdof[i] = bdof[par[i]];
+    for (int j = jadr[i]; j < jadr[i] + jnum[i]; j++)
+      for (int e = 0; e < (jtype[j] == SG_JNT_FREE ? 6 : 1); e++) {
+        const int dof = jdof[j] + e;
+        if (dpar[dof] != -2) { T->err = "two joints share a dof"; return; }
+        if (bdof[i] >= dof) { T->err = "dofs must follow the order of the bodies and their joints"; return; }
+        dpar[dof] = bdof[i]; bdof[i] = dof;
+      }
+  }
+  for (int i = 0; i < nv; i++)
+    if (dpar[i] == -2) { T->err = "a dof without a joint"; return; }
+  std::vector<int>& I = T->ints;
+  auto puti = [&](const int* p, size_t n) { int at = (int)I.size(); I.insert(I.end(), p, p + n); return at; };
+  T->o.bdof = puti(bdof.data(), nb); T->o.dpar = puti(dpar.data(), nv);
+  T->site_body.assign(Dn.ints.begin() + Dn.o.sbody, Dn.ints.begin() + Dn.o.sbody + ns);
+  T->site_pos.assign(Dn.dbl.begin() + Dn.o.spos, Dn.dbl.begin() + Dn.o.spos + 3 * ns);
+  T->site_quat.assign(squat, squat + 4 * ns);
   T->ok = true;
 }
 
@@ -738,6 +773,104 @@ int sg_get_joint_forces(sg_batch* b, const int32_t* env_ids, int n_ids, double* 
 }
 int sg_inverse_dynamics(sg_batch* b, const int32_t* env_ids, int n_ids, const double* qacc, double* qfrc_inverse, void* stream) {
   return smooth("sg_inverse_dynamics", b, env_ids, n_ids, nullptr, nullptr, nullptr, nullptr, qacc, true, qfrc_inverse, stream);
+}
+
+// ---- point motion and point Jacobians: one kernel (sg_point_kernel), whichever outputs the entry point fn passes ----
+static int point(const char* fn, sg_batch* b, const int32_t* env_ids, int n_ids, int n_pts, const int32_t* pt_body, const double* pt_pos, const double* pt_quat,
+                 const double* qpos, const double* qvel, const double* qacc, double* pos, double* mat, double* vel, double* acc, double* gyro, double* accel,
+                 double* jacp, double* jacr, bool use_qvel, void* stream) {
+  // (argument checks first, in an order that lets each be reached without a device)
+  const std::string f = std::string(fn) + ": ";
+  if (n_ids <= 0) return fail(SG_ERR_INVALID, f + "n_ids must be positive");
+  if (n_pts <= 0) return fail(SG_ERR_INVALID, f + "n_pts must be positive");
+  if (!b) return fail(SG_ERR_INVALID, f + "null batch");
+  if (!pt_body || !pt_pos) return fail(SG_ERR_INVALID, f + "null pt_body or pt_pos");
+  const SgKinHost& K = b->m->kin;
+  const SgDynHost& Dn = b->m->dyn;
+  const SgPointHost& Pt = b->m->point;
+  const SgPlanHeader& H = b->m->plan.h;
+  for (int p = 0; p < n_pts; p++) {
+    if (K.ok && (pt_body[p] < 0 || pt_body[p] >= K.o.nbody))
+      return fail(SG_ERR_INVALID, f + "body id " + std::to_string(pt_body[p]) + " of point " + std::to_string(p) + " outside [0, " + std::to_string(K.o.nbody) + ")");
+    for (int c = 0; c < 3; c++)
+      if (!std::isfinite(pt_pos[3 * p + c])) return fail(SG_ERR_INVALID, f + "pt_pos of point " + std::to_string(p) + " is not finite");
+    if (pt_quat) {
+      double n2 = 0.0;
+      for (int c = 0; c < 4; c++) {
+        if (!std::isfinite(pt_quat[4 * p + c])) return fail(SG_ERR_INVALID, f + "pt_quat of point " + std::to_string(p) + " is not finite");
+        n2 += pt_quat[4 * p + c] * pt_quat[4 * p + c];
+      }
+      if (!(n2 > 0.0) || !std::isfinite(n2)) return fail(SG_ERR_INVALID, f + "pt_quat of point " + std::to_string(p) + " has zero length (or overflows)");
+    }
+  }
+  if (K.ok && !Pt.ok) return fail(SG_ERR_MODEL, f + Pt.err);
+  if (K.ok && (Dn.o.nv != H.nv || K.o.nq != H.nq))   // (the strides of qpos / qvel)
+    return fail(SG_ERR_MODEL, f + "the blob's position or dof counts differ from the plan's");
+  if ((long long)n_ids * n_pts > 0x7fffffffll) return fail(SG_ERR_INVALID, f + "too many envs x points for one launch");
+  Readout r{b, fn, (hipStream_t)stream};
+  if (int rc = r.prepare(env_ids, n_ids)) return rc;
+  if (!pos && !mat && !vel && !acc && !gyro && !accel && !jacp && !jacr) return SG_OK;
+  if (!b->dyn_d) {   // (on the side, as the pose tables)
+    SgArena A;
+    double* dd = nullptr;
+    int* di = nullptr;
+    if (!(A.upload(&dd, Dn.dbl) && A.upload(&di, Dn.ints))) return devmem_fail(A.nomem, std::string(fn) + " (dynamics tables)");
+    A.give_to(b->mem);
+    b->dyn_d = dd; b->dyn_i = di;
+  }
+  if (!b->point_i) {   // the point table, and a row of nv zeros: the qvel the Jacobian-only call walks at
+    SgArena A;
+    int* pi = nullptr;
+    double* z = nullptr;
+    if (!(A.upload(&pi, Pt.ints) && A.upload(&z, std::vector<double>(Dn.o.nv > 0 ? Dn.o.nv : 1, 0.0)))) return devmem_fail(A.nomem, std::string(fn) + " (point table)");
+    A.give_to(b->mem);
+    b->point_i = pi; b->point_zero = z;
+  }
+  // nbody <= SGP_MAXBODY, nv <= SGP_MAXDOF (sgp_build): with the kernel's static LDS within SGP_LDS_MAX
+  const size_t lds = sizeof(double) * ((size_t)SGP_REC * K.o.nbody + (size_t)SGP_DOF * Dn.o.nv) + sizeof(int) * (size_t)Dn.o.nv;
+  if (!b->point_attr_set) {   // per device, as the smooth read-out's attribute: above 64 KB the launch's dynamic LDS must be granted
+    HIPCHK(hipFuncSetAttribute((const void*)sg_point_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SGP_LDS_MAX - SGP_STATIC_LDS));
+    b->point_attr_set = true;
+  }
+  // the points: host arrays, read here and copied on the stream
+  if (int rc = r.reserve(b->pt_ids, (size_t)n_pts, "point body ids")) return rc;
+  if (int rc = r.reserve(b->pt_d, 7 * (size_t)n_pts, "points")) return rc;
+  HIPCHK(hipMemcpyAsync(b->pt_ids.p, pt_body, sizeof(int) * n_pts, hipMemcpyHostToDevice, r.s));
+  HIPCHK(hipMemcpyAsync(b->pt_d.p, pt_pos, sizeof(double) * 3 * n_pts, hipMemcpyHostToDevice, r.s));
+  if (pt_quat) HIPCHK(hipMemcpyAsync(b->pt_d.p + 3 * (size_t)n_pts, pt_quat, sizeof(double) * 4 * n_pts, hipMemcpyHostToDevice, r.s));
+  SgPointArgs a;
+  a.D = b->kin_d; a.I = b->kin_i; a.o = K.o; a.DD = b->dyn_d; a.DI = b->dyn_i; a.d = Dn.o; a.PI = b->point_i; a.p = Pt.o;
+  a.qpos = qpos ? qpos : b->qpos; a.qvel = !use_qvel ? b->point_zero : qvel ? qvel : b->qvel; a.qacc = qacc;
+  a.given = (qpos ? 1 : 0) | (use_qvel ? (qvel ? 2 : 0) : 4);
+  a.env_ids = r.dids; a.n_ids = n_ids; a.n_pts = n_pts;
+  a.pt_body = b->pt_ids.p; a.pt_pos = b->pt_d.p; a.pt_quat = pt_quat ? b->pt_d.p + 3 * (size_t)n_pts : nullptr;
+  a.pos = pos; a.mat = mat; a.vel = vel; a.acc = acc; a.gyro = gyro; a.accel = accel; a.jacp = jacp; a.jacr = jacr;
+  hipLaunchKernelGGL(sg_point_kernel, dim3(n_ids), dim3(64), lds, r.s, a);
+  HIPCHK(hipGetLastError());
+  return SG_OK;
+}
+
+int sg_get_point_motion(sg_batch* b, const int32_t* env_ids, int n_ids, int n_pts, const int32_t* pt_body, const double* pt_pos, const double* pt_quat,
+                        const double* qpos, const double* qvel, const double* qacc, double* pos, double* mat, double* vel, double* acc, double* gyro,
+                        double* accel, void* stream) {
+  return point("sg_get_point_motion", b, env_ids, n_ids, n_pts, pt_body, pt_pos, pt_quat, qpos, qvel, qacc, pos, mat, vel, acc, gyro, accel, nullptr, nullptr, true, stream);
+}
+int sg_get_jacobians(sg_batch* b, const int32_t* env_ids, int n_ids, int n_pts, const int32_t* pt_body, const double* pt_pos, const double* qpos, double* jacp,
+                     double* jacr, void* stream) {
+  return point("sg_get_jacobians", b, env_ids, n_ids, n_pts, pt_body, pt_pos, nullptr, qpos, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+               jacp, jacr, false, stream);
+}
+
+int sg_model_nsite(const sg_model* m) { return m ? (int)m->point.site_body.size() : 0; }
+// the model's sites as points of the two calls above (host arrays, any may be NULL)
+int sg_model_sites(const sg_model* m, int32_t* body, double* pos, double* quat) {
+  if (!m) return fail(SG_ERR_INVALID, "sg_model_sites: null model");
+  const SgPointHost& P = m->point;
+  if (!P.ok) return fail(SG_ERR_MODEL, "sg_model_sites: " + P.err);
+  if (body) std::copy(P.site_body.begin(), P.site_body.end(), body);
+  if (pos) std::copy(P.site_pos.begin(), P.site_pos.end(), pos);
+  if (quat) std::copy(P.site_quat.begin(), P.site_quat.end(), quat);
+  return SG_OK;
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@
 #define SGS_REC 29
 #define SGS_ACC 13   // a record's acceleration, then force, slots
 #define SGS_INR 19   // a record's inertia slots
-#define SGS_DOF 7
+#define SGS_DOF 7    // (sgs_body writes slots 0 .. 5 of a dof record and never slot 6: sg_point.h keeps its stamp there)
 // The kernel's LDS block: nbody records, nv dof records and two doubles per tendon beside its static LDS (SGS_STATIC_LDS bytes: the
 // block-wide __syncthreads_or; the kept assembly's figure, held by tests/test_smooth_host.py).  A gfx950 workgroup gets 160 KB when the
 // launch asks for it: 1024 dofs and 128 tendons leave room for 449 bodies.

@@ -432,6 +432,50 @@ class ManEnv(Env):
         """mj_inverse at the current state: qacc [k, nv] (device, float64) -> qfrc_inverse [k, nv] = M qacc + bias - passive"""
         return self.env.inverse_dynamics(qacc, env_ids=env_ids)
 
+    def get_point_motion(self, body, pos, quat=None, qpos=None, qvel=None, qacc=None, env_ids=None):
+        """pose, velocity, acceleration and gyro / accelerometer readings of body-fixed points (sg_get_point_motion):
+        NativeBatch.point_motion's arguments and dict of device tensors pos, mat, vel, acc, gyro, accel"""
+        return self.env.point_motion(body, pos, quat, qpos=qpos, qvel=qvel, qacc=qacc, env_ids=env_ids)
+
+    def get_jacobians(self, body, pos, qpos=None, env_ids=None):
+        """mj_jac of body-fixed points (sg_get_jacobians): NativeBatch.jacobians' dict of device tensors jacp, jacr [k, P, 3, nv]"""
+        return self.env.jacobians(body, pos, qpos=qpos, env_ids=env_ids)
+
+    def sensor_sites(self):
+        """the model's IMU sites -- every site a gyro or an accelerometer sits at, in ascending order -- as (body [S] int32, pos [S, 3],
+        quat [S, 4]), ready to pass as points: ``get_point_motion(*env.sensor_sites())``"""
+        body, pos, quat = self.nmodel.sites()
+        m = self.model
+        from .mjcf import SENS_ACCELEROMETER, SENS_GYRO
+        imu = sorted({int(m.sensor_objid[s]) for s in range(len(m.sensor_type)) if int(m.sensor_type[s]) in (SENS_ACCELEROMETER, SENS_GYRO)})
+        return body[imu], pos[imu], quat[imu]
+
+    def virtual_imu(self, body, pos, quat=None, n_substeps=-1):
+        """one env step with gyros and accelerometers at the given points for the SAME forward pass as the sensordata it returns (the
+        header's recipe): n - 1 substeps, qpos and qvel saved, one substep, then sg_get_point_motion at the saved state with that
+        substep's qacc (qacc_warmstart).  Returns (sensordata [n_envs, nsensordata], gyro [n_envs, P, 3], accel [n_envs, P, 3]),
+        ALWAYS as device tensors, also with n_envs == 1 (step() returns an ndarray and a bool there), and no contact flag.
+        While no env raises a flag the batch ends in the state step() leaves and the sensordata has step()'s bits.  For an env that
+        does raise one the two differ: the env is reset as in step(), but the sensordata returned is that of the step that FAILED,
+        which the virtual readings belong to -- step() returns the sensordata after the reset --, and an env flagged BADQPOS / BADQVEL /
+        BADQACC in the first n - 1 substeps is taken through the last substep by the second sg_step call, where one sg_step(n) would
+        have left it where it stopped; it is reset right after, so nothing of that substep survives"""
+        n = self.sim_step if n_substeps < 1 else n_substeps
+        if n > 1:
+            self.env.step(n - 1, sens=self._sens, flags=self._flags, touch=self._touch)
+            early = self._flags.clone()
+        st = self.env.get_state()
+        self.env.step(1, sens=self._sens, flags=self._flags, touch=self._touch)
+        if n > 1:
+            self._flags |= early
+        out = self.env.point_motion(body, pos, quat, qpos=st["qpos"], qvel=st["qvel"], qacc=self.env.get_state()["qacc_warmstart"], outputs=("gyro", "accel"))
+        sens = self._sens.clone()
+        bad = (self._flags != 0)
+        if bool(bad.any()):
+            self.n_capacity_resets += int(((self._flags & native.SG_FLAG_CONTACTFULL) != 0).sum())
+            self._reset_envs(bad)
+        return sens, out["gyro"], out["accel"]
+
     def raycast(self, origin, direction, body=None, exclude=None, env_ids=None, cat_mask=native.SG_RAY_ALL, max_dist=0.0, normals=False, skin=False):
         """ray queries on the current state (mj_ray; sg_ray): NativeBatch.raycast's arguments and dict of device tensors (dist [k, R],
         geom [k, R], normal [k, R, 3] with normals=True).  skin=True (SG_RAY_SKIN): the soft object is seen as its skin (the scene's

@@ -26,6 +26,7 @@ SYMBOLS = [
     "sg_get_contacts", "sg_model_ncollision_pairs", "sg_model_set_skin", "sg_model_skin", "sg_render_ex", "sg_ray",
     "sg_lstm_forward", "sg_lstm_backward", "sg_get_velocities", "sg_get_tendons", "sg_get_energy",
     "sg_get_mass_matrix", "sg_get_joint_forces", "sg_inverse_dynamics",
+    "sg_get_point_motion", "sg_get_jacobians", "sg_model_nsite", "sg_model_sites",
 ]
 SG_RENDER_SKIN = 1
 # sg_ray: category bits of cat_mask (ground plane, static, moving finger box, shell element, centre sphere) and flags
@@ -106,6 +107,10 @@ def load_library(path):
     L.sg_get_mass_matrix.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, vp]
     L.sg_get_joint_forces.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, dp, dp, vp]
     L.sg_inverse_dynamics.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, dp, vp]
+    L.sg_get_point_motion.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32), dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, vp]
+    L.sg_get_jacobians.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32), dp, dp, dp, dp, vp]
+    L.sg_model_nsite.argtypes = [vp]
+    L.sg_model_sites.argtypes = [vp, C.POINTER(C.c_int32), dp, dp]
     L.sg_lstm_forward.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int, vp]
     L.sg_lstm_backward.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, vp]
     L.sg_profile_enable.argtypes = [vp, C.c_int]
@@ -179,6 +184,14 @@ class NativeModel:
         check(self.L.sg_model_skin(self.ptr, None, None, vb.ctypes.data_as(C.c_void_p), vp.ctypes.data_as(C.c_void_p),
                                    fc.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.POINTER(C.c_float))), self.L)
         return dict(vert_body=vb, vert_pos=vp, face=fc, rgba=rgba)
+
+    def sites(self):
+        """the model's sites as points of NativeBatch.point_motion / jacobians (sg_model_sites): (body [nsite] int32, pos [nsite, 3],
+        quat [nsite, 4])"""
+        n = self.L.sg_model_nsite(self.ptr)
+        body, pos, quat = np.empty(n, np.int32), np.empty((n, 3), np.float64), np.empty((n, 4), np.float64)
+        check(self.L.sg_model_sites(self.ptr, body.ctypes.data_as(C.POINTER(C.c_int32)), pos.ctypes.data_as(C.c_void_p), quat.ctypes.data_as(C.c_void_p)), self.L)
+        return body, pos, quat
 
     def default_camera(self):
         """MuJoCo free camera [lookat xyz, distance, azimuth, elevation, fovy] that frames the scene at qpos0 (sg_model_default_camera)"""
@@ -357,6 +370,57 @@ class NativeBatch:
         out = t.empty(k, nv, dtype=t.float64, device=self.device)
         self._check(self.L.sg_inverse_dynamics(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, _ptr(qacc), _ptr(out),
                                                self._stream()))
+        return out
+
+    def _points(self, body, pos, quat):
+        """the host arrays of a point list: body [P] int32, pos [P, 3], quat [P, 4] or None"""
+        body = np.ascontiguousarray(body, dtype=np.int32).reshape(-1)
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        if len(pos) != len(body):
+            raise ValueError("points: pos needs one row per body id")
+        if quat is not None:
+            quat = np.ascontiguousarray(quat, dtype=np.float64).reshape(-1, 4)
+            if len(quat) != len(body):
+                raise ValueError("points: quat needs one row per body id")
+        return body, pos, quat
+
+    def _rows(self, x, k, n):
+        assert x is None or (x.is_cuda and x.dtype == self.torch.float64 and x.is_contiguous() and x.shape == (k, n))
+        return _ptr(x)
+
+    def point_motion(self, body, pos, quat=None, qpos=None, qvel=None, qacc=None, env_ids=None, outputs=None):
+        """pose, velocity and acceleration of body-fixed points and the gyro / accelerometer readings there (sg_get_point_motion).
+        Points: body [P] (0 is the world), pos [P, 3] in the body's frame, quat [P, 4] the probe's frame in the body's (None:
+        identity; normalised by the call) -- host arrays; a site's site_bodyid, site_pos, site_quat is that site.  qpos [k, nq], qvel
+        [k, nv], qacc [k, nv]: float64 device tensors, row i the i-th listed env's (None: the batch's current qpos / qvel, qacc zero).
+        Returns a dict of float64 device tensors, world axes: pos [k, P, 3], mat [k, P, 3, 3] (the probe's frame), vel [k, P, 6]
+        (angular, then linear of the material point), acc [k, P, 6] (kinematic, without gravity), gyro [k, P, 3] = mat' ang, accel
+        [k, P, 3] = mat' (a - gravity).  outputs: the names wanted (None: all)."""
+        t, m = self.torch, self.nmodel
+        ids, k = self._ids(env_ids)
+        body, pos, quat = self._points(body, pos, quat)
+        P = len(body)
+        shapes = dict(pos=(3,), mat=(3, 3), vel=(6,), acc=(6,), gyro=(3,), accel=(3,))
+        out = {n: t.empty((k, P) + shapes[n], dtype=t.float64, device=self.device) for n in (shapes if outputs is None else outputs)}
+        vp = C.c_void_p
+        self._check(self.L.sg_get_point_motion(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, P,
+                                               body.ctypes.data_as(C.POINTER(C.c_int32)), pos.ctypes.data_as(vp), None if quat is None else quat.ctypes.data_as(vp),
+                                               self._rows(qpos, k, m.nq), self._rows(qvel, k, m.nv), self._rows(qacc, k, m.nv),
+                                               *[_ptr(out.get(n)) for n in shapes], self._stream()))
+        return out
+
+    def jacobians(self, body, pos, qpos=None, env_ids=None):
+        """the Jacobians of body-fixed points (sg_get_jacobians; mj_jac): points as in point_motion, qpos [k, nq] (None: the batch's
+        current one) -> dict of float64 device tensors jacp, jacr [k, P, 3, nv], every entry written.  Column d is dof d's effect
+        under velocities()' dof conventions, so ``jacp @ qvel`` is the point's linear and ``jacr @ qvel`` its angular velocity."""
+        t, m = self.torch, self.nmodel
+        ids, k = self._ids(env_ids)
+        body, pos, _ = self._points(body, pos, None)
+        P = len(body)
+        out = {n: t.empty(k, P, 3, m.nv, dtype=t.float64, device=self.device) for n in ("jacp", "jacr")}
+        self._check(self.L.sg_get_jacobians(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, P,
+                                            body.ctypes.data_as(C.POINTER(C.c_int32)), pos.ctypes.data_as(C.c_void_p), self._rows(qpos, k, m.nq),
+                                            _ptr(out["jacp"]), _ptr(out["jacr"]), self._stream()))
         return out
 
     def contacts(self, env_ids=None, max_contacts=256):
