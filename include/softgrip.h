@@ -388,6 +388,45 @@ int sg_get_jacobians(sg_batch* b, const int32_t* env_ids, int n_ids, int n_pts, 
 int sg_model_nsite(const sg_model* m);
 int sg_model_sites(const sg_model* m, int32_t* body, double* pos, double* quat);   /* host pointers, any may be NULL */
 
+/* ---- mass-matrix solves, smooth forward dynamics and point inertias: replaces mj_solveM, reading data.qacc_smooth / data.qfrc_smooth
+ * after mj_fwdAcceleration, and forming J M^-1 J' on the host from a downloaded M.  Everything here starts with the inverse of M, the
+ * matrix sg_get_mass_matrix documents (same dof conventions, armature included); M itself never leaves the chip: only its nonzero
+ * entries -- (i, j) with j = i or an ancestor dof of i -- are formed, and factorised in place in LDS.
+ * Each call is a pure function of the batch's CURRENT qpos (sg_forward_smooth: and qvel, act and the per-env stiffness the env's next
+ * step uses, in stream order against sg_set_stiffness).  env_ids as in sg_get_poses (HOST, NULL = all); all other arrays are DEVICE
+ * pointers unless stated, row k belonging to the k-th listed env.  The calls read the batch, change nothing in it and do not
+ * synchronise the host; free quaternions are normalised on the way in.
+ * The factorisation is mj_factorM's: M = L' D L, L unit lower triangular with L[k][j] != 0 only where dof j is an ancestor of dof k.  NO
+ * pivoting and NO clamping of small pivots.
+ * pivot: [n_ids], min over the dofs of D_i / M_ii: 1 for a diagonal M, falling towards 0 as M approaches singularity.  If some D_i is not
+ *   finite or is <= 0 the env gets NaN in every other output of the call and pivot holds that ratio (or NaN).  A tiny positive pivot gives
+ *   finite results that are not meaningful: pivot is how the caller learns of it.
+ * sg_solve_mass: x = M^-1 y (mj_solveM).  y and x are [n_ids][n_rhs][nv]; x may be the same pointer as y.  y and at least one of x and
+ *   pivot are required.
+ * sg_forward_smooth: qfrc_smooth [n_ids][nv] = passive + actuator + qfrc_applied - bias, sg_get_joint_forces' three arrays and the
+ *   caller's qfrc_applied [n_ids][nv] (NULL: zero); qacc_smooth [n_ids][nv] = M^-1 qfrc_smooth (mj_fwdAcceleration): the acceleration
+ *   without contacts, equalities and limits.  Any output may be NULL.  Two identities: sg_inverse_dynamics(qacc_smooth) = actuator +
+ *   qfrc_applied; and with the qacc of a step, M (qacc - qacc_smooth) is the generalised force of the constraints.
+ * sg_get_point_inertia: W [n_ids][n_pts][6][6] = J M^-1 J', the inverse inertia seen at a body-fixed point: J is jacr in rows 0 - 2 and
+ *   jacp in rows 3 - 5 of sg_get_jacobians for the same points -- the angular-then-linear order of sg_get_point_motion's vel.  Each pair
+ *   is computed once and stored twice: W is symmetric to the bit; all zeros for a point on the world body.  1 / (n' W[3:6][3:6] n) is
+ *   the effective mass along a unit vector n.  pt_body [n_pts] and pt_pos [n_pts][3] are HOST arrays as in sg_get_jacobians.
+ * No atomics: two calls give the same bits; an env's bits depend neither on the env list, nor on its order, nor on which outputs are
+ * NULL; a right-hand side's bits depend neither on n_rhs nor on its place in the list, a point's neither on n_pts nor on its place.  An
+ * env whose state -- the qpos, qvel, y rows or qfrc_applied row that the call uses -- holds a NaN or inf gets NaN in every output of the
+ * call, pivot included, and disturbs no other env.
+ * SG_ERR_INVALID (checked before anything touches the device; nothing is written): NULL batch, n_ids <= 0, an env id out of range,
+ * n_rhs <= 0 or n_pts <= 0, NULL y, NULL x and pivot together, NULL pt_body or pt_pos, a body id outside [0, nbody), a non-finite pt_pos.
+ * SG_ERR_MODEL, with the limit named in the message: a model sg_get_mass_matrix cannot run, and a model whose LDS block does not fit
+ * the 160 KB a workgroup can have: sg_get_mass_matrix' records, nM + nv doubles of factor (nM: the nonzero entries of M's lower
+ * triangle) and six right-hand sides of nv doubles.  A serial chain of 1024 dofs has nM = 524 800 and is refused; the committed scenes
+ * have nM between 54 and 1567. */
+int sg_solve_mass(sg_batch* b, const int32_t* env_ids, int n_ids, int n_rhs, const double* y, double* x, double* pivot, void* stream);
+int sg_forward_smooth(sg_batch* b, const int32_t* env_ids, int n_ids, const double* qfrc_applied, double* qacc_smooth, double* qfrc_smooth, double* pivot,
+                      void* stream);
+int sg_get_point_inertia(sg_batch* b, const int32_t* env_ids, int n_ids, int n_pts, const int32_t* pt_body, const double* pt_pos, double* W, double* pivot,
+                         void* stream);
+
 /* The recurrence of one direction of one fp64 LSTM layer with H = 128 hidden units (csrc/sg_lstm.hip), for the Conv-LSTM and
  * Conv-BiLSTM regressors (soft-grip_amd/lstm.py).  Keras' conventions: gate order i, f, g (the candidate), o along the 4H axis, sigmoid
  * for i, f and o, tanh for g and for the cell, row-major kernels.  The caller keeps what is regular -- the input projection

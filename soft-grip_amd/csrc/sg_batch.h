@@ -10,6 +10,7 @@
 #include "sg_dyn.h"
 #include "sg_smooth.h"
 #include "sg_point.h"
+#include "sg_solve.h"
 #include "sg_skin.h"
 #include "sg_rows_host.h"   // (sg_work.h, sg_plan.h)
 #include "sg_devmem.h"   // SgArena, SgScratch: the owners of every device buffer below (after the HIP runtime's declarations)
@@ -38,6 +39,7 @@ struct sg_model {
   SgDynHost dyn;    // masses, springs, sites and tendons of sg_get_velocities / sg_get_tendons / sg_get_energy
   SgSmoothHost smooth;   // dampers, actuators, child lists and parent dofs of sg_get_mass_matrix / sg_get_joint_forces / sg_inverse_dynamics
   SgPointHost point;     // the dof-parent chain's entries and the sites of sg_get_point_motion / sg_get_jacobians / sg_model_sites
+  SgSolveHost solve;     // the packed factor's schedule of sg_solve_mass / sg_forward_smooth / sg_get_point_inertia
   SgSkinHost skin;  // the composite's skin (sg_skin.h; nvert == 0: none): sg_model_set_skin, drawn by sg_render_ex
 };
 
@@ -130,6 +132,12 @@ struct sg_batch {
   bool point_attr_set = false;
   SgScratch<int> pt_ids;
   SgScratch<double> pt_d;
+  // mass-matrix solves, smooth forward dynamics and point inertias: the solve table, a row of nv zeros, the last call's points
+  int* solve_i = nullptr;
+  double* solve_zero = nullptr;
+  bool solve_attr_set = false;
+  SgScratch<int> sv_ids;
+  SgScratch<double> sv_pos;
   ~sg_batch() {   // (on the batch's device: sg_batch_destroy.  The arenas and scratch buffers free themselves)
     for (auto& e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (auto& e : ev_pgs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }

@@ -1,7 +1,8 @@
 // sg_readout.hip -- the read-out half of the C ABI (include/softgrip.h): sg_get_poses, sg_render / sg_render_ex and the skin,
 // sg_get_contacts, sg_ray, sg_get_velocities / sg_get_tendons / sg_get_energy, sg_get_mass_matrix / sg_get_joint_forces /
-// sg_inverse_dynamics, sg_get_point_motion / sg_get_jacobians, with the kernels they launch (the *_kernel*.h files, whose
-// device assembly is sg_readout.device.s) and the host builders of their per-model tables (sg_readout.h, sg_dyn.h, sg_smooth.h, sg_point.h).  None of them writes the state: every pipeline is served.  No CPU fallback.
+// sg_inverse_dynamics, sg_get_point_motion / sg_get_jacobians, sg_solve_mass / sg_forward_smooth / sg_get_point_inertia, with the kernels
+// they launch (the *_kernel*.h files, whose device assembly is sg_readout.device.s) and the host builders of their per-model tables
+// (sg_readout.h, sg_dyn.h, sg_smooth.h, sg_point.h; sg_solve.h builds its own).  None of them writes the state: every pipeline is served.  No CPU fallback.
 #include <algorithm>
 #include <cstring>
 #include <type_traits>
@@ -15,6 +16,7 @@
 #include "sg_dyn_kernel.h"
 #include "sg_smooth_kernel.h"
 #include "sg_point_kernel.h"
+#include "sg_solve_kernel.h"
 
 // ---- the builders sg_model_create calls (sg_readout.h) ----
 // an array of the blob as `var`, its length in c (want >= 0: that many elements), or the builder ends with T->err set
@@ -859,6 +861,100 @@ int sg_get_jacobians(sg_batch* b, const int32_t* env_ids, int n_ids, int n_pts, 
                      double* jacr, void* stream) {
   return point("sg_get_jacobians", b, env_ids, n_ids, n_pts, pt_body, pt_pos, nullptr, qpos, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                jacp, jacr, false, stream);
+}
+
+// ---- mass-matrix solves, smooth forward dynamics and point inertias: one kernel (sg_solve_kernel), in the mode of the entry point fn ----
+static int solve(const char* fn, int mode, sg_batch* b, const int32_t* env_ids, int n_ids, int n_rhs, const double* y, double* x, const double* applied,
+                 double* qacc, double* qfrc, const int32_t* pt_body, const double* pt_pos, double* W, double* pivot, void* stream) {
+  // (argument checks first, in an order that lets each be reached without a device)
+  const std::string f = std::string(fn) + ": ";
+  if (n_ids <= 0) return fail(SG_ERR_INVALID, f + "n_ids must be positive");
+  if (mode == SGV_MODE_SOLVE && n_rhs <= 0) return fail(SG_ERR_INVALID, f + "n_rhs must be positive");
+  if (mode == SGV_MODE_POINT && n_rhs <= 0) return fail(SG_ERR_INVALID, f + "n_pts must be positive");
+  if (!b) return fail(SG_ERR_INVALID, f + "null batch");
+  if (mode == SGV_MODE_SOLVE && !y) return fail(SG_ERR_INVALID, f + "null y");
+  if (mode == SGV_MODE_SOLVE && !x && !pivot) return fail(SG_ERR_INVALID, f + "x and pivot are both null");
+  if (mode == SGV_MODE_POINT && (!pt_body || !pt_pos)) return fail(SG_ERR_INVALID, f + "null pt_body or pt_pos");
+  const SgKinHost& K = b->m->kin;
+  const SgDynHost& Dn = b->m->dyn;
+  const SgSmoothHost& Sm = b->m->smooth;
+  const SgSolveHost& Sv = b->m->solve;
+  const SgPlanHeader& H = b->m->plan.h;
+  if (mode == SGV_MODE_POINT)
+    for (int p = 0; p < n_rhs; p++) {
+      if (K.ok && (pt_body[p] < 0 || pt_body[p] >= K.o.nbody))
+        return fail(SG_ERR_INVALID, f + "body id " + std::to_string(pt_body[p]) + " of point " + std::to_string(p) + " outside [0, " + std::to_string(K.o.nbody) + ")");
+      for (int c = 0; c < 3; c++)
+        if (!std::isfinite(pt_pos[3 * p + c])) return fail(SG_ERR_INVALID, f + "pt_pos of point " + std::to_string(p) + " is not finite");
+    }
+  if (K.ok && !Sv.ok) return fail(SG_ERR_MODEL, f + Sv.err);
+  if (K.ok && (Dn.o.nv != H.nv || K.o.nq != H.nq || K.o.njnt != H.njnt || Dn.o.ntendon != H.ntendon || Sm.o.nu != H.nu))   // (the strides of qpos / qvel / act and the masks' lengths)
+    return fail(SG_ERR_MODEL, f + "the blob's joint, dof, tendon or actuator counts differ from the plan's");
+  if ((long long)n_ids * n_rhs > 0x7fffffffll / 36) return fail(SG_ERR_INVALID, f + "too many envs x right-hand sides or points for one launch");
+  Readout r{b, fn, (hipStream_t)stream};
+  if (int rc = r.prepare(env_ids, n_ids)) return rc;
+  if (!x && !qacc && !qfrc && !W && !pivot) return SG_OK;
+  if (!b->dyn_d) {   // (on the side, as the pose tables)
+    SgArena A;
+    double* dd = nullptr;
+    int* di = nullptr;
+    if (!(A.upload(&dd, Dn.dbl) && A.upload(&di, Dn.ints))) return devmem_fail(A.nomem, std::string(fn) + " (dynamics tables)");
+    A.give_to(b->mem);
+    b->dyn_d = dd; b->dyn_i = di;
+  }
+  if (!b->smooth_d) {
+    SgArena A;
+    double* sd = nullptr;
+    int* si = nullptr;
+    if (!(A.upload(&sd, Sm.dbl) && A.upload(&si, Sm.ints))) return devmem_fail(A.nomem, std::string(fn) + " (smooth tables)");
+    A.give_to(b->mem);
+    b->smooth_d = sd; b->smooth_i = si;
+  }
+  if (!b->solve_i) {   // the solve table, and a row of nv zeros: the qvel the calls that need M alone walk at
+    SgArena A;
+    int* vi = nullptr;
+    double* z = nullptr;
+    if (!(A.upload(&vi, Sv.ints) && A.upload(&z, std::vector<double>(Dn.o.nv, 0.0)))) return devmem_fail(A.nomem, std::string(fn) + " (solve table)");
+    A.give_to(b->mem);
+    b->solve_i = vi; b->solve_zero = z;
+  }
+  // a tile of SGV_MINRHS right-hand sides fits beside the fixed block (sgv_build); the launch asks for the tile it uses, no more
+  const long long fixed = sgv_fixed_doubles(K.o.nbody, Dn.o.nv, Dn.o.ntendon, Sv.o.nM), room = sgv_tile(K.o.nbody, Dn.o.nv, Dn.o.ntendon, Sv.o.nM);
+  const int tile = mode == SGV_MODE_FORWARD ? 1 : (int)std::min<long long>(n_rhs, mode == SGV_MODE_POINT ? room / 6 : room);
+  const size_t lds = sizeof(double) * ((size_t)fixed + (size_t)tile * (mode == SGV_MODE_POINT ? 6 : 1) * Dn.o.nv);
+  if (!b->solve_attr_set) {   // per device, as the smooth read-out's attribute: above 64 KB the launch's dynamic LDS must be granted
+    HIPCHK(hipFuncSetAttribute((const void*)sg_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SGV_LDS_MAX - SGV_STATIC_LDS));
+    b->solve_attr_set = true;
+  }
+  if (mode == SGV_MODE_POINT) {   // the points: host arrays, read here and copied on the stream
+    if (int rc = r.reserve(b->sv_ids, (size_t)n_rhs, "point body ids")) return rc;
+    if (int rc = r.reserve(b->sv_pos, 3 * (size_t)n_rhs, "points")) return rc;
+    HIPCHK(hipMemcpyAsync(b->sv_ids.p, pt_body, sizeof(int) * n_rhs, hipMemcpyHostToDevice, r.s));
+    HIPCHK(hipMemcpyAsync(b->sv_pos.p, pt_pos, sizeof(double) * 3 * n_rhs, hipMemcpyHostToDevice, r.s));
+  }
+  SgSolveArgs a;
+  a.D = b->kin_d; a.I = b->kin_i; a.o = K.o; a.DD = b->dyn_d; a.DI = b->dyn_i; a.d = Dn.o; a.SD = b->smooth_d; a.SI = b->smooth_i; a.s = Sm.o;
+  a.VI = b->solve_i; a.v = Sv.o;
+  a.qpos = b->qpos; a.qvel = b->qvel; a.act = b->act; a.kenv = b->kenv; a.zero = b->solve_zero; a.kmask_jnt = b->kmask_jnt; a.kmask_ten = b->kmask_ten;
+  a.env_ids = r.dids; a.n_ids = n_ids; a.mode = mode; a.n_rhs = mode == SGV_MODE_FORWARD ? 1 : n_rhs; a.tile = tile;
+  a.y = y; a.x = x; a.applied = applied; a.qacc = qacc; a.qfrc = qfrc;
+  a.pt_body = mode == SGV_MODE_POINT ? b->sv_ids.p : nullptr; a.pt_pos = mode == SGV_MODE_POINT ? b->sv_pos.p : nullptr; a.W = W; a.pivot = pivot;
+  hipLaunchKernelGGL(sg_solve_kernel, dim3(n_ids), dim3(64), lds, r.s, a);
+  HIPCHK(hipGetLastError());
+  return SG_OK;
+}
+
+int sg_solve_mass(sg_batch* b, const int32_t* env_ids, int n_ids, int n_rhs, const double* y, double* x, double* pivot, void* stream) {
+  return solve("sg_solve_mass", SGV_MODE_SOLVE, b, env_ids, n_ids, n_rhs, y, x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pivot, stream);
+}
+int sg_forward_smooth(sg_batch* b, const int32_t* env_ids, int n_ids, const double* qfrc_applied, double* qacc_smooth, double* qfrc_smooth, double* pivot,
+                      void* stream) {
+  return solve("sg_forward_smooth", SGV_MODE_FORWARD, b, env_ids, n_ids, 1, nullptr, nullptr, qfrc_applied, qacc_smooth, qfrc_smooth, nullptr, nullptr, nullptr,
+               pivot, stream);
+}
+int sg_get_point_inertia(sg_batch* b, const int32_t* env_ids, int n_ids, int n_pts, const int32_t* pt_body, const double* pt_pos, double* W, double* pivot,
+                         void* stream) {
+  return solve("sg_get_point_inertia", SGV_MODE_POINT, b, env_ids, n_ids, n_pts, nullptr, nullptr, nullptr, nullptr, nullptr, pt_body, pt_pos, W, pivot, stream);
 }
 
 int sg_model_nsite(const sg_model* m) { return m ? (int)m->point.site_body.size() : 0; }

@@ -441,6 +441,20 @@ class ManEnv(Env):
         """mj_jac of body-fixed points (sg_get_jacobians): NativeBatch.jacobians' dict of device tensors jacp, jacr [k, P, 3, nv]"""
         return self.env.jacobians(body, pos, qpos=qpos, env_ids=env_ids)
 
+    def solve_mass(self, y, env_ids=None, out=None):
+        """mj_solveM at the current state: y [k, R, nv] or [k, nv] (device, float64) -> (x = M^-1 y, pivot [k]); NativeBatch.solve_mass"""
+        return self.env.solve_mass(y, env_ids=env_ids, out=out)
+
+    def get_qacc_smooth(self, qfrc_applied=None, env_ids=None):
+        """the smooth forward dynamics at the current state (data.qacc_smooth, data.qfrc_smooth): NativeBatch.forward_smooth's dict of
+        device tensors qacc_smooth, qfrc_smooth [k, nv] and pivot [k]"""
+        return self.env.forward_smooth(qfrc_applied, env_ids=env_ids)
+
+    def get_point_inertia(self, body, pos, quat=None, env_ids=None):
+        """J M^-1 J' at body-fixed points (sg_get_point_inertia): (W [k, P, 6, 6], pivot [k]).  quat is accepted and ignored -- W is in
+        world axes -- so that ``get_point_inertia(*env.sensor_sites())`` works as ``get_point_motion(*env.sensor_sites())`` does"""
+        return self.env.point_inertia(body, pos, env_ids=env_ids)
+
     def sensor_sites(self):
         """the model's IMU sites -- every site a gyro or an accelerometer sits at, in ascending order -- as (body [S] int32, pos [S, 3],
         quat [S, 4]), ready to pass as points: ``get_point_motion(*env.sensor_sites())``"""

@@ -27,6 +27,7 @@ SYMBOLS = [
     "sg_lstm_forward", "sg_lstm_backward", "sg_get_velocities", "sg_get_tendons", "sg_get_energy",
     "sg_get_mass_matrix", "sg_get_joint_forces", "sg_inverse_dynamics",
     "sg_get_point_motion", "sg_get_jacobians", "sg_model_nsite", "sg_model_sites",
+    "sg_solve_mass", "sg_forward_smooth", "sg_get_point_inertia",
 ]
 SG_RENDER_SKIN = 1
 # sg_ray: category bits of cat_mask (ground plane, static, moving finger box, shell element, centre sphere) and flags
@@ -111,6 +112,9 @@ def load_library(path):
     L.sg_get_jacobians.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32), dp, dp, dp, dp, vp]
     L.sg_model_nsite.argtypes = [vp]
     L.sg_model_sites.argtypes = [vp, C.POINTER(C.c_int32), dp, dp]
+    L.sg_solve_mass.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, dp, dp, dp, vp]
+    L.sg_forward_smooth.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, dp, dp, dp, vp]
+    L.sg_get_point_inertia.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32), dp, dp, dp, vp]
     L.sg_lstm_forward.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int, vp]
     L.sg_lstm_backward.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, vp]
     L.sg_profile_enable.argtypes = [vp, C.c_int]
@@ -422,6 +426,51 @@ class NativeBatch:
                                             body.ctypes.data_as(C.POINTER(C.c_int32)), pos.ctypes.data_as(C.c_void_p), self._rows(qpos, k, m.nq),
                                             _ptr(out["jacp"]), _ptr(out["jacr"]), self._stream()))
         return out
+
+    def solve_mass(self, y, env_ids=None, out=None):
+        """x = M^-1 y of the listed envs (None: all) on the current state (sg_solve_mass; mj_solveM): y, a float64 device tensor
+        [k, R, nv] (or [k, nv]: one right-hand side), row i the i-th listed env's -> (x, pivot): x of y's shape, pivot [k] = min D_i /
+        M_ii of the factor M = L' D L (1 for a diagonal M, towards 0 as M nears singularity; an env whose pivot is NaN or <= 0 has NaN
+        in x).  out: a contiguous tensor of y's shape to fill; it may be y itself."""
+        t = self.torch
+        ids, k = self._ids(env_ids)
+        nv = self.nmodel.nv
+        assert y.is_cuda and y.dtype == t.float64 and y.is_contiguous() and y.shape[0] == k and y.shape[-1] == nv and y.dim() in (2, 3)
+        if out is None:
+            out = t.empty_like(y)
+        assert out.is_cuda and out.dtype == t.float64 and out.is_contiguous() and out.shape == y.shape
+        pivot = t.empty(k, dtype=t.float64, device=self.device)
+        self._check(self.L.sg_solve_mass(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, 1 if y.dim() == 2 else y.shape[1],
+                                         _ptr(y), _ptr(out), _ptr(pivot), self._stream()))
+        return out, pivot
+
+    def forward_smooth(self, qfrc_applied=None, env_ids=None):
+        """the smooth forward dynamics of the listed envs (None: all) on the current state (sg_forward_smooth; mj_fwdAcceleration):
+        dict of float64 device tensors qfrc_smooth [k, nv] = passive + actuator + qfrc_applied - bias (joint_forces()' arrays;
+        qfrc_applied [k, nv] on the device, None: zero), qacc_smooth [k, nv] = M^-1 qfrc_smooth, the acceleration without contacts,
+        equalities and limits, and pivot [k] as in solve_mass.  ``inverse_dynamics(qacc_smooth) = actuator + qfrc_applied``."""
+        t = self.torch
+        ids, k = self._ids(env_ids)
+        nv = self.nmodel.nv
+        out = {name: t.empty(k, nv, dtype=t.float64, device=self.device) for name in ("qacc_smooth", "qfrc_smooth")}
+        out["pivot"] = t.empty(k, dtype=t.float64, device=self.device)
+        self._check(self.L.sg_forward_smooth(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, self._rows(qfrc_applied, k, nv),
+                                             _ptr(out["qacc_smooth"]), _ptr(out["qfrc_smooth"]), _ptr(out["pivot"]), self._stream()))
+        return out
+
+    def point_inertia(self, body, pos, env_ids=None):
+        """the inverse inertia seen at body-fixed points (sg_get_point_inertia): points as in jacobians() -> (W, pivot): W [k, P, 6, 6]
+        = J M^-1 J' with J = (jacr; jacp), angular rows first, symmetric to the bit, zero for a point on the world; pivot [k] as in
+        solve_mass.  ``1 / (n @ W[e, p, 3:, 3:] @ n)`` is the effective mass along a unit vector n."""
+        t = self.torch
+        ids, k = self._ids(env_ids)
+        body, pos, _ = self._points(body, pos, None)
+        P = len(body)
+        W = t.empty(k, P, 6, 6, dtype=t.float64, device=self.device)
+        pivot = t.empty(k, dtype=t.float64, device=self.device)
+        self._check(self.L.sg_get_point_inertia(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, P,
+                                                body.ctypes.data_as(C.POINTER(C.c_int32)), pos.ctypes.data_as(C.c_void_p), _ptr(W), _ptr(pivot), self._stream()))
+        return W, pivot
 
     def contacts(self, env_ids=None, max_contacts=256):
         """mj_collision of the listed envs (None: all) on the current state (sg_get_contacts): dict of device tensors ncon [k] int32
