@@ -1,7 +1,8 @@
 // Host program of scripts/sanitize/run.sh (ASan + UBSan, CPU only).
 //   host_main FILE.xml ...            compiles each scene in both composite variants and builds both plans (two-finger and tree)
-//   host_main --mutate FILE.sgmodel.. feeds both plan builders, and the blob lookups sg_readout.hip's builders use, damaged copies of each
-//                                     blob: every one must be refused with a message, and none may make a reader leave its buffer
+//   host_main --mutate FILE.sgmodel.. feeds both plan builders, and then the read-out tables' builders (csrc/sg_tables.cpp, sg_solve.h),
+//                                     damaged copies of each blob: both plan builders must refuse every one with a message, every
+//                                     table builder must answer with ok or a message, and none may make a reader leave its buffer
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -13,12 +14,30 @@
 #include "../../soft-grip_amd/csrc/sg_blob.h"
 #include "../../soft-grip_amd/csrc/sg_mjcf.h"
 #include "../../soft-grip_amd/csrc/sg_plan.h"
+#include "../../soft-grip_amd/csrc/sg_point.h"
+#include "../../soft-grip_amd/csrc/sg_solve.h"
 
 static bool build_both(const void* blob, size_t n, std::string msg[2]) {
   SgPlan P, PT;
   auto tree = std::make_unique<SgTreeDev>();
   const bool a = sg_plan_build(blob, n, &P, &msg[0]), b = sg_tree_plan_build(blob, n, &PT, tree.get(), &msg[1]);
   return a || b;
+}
+
+// kin, con, dyn, smooth, point, solve, as sg_model_create calls them (plan == NULL: a plan that names no geom) -> the first table that has
+// neither ok nor a message, or NULL
+static const char* build_tables(const void* blob, size_t n, const SgPlan* plan, const SgTreeDev* tree, bool fast) {
+  SgPlan none{};
+  none.h.plane_geom = none.h.center_geom = -1;
+  SgKinHost K{}; SgConHost C{}; SgDynHost D{}; SgSmoothHost S{}; SgPointHost P{}; SgSolveHost V{};
+  sgk_build(blob, n, plan ? *plan : none, tree, fast, &K);
+  sgc_from_blob(blob, n, K, &C);
+  sgd_build(blob, n, K, &D);
+  sgs_build(blob, n, K, D, &S);
+  sgp_build(blob, n, K, D, &P);
+  sgv_build(K, D, S, &V);
+  auto silent = [](const auto& t) { return !t.ok && t.err.empty(); };
+  return silent(K) ? "kin" : silent(C) ? "con" : silent(D) ? "dyn" : silent(S) ? "smooth" : silent(P) ? "point" : silent(V) ? "solve" : nullptr;
 }
 
 static int n_mut = 0, n_bad = 0;
@@ -33,18 +52,10 @@ static void mutant(const char* what, long long at, const std::string& bytes) {
     printf("ACCEPTED: %s at %lld (%zu bytes): '%s' / '%s'\n", what, at, bytes.size(), msg[0].c_str(), msg[1].c_str());
     n_bad++;
   }
-  // the lookups of sgk_build and sgc_from_blob (sg_readout.hip): whatever they return must lie inside the buffer (read it all)
-  static const struct { const char* name; int dt; } look[] = {{"body_parentid", SG_DT_I32}, {"body_pos", SG_DT_F64}, {"jnt_type", SG_DT_I32},
-      {"qpos0", SG_DT_F64}, {"geom_rbound", SG_DT_F64}, {"geom_margin", SG_DT_F64}, {"jnt_qposadr", SG_DT_I32}, {"opt_i", SG_DT_I32},
-      {"sensor_adr", SG_DT_I32}, {"names", SG_DT_U8}, {"no_such_array", SG_DT_F64}};
-  unsigned sum = 0;
-  for (const auto& l : look) {
-    long long cnt = 0;
-    const unsigned char* p = (const unsigned char*)sg_blob_find(buf.get(), bytes.size(), l.name, l.dt, &cnt);
-    for (long long i = 0; p && i < cnt * (l.dt == SG_DT_F64 ? 8 : l.dt == SG_DT_I32 ? 4 : 1); i++) sum += p[i];
+  if (const char* silent = build_tables(buf.get(), bytes.size(), nullptr, nullptr, false)) {
+    printf("SILENT: %s at %lld (%zu bytes): the %s table has neither ok nor a message\n", what, at, bytes.size(), silent);
+    n_bad++;
   }
-  static volatile unsigned sink;
-  sink = sum;
 }
 
 static int mutate(const char* path) {
@@ -52,6 +63,15 @@ static int mutate(const char* path) {
   const std::string blob((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
   std::string msg[2];
   if (!build_both(blob.data(), blob.size(), msg)) { printf("%s: no builder takes the intact blob: %s / %s\n", path, msg[0].c_str(), msg[1].c_str()); return 1; }
+  {   // the intact blob's tables, on the plans sg_model_create would use
+    SgPlan P, PT;
+    auto tree = std::make_unique<SgTreeDev>();
+    const bool fast = sg_plan_build(blob.data(), blob.size(), &P, &msg[0]), has_tree = sg_tree_plan_build(blob.data(), blob.size(), &PT, tree.get(), &msg[1]);
+    if (const char* silent = build_tables(blob.data(), blob.size(), fast ? &P : &PT, has_tree ? tree.get() : nullptr, fast)) {
+      printf("%s: the %s table of the intact blob has neither ok nor a message\n", path, silent);
+      return 1;
+    }
+  }
   sg_blob_header hd;
   memcpy(&hd, blob.data(), sizeof hd);
   std::vector<size_t> rec_at;   // the records' offsets, then the end

@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 if _HERE not in sys.path:
     sys.path.insert(0, _HERE)      # isa_check.py (this directory is a package with a hyphen in its name: imported by file)
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["sg_api.hip", "sg_readout.hip", "sg_phase.hip", "sg_rows.hip", "sg_tree.hip", "sg_lstm.hip", "sg_plan.cpp", "sg_mjcf.cpp"]   # what the product runs
+SOURCES = ["sg_api.hip", "sg_readout.hip", "sg_phase.hip", "sg_rows.hip", "sg_tree.hip", "sg_lstm.hip", "sg_plan.cpp", "sg_mjcf.cpp", "sg_tables.cpp"]   # what the product runs
 # -amdgpu-sched-strategy=iterative-ilp: LLVM's iterative ILP machine scheduler instead of the default max-occupancy one.  The
 # kernels run at one or two wavefronts per SIMD whatever their register count (the solver by design, the phase kernel by its
 # LDS), so trading registers for a shorter dependency-stalled schedule is free: solver -2.5 %, phase kernel -4.9 % per episode

@@ -97,9 +97,12 @@ struct sg_batch {
   double prof_pgs_ms = 0;
   long long prof_pgs_n = 0;
   // ---- the read-outs (sg_readout.hip), everything allocated at first use ----
+  // the per-model tables on the batch's device (sg_devmem.h SgDevTable; Readout::need_* in sg_readout.hip brings each up with what it
+  // is built on): kin the kinematics table; con the candidate pairs (i) and the margins / bounding radii (d); dyn, smooth, point and solve
+  // the tables of sg_dyn.h, sg_smooth.h, sg_point.h and sg_solve.h; zero a row of max(nv, 1) zeros, the qvel the point and solve calls
+  // that need none walk at
+  SgDevTable kin, con, dyn, smooth, point, solve, zero;
   // pose read-out / renderer
-  double* kin_d = nullptr;
-  int* kin_i = nullptr;
   SgScratch<int> kin_ids;    // the listed env ids on the device
   SgScratch<float> rrecs;    // [n_ids][ngeom][SGR_REC] fp32 geom records of the last sg_render
   // the skin (sg_render_ex): tables uploaded at first use and again when the model's skin version has moved
@@ -109,8 +112,6 @@ struct sg_batch {
   SgScratch<double> skin_xpos, skin_xquat;   // [n_ids][nbody][3 | 4] body poses of the last skin render
   SgScratch<float> skin_vrec;                // [n_ids][nvert][SGR_VREC] vertex records of the last skin render
   // contact read-out
-  int* con_pairs = nullptr;
-  double* con_gaux = nullptr;
   SgScratch<double> con_scratch;   // per-env pose blocks of a model whose poses do not fit LDS
   bool con_attr_set = false;
   // ray queries: the poses of the last call's envs and its rays' body / exclude ids
@@ -119,22 +120,13 @@ struct sg_batch {
   SgScratch<double> ray_vtx;                                      // [n_ids][nvert][3] the skin's vertices of the last SG_RAY_SKIN call
   const int* skin_vis = nullptr;                                  // [skin_nvis] the geoms the skin does not replace (in skin_mem, with skin_dev)
   int skin_nvis = 0;
-  // velocity, tendon and energy read-outs: the dynamics table
-  double* dyn_d = nullptr;
-  int* dyn_i = nullptr;
-  // mass-matrix, joint-force and inverse-dynamics read-outs: the smooth table
-  double* smooth_d = nullptr;
-  int* smooth_i = nullptr;
+  // mass-matrix, joint-force and inverse-dynamics read-outs
   bool smooth_attr_set = false;
-  // point motion and Jacobians: the point table, and the last call's points (body ids; positions [n_pts][3] then quaternions [n_pts][4])
-  int* point_i = nullptr;
-  double* point_zero = nullptr;   // [nv] zeros
+  // point motion and Jacobians: the last call's points (body ids; positions [n_pts][3] then quaternions [n_pts][4])
   bool point_attr_set = false;
   SgScratch<int> pt_ids;
   SgScratch<double> pt_d;
-  // mass-matrix solves, smooth forward dynamics and point inertias: the solve table, a row of nv zeros, the last call's points
-  int* solve_i = nullptr;
-  double* solve_zero = nullptr;
+  // mass-matrix solves, smooth forward dynamics and point inertias: the last call's points
   bool solve_attr_set = false;
   SgScratch<int> sv_ids;
   SgScratch<double> sv_pos;

@@ -1,5 +1,5 @@
 // sg_blob.h -- the one reader of the model blob (include/softgrip_model.h) and its schema SG_MODEL_ARRAYS, which sg_mjcf.cpp writes from.
-// Host only, no HIP: sg_plan.cpp, sg_readout.hip and the g++ builds under tests/emu and scripts/sanitize all read blobs through it.
+// Host only, no HIP: sg_plan.cpp, sg_tables.cpp and the g++ builds under tests/emu and scripts/sanitize all read blobs through it.
 //   sg_blob_valid   magic, version, total_bytes == nbytes, and every one of the nrec records with its padded payload inside the buffer
 //   sg_blob_find    the array (name, dtype): pointer and count.  Checks every record it walks on its own, so it is safe on bytes nobody
 //                   validated: it never reads outside [blob, blob + nbytes)

@@ -41,6 +41,30 @@ struct SgArena {
   }
 };
 
+// a per-model table on a batch's device: the device pointers of its sections -- doubles, ints, or both -- all NULL until every section
+// is up.  ensure() is the one way up: the sections are uploaded on a side arena and handed to `owner` only when all of them are there, so
+// a failure leaves the table and the owner as they were (and a later call may try again); once up, it costs a comparison
+struct SgDevTable {
+  double* d = nullptr;
+  int* i = nullptr;
+  bool nomem = false;
+  // dbl / ints: the host sections (NULL: the table has no such section)
+  bool ensure(SgArena& owner, const std::vector<double>* dbl, const std::vector<int>* ints) {
+    if (d || i) return true;
+    SgArena side;
+    double* pd = nullptr;
+    int* pi = nullptr;
+    nomem = false;
+    if (!((!dbl || side.upload(&pd, *dbl)) && (!ints || side.upload(&pi, *ints)))) {
+      nomem = side.nomem;
+      return false;
+    }
+    side.give_to(owner);
+    d = pd; i = pi;
+    return true;
+  }
+};
+
 // a buffer that grows on demand and never shrinks; its contents do not survive a growth
 template <class T>
 struct SgScratch {

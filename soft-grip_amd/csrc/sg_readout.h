@@ -1,13 +1,18 @@
 // sg_readout.h -- what the read-outs (sg_get_poses, sg_render, sg_get_contacts, sg_ray) keep per model and per batch: the kinematics table
 // with mj_kinematics' per-body / per-geom routines, the contact read-out's pair table and the skin's device tables.  The builders are
-// defined in sg_readout.hip; sg_model_create (sg_api.hip) calls them, sg_model and sg_batch (sg_batch.h) hold the results.
+// defined in sg_tables.cpp (host C++, no HIP); sg_model_create (sg_api.hip) calls them, sg_model and sg_batch (sg_batch.h) hold the results.
 #pragma once
+#if !defined(__HIPCC__) && !defined(__host__)
+#define __host__
+#define __device__
+#endif
 #include <cmath>
 #include <string>
 #include <vector>
 
 #include "sg_contacts.h"   // SGC_MAXCON; the joint and geom type codes of softgrip_model.h
 #include "sg_plan.h"
+#include "sg_render.h"     // the geom categories and types in gmeta (SGR_CAT_*, SGR_PLANE ..), uint32_t
 
 // ---- the kinematics table: one double and one int array, sections at the offsets below ----
 struct SgKinOff {
@@ -27,6 +32,17 @@ struct SgKinHost {
   std::vector<int> ints;
   std::vector<double> qpos0, rbound;
 };
+
+// the one writer of every read-out table (this one, sg_dyn.h, sg_smooth.h, sg_point.h, sg_solve.h): appends a section to a table's array
+// and returns the offset it starts at
+template <class T>
+inline int sg_put(std::vector<T>& to, const T* p, size_t n) {
+  const int at = (int)to.size();
+  to.insert(to.end(), p, p + n);
+  return at;
+}
+template <class T>
+inline int sg_put(std::vector<T>& to, const std::vector<T>& section) { return sg_put(to, section.data(), section.size()); }
 
 // mj_kinematics for one body, as mjcf.Model.kinematics() does it (parent pose in px / pq, parent quaternion normalised)
 __host__ __device__ inline void sgk_quat_mul(double* r, const double* a, const double* b) {

@@ -1,14 +1,13 @@
 // sg_readout.hip -- the read-out half of the C ABI (include/softgrip.h): sg_get_poses, sg_render / sg_render_ex and the skin,
 // sg_get_contacts, sg_ray, sg_get_velocities / sg_get_tendons / sg_get_energy, sg_get_mass_matrix / sg_get_joint_forces /
 // sg_inverse_dynamics, sg_get_point_motion / sg_get_jacobians, sg_solve_mass / sg_forward_smooth / sg_get_point_inertia, with the kernels
-// they launch (the *_kernel*.h files, whose device assembly is sg_readout.device.s) and the host builders of their per-model tables
-// (sg_readout.h, sg_dyn.h, sg_smooth.h, sg_point.h; sg_solve.h builds its own).  None of them writes the state: every pipeline is served.  No CPU fallback.
+// they launch (the *_kernel*.h files, whose device assembly is sg_readout.device.s).  Entry points and launches only: the host builders of
+// the per-model tables are in sg_tables.cpp (sg_solve.h builds its own), what brings a table to a batch's device is SgDevTable
+// (sg_devmem.h) under Readout::need_*.  None of them writes the state: every pipeline is served.  No CPU fallback.
 #include <algorithm>
 #include <cstring>
-#include <type_traits>
 
 #include "sg_batch.h"
-#include "sg_blob.h"   // sg_blob_find: the one (bounds-checked) reader of the model blob
 #include "sg_kin_kernels.h"
 #include "sg_contacts_kernel.h"
 #include "sg_ray_kernels.h"
@@ -18,319 +17,11 @@
 #include "sg_point_kernel.h"
 #include "sg_solve_kernel.h"
 
-// ---- the builders sg_model_create calls (sg_readout.h) ----
-// an array of the blob as `var`, its length in c (want >= 0: that many elements), or the builder ends with T->err set
-#define SG_FIELD(T, var, name, dt, want)                                                                                 \
-  const auto* var = (const std::conditional<dt == SG_DT_F64, double, int>::type*)sg_blob_find(blob, nbytes, name, dt, &c); \
-  if (!var || (want >= 0 && c != want)) { T->err = std::string("model blob lacks ") + name; return; }
-
-// the kinematics table: per body its parent, body_pos, body_quat and joints; per joint type, jnt_pos, jnt_axis, qposadr, qpos0; per geom body,
-// geom_pos, geom_quat (as a matrix), geom_size, geom_type, geom_rbound and a category from the plan; the bodies' depth-level schedule
-void sgk_build(const void* blob, size_t nbytes, const SgPlan& plan, const SgTreeDev* tree, bool fast, SgKinHost* K) {
-  long long nb = 0, nj = 0, ng = 0, nq = 0, c = 0;
-  SG_FIELD(K, par, "body_parentid", SG_DT_I32, -1);
-  nb = c;
-  SG_FIELD(K, bpos, "body_pos", SG_DT_F64, 3 * nb);
-  SG_FIELD(K, bquat, "body_quat", SG_DT_F64, 4 * nb);
-  SG_FIELD(K, jadr, "body_jntadr", SG_DT_I32, nb);
-  SG_FIELD(K, jnum, "body_jntnum", SG_DT_I32, nb);
-  SG_FIELD(K, jtype, "jnt_type", SG_DT_I32, -1);
-  nj = c;
-  SG_FIELD(K, jpos, "jnt_pos", SG_DT_F64, 3 * nj);
-  SG_FIELD(K, jaxis, "jnt_axis", SG_DT_F64, 3 * nj);
-  SG_FIELD(K, q0, "qpos0", SG_DT_F64, -1);
-  nq = c;
-  SG_FIELD(K, gtype, "geom_type", SG_DT_I32, -1);
-  ng = c;
-  SG_FIELD(K, gbody, "geom_bodyid", SG_DT_I32, ng);
-  SG_FIELD(K, gpos, "geom_pos", SG_DT_F64, 3 * ng);
-  SG_FIELD(K, gquat, "geom_quat", SG_DT_F64, 4 * ng);
-  SG_FIELD(K, gsize, "geom_size", SG_DT_F64, 3 * ng);
-  SG_FIELD(K, grb, "geom_rbound", SG_DT_F64, ng);
-  long long ca = 0;
-  const int* qadr = (const int*)sg_blob_find(blob, nbytes, "jnt_qposadr", SG_DT_I32, &ca);   // (only blobs with a free joint carry it)
-  if (qadr && ca != nj) qadr = nullptr;
-  if (nb < 1 || nb > 1024) { K->err = "the kinematic tree has more than 1024 bodies"; return; }
-  // checks: parents before children, joint / position addresses in range
-  std::vector<int> depth(nb, 0);
-  for (int i = 1; i < nb; i++) {
-    if (par[i] < 0 || par[i] >= i) { K->err = "body parents must precede their children"; return; }
-    depth[i] = depth[par[i]] + 1;
-    if (jnum[i] < 0 || (jnum[i] > 0 && (jadr[i] < 0 || jadr[i] + jnum[i] > nj))) { K->err = "joint address out of range"; return; }
-  }
-  for (int j = 0; j < nj; j++) {
-    const int qa = qadr ? qadr[j] : j;
-    if (qa < 0 || qa + (jtype[j] == SG_JNT_FREE ? 7 : 1) > nq) { K->err = "joint position address out of range"; return; }
-    if (jtype[j] != SG_JNT_FREE && jtype[j] != SG_JNT_SLIDE && jtype[j] != SG_JNT_HINGE) { K->err = "unsupported joint type"; return; }
-  }
-  for (int g = 0; g < ng; g++)
-    if (gbody[g] < 0 || gbody[g] >= nb) { K->err = "geom body out of range"; return; }
-  // categories from the plan
-  std::vector<int> cat(ng, SGR_CAT_STATIC);
-  if (plan.h.plane_geom >= 0 && plan.h.plane_geom < ng) cat[plan.h.plane_geom] = SGR_CAT_GROUND;
-  for (int g : plan.elem_geom)
-    if (g >= 0 && g < ng) cat[g] = SGR_CAT_ELEM;
-  if (fast)
-    for (int ch = 0; ch < plan.h.nchain; ch++)
-      for (int k = 0; k < plan.h.chain[ch].ngeom; k++) cat[plan.h.chain[ch].g_id[k]] = SGR_CAT_FINGER;
-  if (tree)
-    for (int k = 0; k < tree->NG; k++) cat[tree->g_id[k]] = SGR_CAT_FINGER;
-  if (plan.h.has_center && plan.h.center_geom >= 0 && plan.h.center_geom < ng) cat[plan.h.center_geom] = SGR_CAT_CENTER;
-  // level schedule (level 0 = the world body)
-  int nlevel = 0;
-  for (int i = 0; i < nb; i++) nlevel = std::max(nlevel, depth[i] + 1);
-  std::vector<int> lstart(nlevel + 1, 0), lbody;
-  for (int L = 0; L < nlevel; L++) {
-    lstart[L] = (int)lbody.size();
-    for (int i = 0; i < nb; i++)
-      if (depth[i] == L) lbody.push_back(i);
-  }
-  lstart[nlevel] = (int)lbody.size();
-  SgKinOff& o = K->o;
-  o.nbody = (int)nb; o.ngeom = (int)ng; o.njnt = (int)nj; o.nq = (int)nq; o.nlevel = nlevel;
-  std::vector<double>& D = K->dbl;
-  auto putd = [&](const double* p, size_t n) { int at = (int)D.size(); D.insert(D.end(), p, p + n); return at; };
-  o.bpos = putd(bpos, 3 * nb); o.bquat = putd(bquat, 4 * nb); o.jpos = putd(jpos, 3 * nj); o.jaxis = putd(jaxis, 3 * nj);
-  std::vector<double> jq0(nj);
-  for (int j = 0; j < nj; j++) jq0[j] = q0[qadr ? qadr[j] : j];
-  o.jq0 = putd(jq0.data(), nj);
-  o.gpos = putd(gpos, 3 * ng);
-  std::vector<double> gm(9 * ng);
-  for (int g = 0; g < ng; g++) sgk_quat_mat(&gm[9 * g], gquat + 4 * g);
-  o.gmat = putd(gm.data(), 9 * ng);
-  o.gsize = putd(gsize, 3 * ng);
-  std::vector<int>& I = K->ints;
-  auto puti = [&](const int* p, size_t n) { int at = (int)I.size(); I.insert(I.end(), p, p + n); return at; };
-  o.bpar = puti(par, nb); o.bjadr = puti(jadr, nb); o.bjnum = puti(jnum, nb); o.jtype = puti(jtype, nj);
-  std::vector<int> qa(nj), meta(ng);
-  for (int j = 0; j < nj; j++) qa[j] = qadr ? qadr[j] : j;
-  o.jqadr = puti(qa.data(), nj);
-  o.gbody = puti(gbody, ng);
-  for (int g = 0; g < ng; g++) {
-    meta[g] = (gtype[g] & 0xFF) | (cat[g] << 8);
-    if (K->bad_type < 0 && gtype[g] != SGR_PLANE && gtype[g] != SGR_SPHERE && gtype[g] != SGR_CAPSULE && gtype[g] != SGR_BOX) K->bad_type = gtype[g];
-  }
-  o.gmeta = puti(meta.data(), ng);
-  o.lstart = puti(lstart.data(), lstart.size());
-  o.lbody = puti(lbody.data(), lbody.size());
-  K->qpos0.assign(q0, q0 + nq);
-  K->rbound.assign(grb, grb + ng);
-  K->ok = true;
-}
-
-void sgk_host_fk(const SgKinHost& K, std::vector<double>* body) {
-  const SgKinOff& o = K.o;
-  body->assign((size_t)o.nbody * 7, 0.0);
-  (*body)[3] = 1.0;
-  for (int i = 1; i < o.nbody; i++) {   // (parents precede children)
-    const int p = K.ints[o.bpar + i];
-    sgk_body(K.dbl.data(), K.ints.data(), o, K.qpos0.data(), i, &(*body)[7 * p], &(*body)[7 * p + 3], &(*body)[7 * i]);
-  }
-}
-
-// the default free camera: lookat = centre of the bounding box of the non-plane geoms' centres at qpos0, distance = 2 x (its
-// half-diagonal + the largest bounding radius of those geoms), azimuth 90, elevation -30, fovy 45.  (1.5 x half-diagonal + radius cuts
-// the near finger off at the image border in every committed scene: the gripper's base box alone has a 1.36 m bounding radius.)
-void sgk_default_camera(const SgKinHost& K, double* cam) {
-  std::vector<double> body;
-  sgk_host_fk(K, &body);
-  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, rb = 0;
-  for (int g = 0; g < K.o.ngeom; g++) {
-    if ((K.ints[K.o.gmeta + g] & 0xFF) == SGR_PLANE) continue;   // (rb too: a plane's bounding radius is 0 or infinite)
-    double gx[3], gm[9];
-    sgk_geom(K.dbl.data(), K.ints.data(), K.o, &body[7 * K.ints[K.o.gbody + g]], g, gx, gm);
-    for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], gx[k]); hi[k] = std::max(hi[k], gx[k]); }
-    rb = std::max(rb, K.rbound[g]);
-  }
-  if (!(lo[0] <= hi[0])) { lo[0] = lo[1] = lo[2] = hi[0] = hi[1] = hi[2] = 0; }
-  double hd = 0;
-  for (int k = 0; k < 3; k++) { cam[k] = 0.5 * (lo[k] + hi[k]); hd += 0.25 * (hi[k] - lo[k]) * (hi[k] - lo[k]); }
-  cam[3] = 2.0 * (sqrt(hd) + rb);
-  if (!(cam[3] > 0)) cam[3] = 1.0;
-  cam[4] = 90.0; cam[5] = -30.0; cam[6] = 45.0;
-}
-
-void sgc_from_blob(const void* blob, size_t nbytes, const SgKinHost& K, SgConHost* C) {
-  if (!K.ok) { C->err = K.err; return; }
-  long long c = 0;
-  const long long nb = K.o.nbody, ng = K.o.ngeom;
-  SG_FIELD(C, par, "body_parentid", SG_DT_I32, nb);
-  SG_FIELD(C, weld, "body_weldid", SG_DT_I32, nb);
-  SG_FIELD(C, gadr, "body_geomadr", SG_DT_I32, nb);
-  SG_FIELD(C, gnum, "body_geomnum", SG_DT_I32, nb);
-  SG_FIELD(C, gbody, "geom_bodyid", SG_DT_I32, ng);
-  SG_FIELD(C, gtype, "geom_type", SG_DT_I32, ng);
-  SG_FIELD(C, ctype, "geom_contype", SG_DT_I32, ng);
-  SG_FIELD(C, caff, "geom_conaffinity", SG_DT_I32, ng);
-  SG_FIELD(C, gmargin, "geom_margin", SG_DT_F64, ng);
-  SG_FIELD(C, grb, "geom_rbound", SG_DT_F64, ng);
-  const int* oi = (const int*)sg_blob_find(blob, nbytes, "opt_i", SG_DT_I32, &c);
-  if (!oi || c < 2) { C->err = "model blob lacks opt_i"; return; }
-  C->cap = sgc_cap(oi[1]);
-  if (!sgc_build_pairs((int)nb, (int)ng, par, weld, gadr, gnum, gbody, gtype, ctype, caff, &C->pairs, &C->err)) return;
-  C->gaux.resize(2 * ng);
-  for (int g = 0; g < ng; g++) { C->gaux[2 * g] = gmargin[g]; C->gaux[2 * g + 1] = grb[g]; }
-  C->ok = true;
-}
-
-// the dynamics table (sg_dyn.h): per body mass, body_ipos, body_imat; per joint its dof, qpos_spring and stiffness; per dof the armature;
-// the sites, the tendons and their wraps; gravity.  Tendons of joint wraps only or of site wraps only: the class the blob allows
-void sgd_build(const void* blob, size_t nbytes, const SgKinHost& K, SgDynHost* T) {
-  if (!K.ok) { T->err = K.err; return; }
-  const long long nb = K.o.nbody, nj = K.o.njnt, nq = K.o.nq;
-  long long c = 0, nv = 0, ns = 0, nt = 0, nw = 0;
-  if (nb > SGD_MAXBODY) { T->err = "more than " + std::to_string(SGD_MAXBODY) + " bodies"; return; }
-  SG_FIELD(T, mass, "body_mass", SG_DT_F64, nb);
-  SG_FIELD(T, ipos, "body_ipos", SG_DT_F64, 3 * nb);
-  SG_FIELD(T, imat, "body_imat", SG_DT_F64, 9 * nb);
-  SG_FIELD(T, jstiff, "jnt_stiffness", SG_DT_F64, nj);
-  SG_FIELD(T, qspring, "qpos_spring", SG_DT_F64, nq);
-  SG_FIELD(T, arm, "dof_armature", SG_DT_F64, -1);
-  nv = c;
-  SG_FIELD(T, sbody, "site_bodyid", SG_DT_I32, -1);
-  ns = c;
-  SG_FIELD(T, spos, "site_pos", SG_DT_F64, 3 * ns);
-  SG_FIELD(T, tadr, "tendon_adr", SG_DT_I32, -1);
-  nt = c;
-  SG_FIELD(T, tnum, "tendon_num", SG_DT_I32, nt);
-  SG_FIELD(T, tstiff, "tendon_stiffness", SG_DT_F64, nt);
-  SG_FIELD(T, tspring, "tendon_lengthspring", SG_DT_F64, nt);
-  SG_FIELD(T, wtype, "wrap_type", SG_DT_I32, -1);
-  nw = c;
-  SG_FIELD(T, wobj, "wrap_objid", SG_DT_I32, nw);
-  SG_FIELD(T, wprm, "wrap_prm", SG_DT_F64, nw);
-  SG_FIELD(T, optd, "opt_d", SG_DT_F64, -1);
-  if (c < 4) { T->err = "model blob lacks opt_d"; return; }
-  long long ca = 0;
-  const int* dadr = (const int*)sg_blob_find(blob, nbytes, "jnt_dofadr", SG_DT_I32, &ca);   // (only blobs with a free joint carry it)
-  if (dadr && ca != nj) dadr = nullptr;
-  const int* jtype = K.ints.data() + K.o.jtype;
-  std::vector<int> jd(nj);
-  std::vector<double> jspring(nj);
-  for (int j = 0; j < nj; j++) {
-    jd[j] = dadr ? dadr[j] : j;
-    if (jd[j] < 0 || jd[j] + (jtype[j] == SG_JNT_FREE ? 6 : 1) > nv) { T->err = "joint dof address out of range"; return; }
-    jspring[j] = qspring[K.ints[K.o.jqadr + j]];
-  }
-  for (int s = 0; s < ns; s++)
-    if (sbody[s] < 0 || sbody[s] >= nb) { T->err = "site body out of range"; return; }
-  for (int t = 0; t < nt; t++) {
-    if (tadr[t] < 0 || tnum[t] < 1 || (long long)tadr[t] + tnum[t] > nw) { T->err = "tendon wrap address out of range"; return; }
-    const int type = wtype[tadr[t]];
-    if (type != SG_WRAP_JOINT && type != SG_WRAP_SITE) { T->err = "tendon wraps other than joints and sites"; return; }
-    for (int w = tadr[t]; w < tadr[t] + tnum[t]; w++) {
-      if (wtype[w] != type) { T->err = "a tendon that mixes joint and site wraps"; return; }
-      if (wobj[w] < 0 || wobj[w] >= (type == SG_WRAP_JOINT ? nj : ns)) { T->err = "tendon wrap object out of range"; return; }
-      if (type == SG_WRAP_JOINT && jtype[wobj[w]] == SG_JNT_FREE) { T->err = "a fixed tendon over a free joint"; return; }
-    }
-  }
-  SgDynOff& o = T->o;
-  o.nv = (int)nv; o.nsite = (int)ns; o.ntendon = (int)nt; o.nwrap = (int)nw;
-  std::vector<double>& D = T->dbl;
-  auto putd = [&](const double* p, size_t n) { int at = (int)D.size(); D.insert(D.end(), p, p + n); return at; };
-  o.bmass = putd(mass, nb); o.bipos = putd(ipos, 3 * nb); o.bimat = putd(imat, 9 * nb); o.jspring = putd(jspring.data(), nj);
-  o.jstiff = putd(jstiff, nj); o.arm = putd(arm, nv); o.spos = putd(spos, 3 * ns); o.wprm = putd(wprm, nw); o.tstiff = putd(tstiff, nt);
-  o.tspring = putd(tspring, nt); o.grav = putd(optd + 1, 3);
-  std::vector<int>& I = T->ints;
-  auto puti = [&](const int* p, size_t n) { int at = (int)I.size(); I.insert(I.end(), p, p + n); return at; };
-  o.jdof = puti(jd.data(), nj); o.sbody = puti(sbody, ns); o.tadr = puti(tadr, nt); o.tnum = puti(tnum, nt); o.wtype = puti(wtype, nw);
-  o.wobj = puti(wobj, nw);
-  if (I.empty()) I.push_back(0);   // (a model without joints, sites and tendons: the upload still has something to hold)
-  T->ok = true;
-}
-
-// the smooth table (sg_smooth.h): per dof its damping, its body and its parent dof (the dof before it on the same body, else the last dof
-// of the nearest ancestor that has one, else -1); per tendon its damping; the actuators on their tendons; the bodies' child lists
-void sgs_build(const void* blob, size_t nbytes, const SgKinHost& K, const SgDynHost& Dn, SgSmoothHost* T) {
-  if (!K.ok) { T->err = K.err; return; }
-  if (K.o.nbody > SGS_MAXBODY) { T->err = "more than " + std::to_string(SGS_MAXBODY) + " bodies"; return; }
-  if (!Dn.ok) { T->err = Dn.err; return; }
-  const long long nb = K.o.nbody, nv = Dn.o.nv, nt = Dn.o.ntendon;
-  if (nv > SGS_MAXDOF) { T->err = "more than " + std::to_string(SGS_MAXDOF) + " dofs"; return; }
-  if (nt > SGS_MAXTENDON) { T->err = "more than " + std::to_string(SGS_MAXTENDON) + " tendons"; return; }
-  long long c = 0, nu = 0;
-  SG_FIELD(T, ddamp, "dof_damping", SG_DT_F64, nv);
-  SG_FIELD(T, tdamp, "tendon_damping", SG_DT_F64, nt);
-  SG_FIELD(T, atrn, "actuator_trnid", SG_DT_I32, -1);
-  nu = c;
-  SG_FIELD(T, again, "actuator_gain", SG_DT_F64, nu);
-  SG_FIELD(T, abias, "actuator_bias", SG_DT_F64, 3 * nu);
-  SG_FIELD(T, agear, "actuator_gear", SG_DT_F64, nu);
-  for (int u = 0; u < nu; u++)
-    if (atrn[u] < 0 || atrn[u] >= nt) { T->err = "actuator tendon out of range"; return; }
-  const int *par = K.ints.data() + K.o.bpar, *jadr = K.ints.data() + K.o.bjadr, *jnum = K.ints.data() + K.o.bjnum, *jtype = K.ints.data() + K.o.jtype;
-  const int* jdof = Dn.ints.data() + Dn.o.jdof;
-  std::vector<int> dbody(nv, -1), dpar(nv, -1), last(nb, -1);   // last[i]: the last dof of body i or of its nearest ancestor with one
-  for (int i = 1; i < nb; i++) {
-    last[i] = last[par[i]];
-    for (int j = jadr[i]; j < jadr[i] + jnum[i]; j++)
-      for (int e = 0; e < (jtype[j] == SG_JNT_FREE ? 6 : 1); e++) {
-        const int dof = jdof[j] + e;
-        if (dbody[dof] >= 0) { T->err = "two joints share a dof"; return; }
-        if (last[i] >= dof) { T->err = "dofs must follow the order of the bodies and their joints"; return; }
-        dbody[dof] = i; dpar[dof] = last[i]; last[i] = dof;
-      }
-  }
-  for (int i = 0; i < nv; i++)
-    if (dbody[i] < 0) { T->err = "a dof without a joint"; return; }
-  std::vector<int> cstart(nb + 1, 0), child;
-  for (int i = 0; i < nb; i++) {
-    cstart[i] = (int)child.size();
-    for (int k = i + 1; k < nb; k++)
-      if (par[k] == i) child.push_back(k);
-  }
-  cstart[nb] = (int)child.size();
-  SgSmoothOff& o = T->o;
-  o.nu = (int)nu; o.nspatial = 0;
-  for (int t = 0; t < nt; t++) o.nspatial += Dn.ints[Dn.o.wtype + Dn.ints[Dn.o.tadr + t]] == SG_WRAP_SITE;
-  std::vector<double>& D = T->dbl;
-  auto putd = [&](const double* p, size_t n) { int at = (int)D.size(); D.insert(D.end(), p, p + n); return at; };
-  o.ddamp = putd(ddamp, nv); o.tdamp = putd(tdamp, nt); o.again = putd(again, nu); o.abias = putd(abias, 3 * nu); o.agear = putd(agear, nu);
-  if (D.empty()) D.push_back(0.0);
-  std::vector<int>& I = T->ints;
-  auto puti = [&](const int* p, size_t n) { int at = (int)I.size(); I.insert(I.end(), p, p + n); return at; };
-  o.dbody = puti(dbody.data(), nv); o.dpar = puti(dpar.data(), nv); o.atrn = puti(atrn, nu); o.cstart = puti(cstart.data(), nb + 1);
-  o.child = puti(child.data(), child.size());
-  T->ok = true;
-}
-
-// the point table (sg_point.h): per body where it enters the dof-parent chain, per dof its parent dof; and the model's sites for
-// sg_model_sites.  Its own walk over the bodies, as the smooth table's limits (bodies, tendons) are not the point read-outs'
-void sgp_build(const void* blob, size_t nbytes, const SgKinHost& K, const SgDynHost& Dn, SgPointHost* T) {
-  if (!K.ok) { T->err = K.err; return; }
-  if (!Dn.ok) { T->err = Dn.err; return; }
-  const long long nb = K.o.nbody, nv = Dn.o.nv, ns = Dn.o.nsite;
-  if (nb > SGP_MAXBODY) { T->err = "more than " + std::to_string(SGP_MAXBODY) + " bodies"; return; }
-  if (nv > SGP_MAXDOF) { T->err = "more than " + std::to_string(SGP_MAXDOF) + " dofs"; return; }
-  long long c = 0;
-  SG_FIELD(T, squat, "site_quat", SG_DT_F64, 4 * ns);
-  const int *par = K.ints.data() + K.o.bpar, *jadr = K.ints.data() + K.o.bjadr, *jnum = K.ints.data() + K.o.bjnum, *jtype = K.ints.data() + K.o.jtype;
-  const int* jdof = Dn.ints.data() + Dn.o.jdof;
-  std::vector<int> bdof(nb, -1), dpar(nv, -2);
-  for (int i = 1; i < nb; i++) {
-    bdof[i] = bdof[par[i]];
-    for (int j = jadr[i]; j < jadr[i] + jnum[i]; j++)
-      for (int e = 0; e < (jtype[j] == SG_JNT_FREE ? 6 : 1); e++) {
-        const int dof = jdof[j] + e;
-        if (dpar[dof] != -2) { T->err = "two joints share a dof"; return; }
-        if (bdof[i] >= dof) { T->err = "dofs must follow the order of the bodies and their joints"; return; }
-        dpar[dof] = bdof[i]; bdof[i] = dof;
-      }
-  }
-  for (int i = 0; i < nv; i++)
-    if (dpar[i] == -2) { T->err = "a dof without a joint"; return; }
-  std::vector<int>& I = T->ints;
-  auto puti = [&](const int* p, size_t n) { int at = (int)I.size(); I.insert(I.end(), p, p + n); return at; };
-  T->o.bdof = puti(bdof.data(), nb); T->o.dpar = puti(dpar.data(), nv);
-  T->site_body.assign(Dn.ints.begin() + Dn.o.sbody, Dn.ints.begin() + Dn.o.sbody + ns);
-  T->site_pos.assign(Dn.dbl.begin() + Dn.o.spos, Dn.dbl.begin() + Dn.o.spos + 3 * ns);
-  T->site_quat.assign(squat, squat + 4 * ns);
-  T->ok = true;
-}
-
 // ---- the entry points' common prologue ----
 // One read-out call on stream s: prepare() puts the kinematics table on the batch's device and the listed env ids (host array,
-// range-checked here) in a device buffer, reserve() grows a scratch buffer of the batch, kin() launches sg_kin_kernel over the listed envs.
+// range-checked here) in a device buffer, need_*() the further tables the call's kernel reads -- each with the tables it is built on, so a
+// new read-out family declares what it needs in one line --, reserve() grows a scratch buffer of the batch, grant_lds() lets a kernel ask
+// for more than 64 KB of LDS, tables_*() fill the table part of an argument struct, kin() launches sg_kin_kernel over the listed envs.
 // Every message carries fn, the calling entry point's name.
 struct Readout {
   sg_batch* b;
@@ -349,14 +40,7 @@ struct Readout {
         if (env_ids[i] < 0 || env_ids[i] >= b->n)
           return fail(SG_ERR_INVALID, std::string(fn) + ": env id " + std::to_string(env_ids[i]) + " out of range [0, " + std::to_string(b->n) + ")");
     HIPCHK(hipSetDevice(b->device));
-    if (!b->kin_d) {   // built on the side: the batch sees the tables only once both are filled
-      SgArena A;
-      double* d = nullptr;
-      int* ip = nullptr;
-      if (!(A.upload(&d, K.dbl) && A.upload(&ip, K.ints))) return devmem_fail(A.nomem, std::string(fn) + " (pose tables)");
-      A.give_to(b->mem);
-      b->kin_d = d; b->kin_i = ip;
-    }
+    if (int rc = need(b->kin, &K.dbl, &K.ints, "pose tables")) return rc;
     n_ids = n;
     if (env_ids) {
       if (int rc = reserve(b->kin_ids, n, "env ids")) return rc;
@@ -371,10 +55,66 @@ struct Readout {
     return buf.reserve(count, s) ? SG_OK : devmem_fail(buf.nomem, std::string(fn) + " (" + what + ")");
   }
 
+  // a table on the batch's device, uploaded at its first use (on the side: the batch sees it only once every section is up)
+  int need(SgDevTable& t, const std::vector<double>* dbl, const std::vector<int>* ints, const char* what) {
+    return t.ensure(b->mem, dbl, ints) ? SG_OK : devmem_fail(t.nomem, std::string(fn) + " (" + what + ")");
+  }
+  int need_con() { return need(b->con, &b->m->con.gaux, &b->m->con.pairs, "pair tables"); }
+  int need_dyn() { return need(b->dyn, &b->m->dyn.dbl, &b->m->dyn.ints, "dynamics tables"); }
+  int need_smooth() {
+    if (int rc = need_dyn()) return rc;
+    return need(b->smooth, &b->m->smooth.dbl, &b->m->smooth.ints, "smooth tables");
+  }
+  // (the row of zeros counts as part of the table that asks for it)
+  int need_zero(const char* what) {
+    if (b->zero.d) return SG_OK;
+    const std::vector<double> zeros(std::max(b->m->dyn.o.nv, 1), 0.0);
+    return need(b->zero, &zeros, nullptr, what);
+  }
+  int need_point() {
+    if (int rc = need_dyn()) return rc;
+    if (int rc = need(b->point, nullptr, &b->m->point.ints, "point table")) return rc;
+    return need_zero("point table");
+  }
+  int need_solve() {
+    if (int rc = need_smooth()) return rc;
+    if (int rc = need(b->solve, nullptr, &b->m->solve.ints, "solve table")) return rc;
+    return need_zero("solve table");
+  }
+
+  // once per batch (so per device): a launch's dynamic LDS above 64 KB must be granted to the kernel first
+  template <class Kernel>
+  int grant_lds(bool& granted, Kernel kernel, size_t bytes) {
+    if (granted) return SG_OK;
+    HIPCHK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    granted = true;
+    return SG_OK;
+  }
+
+  // the table part of a kernel's argument struct, one level per table the struct is built on
+  template <class Args>
+  void tables_kin(Args& a) const { a.D = b->kin.d; a.I = b->kin.i; a.o = b->m->kin.o; }
+  template <class Args>
+  void tables_dyn(Args& a) const { tables_kin(a); a.DD = b->dyn.d; a.DI = b->dyn.i; a.d = b->m->dyn.o; }
+  template <class Args>
+  void tables_smooth(Args& a) const { tables_dyn(a); a.SD = b->smooth.d; a.SI = b->smooth.i; a.s = b->m->smooth.o; }
+
+  // the points of a call (host arrays: body ids, positions, with quat quaternions) on the device, copied on the stream: ids holds the
+  // body ids, d the positions [n][3] and, from 3 n on, the quaternions [n][4]; room: doubles of d per point
+  int stage_points(SgScratch<int>& ids, SgScratch<double>& d, int room, int n, const int32_t* body, const double* pos, const double* quat) {
+    if (int rc = reserve(ids, (size_t)n, "point body ids")) return rc;
+    if (int rc = reserve(d, (size_t)room * n, "points")) return rc;
+    HIPCHK(hipMemcpyAsync(ids.p, body, sizeof(int) * n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d.p, pos, sizeof(double) * 3 * n, hipMemcpyHostToDevice, s));
+    if (quat) HIPCHK(hipMemcpyAsync(d.p + 3 * (size_t)n, quat, sizeof(double) * 4 * n, hipMemcpyHostToDevice, s));
+    return SG_OK;
+  }
+
   int kin(double* xpos, double* xquat, double* gxpos, double* gxmat, float* recs, const double* eye) {
     const SgKinHost& K = b->m->kin;
     SgKinArgs a;
-    a.D = b->kin_d; a.I = b->kin_i; a.o = K.o; a.qpos = b->qpos; a.env_ids = dids; a.n_ids = n_ids;
+    tables_kin(a);
+    a.qpos = b->qpos; a.env_ids = dids; a.n_ids = n_ids;
     a.xpos = xpos; a.xquat = xquat; a.gxpos = gxpos; a.gxmat = gxmat; a.recs = recs;
     for (int c = 0; c < 3; c++) a.eye[c] = eye ? eye[c] : 0.0;
     hipLaunchKernelGGL(sg_kin_kernel, dim3(n_ids), dim3(64), sizeof(double) * 7 * K.o.nbody, s, a);
@@ -567,25 +307,17 @@ int sg_get_contacts(sg_batch* b, const int32_t* env_ids, int n_ids, int max_cont
   Readout r{b, "sg_get_contacts", (hipStream_t)stream};
   if (int rc = r.prepare(env_ids, n_ids)) return rc;
   if (!ncon && !geom && !dist && !pos && !frame) return SG_OK;
-  if (!b->con_pairs) {   // (on the side, as the pose tables)
-    SgArena A;
-    int* dp = nullptr;
-    double* dg = nullptr;
-    if (!(A.upload(&dp, Cn.pairs) && A.upload(&dg, Cn.gaux))) return devmem_fail(A.nomem, "sg_get_contacts (pair tables)");
-    A.give_to(b->mem);
-    b->con_pairs = dp; b->con_gaux = dg;
-  }
+  if (int rc = r.need_con()) return rc;
   const size_t npose = sgc_pose_doubles(K.o);
   const size_t lds = sizeof(double) * (SGC_FIXED_DBL + npose);
   const bool in_lds = lds <= 159 * 1024;   // (the kernel has 256 B of static LDS besides; the CU has 160 KB)
   if (!in_lds)
     if (int rc = r.reserve(b->con_scratch, (size_t)n_ids * npose, "pose blocks")) return rc;
-  if (in_lds && !b->con_attr_set) {   // per device, as the solver kernels' attribute; what this model's launches ask for (above 64 KB it must be granted)
-    HIPCHK(hipFuncSetAttribute((const void*)sg_contacts_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    b->con_attr_set = true;
-  }
+  if (in_lds)   // (what this model's launches ask for)
+    if (int rc = r.grant_lds(b->con_attr_set, sg_contacts_kernel<true>, lds)) return rc;
   SgConArgs a;
-  a.D = b->kin_d; a.I = b->kin_i; a.o = K.o; a.gaux = b->con_gaux; a.pairs = b->con_pairs; a.npair = (int)(Cn.pairs.size() / 2); a.cap = Cn.cap;
+  r.tables_kin(a);
+  a.gaux = b->con.d; a.pairs = b->con.i; a.npair = (int)(Cn.pairs.size() / 2); a.cap = Cn.cap;
   a.qpos = b->qpos; a.env_ids = r.dids; a.n_ids = n_ids; a.max_contacts = max_contacts;
   a.ncon = ncon; a.geom = geom; a.dist = dist; a.pos = pos; a.frame = frame; a.scratch = in_lds ? nullptr : b->con_scratch.p;
   if (in_lds) hipLaunchKernelGGL(sg_contacts_kernel<true>, dim3(n_ids), dim3(64), lds, r.s, a);
@@ -637,7 +369,7 @@ int sg_ray(sg_batch* b, const int32_t* env_ids, int n_ids, int n_rays, const dou
   if (ray_exclude) HIPCHK(hipMemcpyAsync(b->ray_ids.p + n_rays, ray_exclude, sizeof(int) * n_rays, hipMemcpyHostToDevice, r.s));
   if (int rc = r.kin(b->ray_xpos.p, b->ray_xquat.p, b->ray_gxpos.p, b->ray_gxmat.p, nullptr, nullptr)) return rc;
   SgRayArgs a;
-  a.D = b->kin_d; a.I = b->kin_i; a.gsize = K.o.gsize; a.gmeta = K.o.gmeta; a.gbody = K.o.gbody; a.ngeom = K.o.ngeom; a.nbody = K.o.nbody;
+  a.D = b->kin.d; a.I = b->kin.i; a.gsize = K.o.gsize; a.gmeta = K.o.gmeta; a.gbody = K.o.gbody; a.ngeom = K.o.ngeom; a.nbody = K.o.nbody;
   a.xpos = b->ray_xpos.p; a.xquat = b->ray_xquat.p; a.gxpos = b->ray_gxpos.p; a.gxmat = b->ray_gxmat.p;
   a.origin = origin; a.dir = dir;
   a.ray_body = ray_body ? b->ray_ids.p : nullptr; a.ray_exclude = ray_exclude ? b->ray_ids.p + n_rays : nullptr;
@@ -675,6 +407,40 @@ int sg_ray(sg_batch* b, const int32_t* env_ids, int n_ids, int n_rays, const dou
   return SG_OK;
 }
 
+// ---- checks the dyn, smooth, point and solve read-outs share ----
+// the blob's counts against the plan header's, which the batch's state is laid out by: COUNTS_POINT the strides of qpos / qvel; COUNTS_DYN
+// the masks' lengths too; COUNTS_SMOOTH the stride of act too -> what differs, in the words of that level, or NULL
+enum { COUNTS_POINT, COUNTS_DYN, COUNTS_SMOOTH };
+static const char* counts_differ(const sg_model* m, int level) {
+  const SgPlanHeader& H = m->plan.h;
+  bool differ = m->dyn.o.nv != H.nv || m->kin.o.nq != H.nq;
+  if (level >= COUNTS_DYN) differ = differ || m->kin.o.njnt != H.njnt || m->dyn.o.ntendon != H.ntendon;
+  if (level >= COUNTS_SMOOTH) differ = differ || m->smooth.o.nu != H.nu;
+  static const char* const words[] = {"the blob's position or dof counts differ from the plan's", "the blob's joint, dof or tendon counts differ from the plan's",
+                                      "the blob's joint, dof, tendon or actuator counts differ from the plan's"};
+  return differ ? words[level] : nullptr;
+}
+
+// the points of a call, point by point: the body id in range (where the model has a kinematics table), pt_pos finite, then pt_quat
+// (NULL: the call takes none) finite and of a length that can be normalised -> SG_OK, or the first fault under the prefix f
+static int check_points(const std::string& f, const SgKinHost& K, int n_pts, const int32_t* pt_body, const double* pt_pos, const double* pt_quat) {
+  for (int p = 0; p < n_pts; p++) {
+    if (K.ok && (pt_body[p] < 0 || pt_body[p] >= K.o.nbody))
+      return fail(SG_ERR_INVALID, f + "body id " + std::to_string(pt_body[p]) + " of point " + std::to_string(p) + " outside [0, " + std::to_string(K.o.nbody) + ")");
+    for (int c = 0; c < 3; c++)
+      if (!std::isfinite(pt_pos[3 * p + c])) return fail(SG_ERR_INVALID, f + "pt_pos of point " + std::to_string(p) + " is not finite");
+    if (pt_quat) {
+      double n2 = 0.0;
+      for (int c = 0; c < 4; c++) {
+        if (!std::isfinite(pt_quat[4 * p + c])) return fail(SG_ERR_INVALID, f + "pt_quat of point " + std::to_string(p) + " is not finite");
+        n2 += pt_quat[4 * p + c] * pt_quat[4 * p + c];
+      }
+      if (!(n2 > 0.0) || !std::isfinite(n2)) return fail(SG_ERR_INVALID, f + "pt_quat of point " + std::to_string(p) + " has zero length (or overflows)");
+    }
+  }
+  return SG_OK;
+}
+
 // ---- velocity, tendon and energy read-outs: one walk (sg_dyn_kernel), whichever outputs the entry point fn passes ----
 static int dyn(const char* fn, sg_batch* b, const int32_t* env_ids, int n_ids, double* ang, double* lin, double* com_lin, double* ten_len, double* ten_vel,
                double* energy, void* stream) {
@@ -683,23 +449,14 @@ static int dyn(const char* fn, sg_batch* b, const int32_t* env_ids, int n_ids, d
   if (!b) return fail(SG_ERR_INVALID, std::string(fn) + ": null batch");
   const SgKinHost& K = b->m->kin;
   const SgDynHost& Dn = b->m->dyn;
-  const SgPlanHeader& H = b->m->plan.h;
   if (K.ok && !Dn.ok) return fail(SG_ERR_MODEL, std::string(fn) + ": " + Dn.err);
-  if (K.ok && (Dn.o.nv != H.nv || K.o.nq != H.nq || K.o.njnt != H.njnt || Dn.o.ntendon != H.ntendon))   // (the strides of qpos / qvel and the masks' lengths)
-    return fail(SG_ERR_MODEL, std::string(fn) + ": the blob's joint, dof or tendon counts differ from the plan's");
+  if (const char* what = K.ok ? counts_differ(b->m, COUNTS_DYN) : nullptr) return fail(SG_ERR_MODEL, std::string(fn) + ": " + what);
   Readout r{b, fn, (hipStream_t)stream};
   if (int rc = r.prepare(env_ids, n_ids)) return rc;
   if (!ang && !lin && !com_lin && !ten_len && !ten_vel && !energy) return SG_OK;
-  if (!b->dyn_d) {   // (on the side, as the pose tables)
-    SgArena A;
-    double* dd = nullptr;
-    int* di = nullptr;
-    if (!(A.upload(&dd, Dn.dbl) && A.upload(&di, Dn.ints))) return devmem_fail(A.nomem, std::string(fn) + " (dynamics tables)");
-    A.give_to(b->mem);
-    b->dyn_d = dd; b->dyn_i = di;
-  }
+  if (int rc = r.need_dyn()) return rc;
   SgDynArgs a;
-  a.D = b->kin_d; a.I = b->kin_i; a.o = K.o; a.DD = b->dyn_d; a.DI = b->dyn_i; a.d = Dn.o;
+  r.tables_dyn(a);
   a.qpos = b->qpos; a.qvel = b->qvel; a.kenv = b->kenv; a.kmask_jnt = b->kmask_jnt; a.kmask_ten = b->kmask_ten;
   a.env_ids = r.dids; a.n_ids = n_ids;
   a.ang = ang; a.lin = lin; a.com_lin = com_lin; a.ten_len = ten_len; a.ten_vel = ten_vel; a.energy = energy;
@@ -728,37 +485,17 @@ static int smooth(const char* fn, sg_batch* b, const int32_t* env_ids, int n_ids
   const SgKinHost& K = b->m->kin;
   const SgDynHost& Dn = b->m->dyn;
   const SgSmoothHost& Sm = b->m->smooth;
-  const SgPlanHeader& H = b->m->plan.h;
   if (K.ok && !Sm.ok) return fail(SG_ERR_MODEL, std::string(fn) + ": " + Sm.err);
-  if (K.ok && (Dn.o.nv != H.nv || K.o.nq != H.nq || K.o.njnt != H.njnt || Dn.o.ntendon != H.ntendon || Sm.o.nu != H.nu))   // (the strides of qpos / qvel / act and the masks' lengths)
-    return fail(SG_ERR_MODEL, std::string(fn) + ": the blob's joint, dof, tendon or actuator counts differ from the plan's");
+  if (const char* what = K.ok ? counts_differ(b->m, COUNTS_SMOOTH) : nullptr) return fail(SG_ERR_MODEL, std::string(fn) + ": " + what);
   Readout r{b, fn, (hipStream_t)stream};
   if (int rc = r.prepare(env_ids, n_ids)) return rc;
   if (!M && !bias && !passive && !actuator && !inverse) return SG_OK;
-  if (!b->dyn_d) {   // (on the side, as the pose tables)
-    SgArena A;
-    double* dd = nullptr;
-    int* di = nullptr;
-    if (!(A.upload(&dd, Dn.dbl) && A.upload(&di, Dn.ints))) return devmem_fail(A.nomem, std::string(fn) + " (dynamics tables)");
-    A.give_to(b->mem);
-    b->dyn_d = dd; b->dyn_i = di;
-  }
-  if (!b->smooth_d) {
-    SgArena A;
-    double* sd = nullptr;
-    int* si = nullptr;
-    if (!(A.upload(&sd, Sm.dbl) && A.upload(&si, Sm.ints))) return devmem_fail(A.nomem, std::string(fn) + " (smooth tables)");
-    A.give_to(b->mem);
-    b->smooth_d = sd; b->smooth_i = si;
-  }
+  if (int rc = r.need_smooth()) return rc;
   // nbody <= SGS_MAXBODY, nv <= SGS_MAXDOF, ntendon <= SGS_MAXTENDON (sgs_build): with the kernel's static LDS within SGS_LDS_MAX
   const size_t lds = sizeof(double) * ((size_t)SGS_REC * K.o.nbody + (size_t)SGS_DOF * Dn.o.nv + 2 * (size_t)Dn.o.ntendon);
-  if (!b->smooth_attr_set) {   // per device, as the contact read-out's attribute: above 64 KB the launch's dynamic LDS must be granted
-    HIPCHK(hipFuncSetAttribute((const void*)sg_smooth_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SGS_LDS_MAX - SGS_STATIC_LDS));
-    b->smooth_attr_set = true;
-  }
+  if (int rc = r.grant_lds(b->smooth_attr_set, sg_smooth_kernel, SGS_LDS_MAX - SGS_STATIC_LDS)) return rc;
   SgSmoothArgs a;
-  a.D = b->kin_d; a.I = b->kin_i; a.o = K.o; a.DD = b->dyn_d; a.DI = b->dyn_i; a.d = Dn.o; a.SD = b->smooth_d; a.SI = b->smooth_i; a.s = Sm.o;
+  r.tables_smooth(a);
   a.qpos = b->qpos; a.qvel = b->qvel; a.act = b->act; a.kenv = b->kenv; a.kmask_jnt = b->kmask_jnt; a.kmask_ten = b->kmask_ten;
   a.env_ids = r.dids; a.n_ids = n_ids;
   a.M = M; a.bias = bias; a.passive = passive; a.actuator = actuator; a.qacc = qacc; a.inverse = inverse;
@@ -790,59 +527,22 @@ static int point(const char* fn, sg_batch* b, const int32_t* env_ids, int n_ids,
   const SgKinHost& K = b->m->kin;
   const SgDynHost& Dn = b->m->dyn;
   const SgPointHost& Pt = b->m->point;
-  const SgPlanHeader& H = b->m->plan.h;
-  for (int p = 0; p < n_pts; p++) {
-    if (K.ok && (pt_body[p] < 0 || pt_body[p] >= K.o.nbody))
-      return fail(SG_ERR_INVALID, f + "body id " + std::to_string(pt_body[p]) + " of point " + std::to_string(p) + " outside [0, " + std::to_string(K.o.nbody) + ")");
-    for (int c = 0; c < 3; c++)
-      if (!std::isfinite(pt_pos[3 * p + c])) return fail(SG_ERR_INVALID, f + "pt_pos of point " + std::to_string(p) + " is not finite");
-    if (pt_quat) {
-      double n2 = 0.0;
-      for (int c = 0; c < 4; c++) {
-        if (!std::isfinite(pt_quat[4 * p + c])) return fail(SG_ERR_INVALID, f + "pt_quat of point " + std::to_string(p) + " is not finite");
-        n2 += pt_quat[4 * p + c] * pt_quat[4 * p + c];
-      }
-      if (!(n2 > 0.0) || !std::isfinite(n2)) return fail(SG_ERR_INVALID, f + "pt_quat of point " + std::to_string(p) + " has zero length (or overflows)");
-    }
-  }
+  if (int rc = check_points(f, K, n_pts, pt_body, pt_pos, pt_quat)) return rc;
   if (K.ok && !Pt.ok) return fail(SG_ERR_MODEL, f + Pt.err);
-  if (K.ok && (Dn.o.nv != H.nv || K.o.nq != H.nq))   // (the strides of qpos / qvel)
-    return fail(SG_ERR_MODEL, f + "the blob's position or dof counts differ from the plan's");
+  if (const char* what = K.ok ? counts_differ(b->m, COUNTS_POINT) : nullptr) return fail(SG_ERR_MODEL, f + what);
   if ((long long)n_ids * n_pts > 0x7fffffffll) return fail(SG_ERR_INVALID, f + "too many envs x points for one launch");
   Readout r{b, fn, (hipStream_t)stream};
   if (int rc = r.prepare(env_ids, n_ids)) return rc;
   if (!pos && !mat && !vel && !acc && !gyro && !accel && !jacp && !jacr) return SG_OK;
-  if (!b->dyn_d) {   // (on the side, as the pose tables)
-    SgArena A;
-    double* dd = nullptr;
-    int* di = nullptr;
-    if (!(A.upload(&dd, Dn.dbl) && A.upload(&di, Dn.ints))) return devmem_fail(A.nomem, std::string(fn) + " (dynamics tables)");
-    A.give_to(b->mem);
-    b->dyn_d = dd; b->dyn_i = di;
-  }
-  if (!b->point_i) {   // the point table, and a row of nv zeros: the qvel the Jacobian-only call walks at
-    SgArena A;
-    int* pi = nullptr;
-    double* z = nullptr;
-    if (!(A.upload(&pi, Pt.ints) && A.upload(&z, std::vector<double>(Dn.o.nv > 0 ? Dn.o.nv : 1, 0.0)))) return devmem_fail(A.nomem, std::string(fn) + " (point table)");
-    A.give_to(b->mem);
-    b->point_i = pi; b->point_zero = z;
-  }
+  if (int rc = r.need_point()) return rc;   // (with the row of zeros: the qvel the Jacobian-only call walks at)
   // nbody <= SGP_MAXBODY, nv <= SGP_MAXDOF (sgp_build): with the kernel's static LDS within SGP_LDS_MAX
   const size_t lds = sizeof(double) * ((size_t)SGP_REC * K.o.nbody + (size_t)SGP_DOF * Dn.o.nv) + sizeof(int) * (size_t)Dn.o.nv;
-  if (!b->point_attr_set) {   // per device, as the smooth read-out's attribute: above 64 KB the launch's dynamic LDS must be granted
-    HIPCHK(hipFuncSetAttribute((const void*)sg_point_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SGP_LDS_MAX - SGP_STATIC_LDS));
-    b->point_attr_set = true;
-  }
-  // the points: host arrays, read here and copied on the stream
-  if (int rc = r.reserve(b->pt_ids, (size_t)n_pts, "point body ids")) return rc;
-  if (int rc = r.reserve(b->pt_d, 7 * (size_t)n_pts, "points")) return rc;
-  HIPCHK(hipMemcpyAsync(b->pt_ids.p, pt_body, sizeof(int) * n_pts, hipMemcpyHostToDevice, r.s));
-  HIPCHK(hipMemcpyAsync(b->pt_d.p, pt_pos, sizeof(double) * 3 * n_pts, hipMemcpyHostToDevice, r.s));
-  if (pt_quat) HIPCHK(hipMemcpyAsync(b->pt_d.p + 3 * (size_t)n_pts, pt_quat, sizeof(double) * 4 * n_pts, hipMemcpyHostToDevice, r.s));
+  if (int rc = r.grant_lds(b->point_attr_set, sg_point_kernel, SGP_LDS_MAX - SGP_STATIC_LDS)) return rc;
+  if (int rc = r.stage_points(b->pt_ids, b->pt_d, 7, n_pts, pt_body, pt_pos, pt_quat)) return rc;
   SgPointArgs a;
-  a.D = b->kin_d; a.I = b->kin_i; a.o = K.o; a.DD = b->dyn_d; a.DI = b->dyn_i; a.d = Dn.o; a.PI = b->point_i; a.p = Pt.o;
-  a.qpos = qpos ? qpos : b->qpos; a.qvel = !use_qvel ? b->point_zero : qvel ? qvel : b->qvel; a.qacc = qacc;
+  r.tables_dyn(a);
+  a.PI = b->point.i; a.p = Pt.o;
+  a.qpos = qpos ? qpos : b->qpos; a.qvel = !use_qvel ? b->zero.d : qvel ? qvel : b->qvel; a.qacc = qacc;
   a.given = (qpos ? 1 : 0) | (use_qvel ? (qvel ? 2 : 0) : 4);
   a.env_ids = r.dids; a.n_ids = n_ids; a.n_pts = n_pts;
   a.pt_body = b->pt_ids.p; a.pt_pos = b->pt_d.p; a.pt_quat = pt_quat ? b->pt_d.p + 3 * (size_t)n_pts : nullptr;
@@ -877,65 +577,27 @@ static int solve(const char* fn, int mode, sg_batch* b, const int32_t* env_ids, 
   if (mode == SGV_MODE_POINT && (!pt_body || !pt_pos)) return fail(SG_ERR_INVALID, f + "null pt_body or pt_pos");
   const SgKinHost& K = b->m->kin;
   const SgDynHost& Dn = b->m->dyn;
-  const SgSmoothHost& Sm = b->m->smooth;
   const SgSolveHost& Sv = b->m->solve;
-  const SgPlanHeader& H = b->m->plan.h;
   if (mode == SGV_MODE_POINT)
-    for (int p = 0; p < n_rhs; p++) {
-      if (K.ok && (pt_body[p] < 0 || pt_body[p] >= K.o.nbody))
-        return fail(SG_ERR_INVALID, f + "body id " + std::to_string(pt_body[p]) + " of point " + std::to_string(p) + " outside [0, " + std::to_string(K.o.nbody) + ")");
-      for (int c = 0; c < 3; c++)
-        if (!std::isfinite(pt_pos[3 * p + c])) return fail(SG_ERR_INVALID, f + "pt_pos of point " + std::to_string(p) + " is not finite");
-    }
+    if (int rc = check_points(f, K, n_rhs, pt_body, pt_pos, nullptr)) return rc;
   if (K.ok && !Sv.ok) return fail(SG_ERR_MODEL, f + Sv.err);
-  if (K.ok && (Dn.o.nv != H.nv || K.o.nq != H.nq || K.o.njnt != H.njnt || Dn.o.ntendon != H.ntendon || Sm.o.nu != H.nu))   // (the strides of qpos / qvel / act and the masks' lengths)
-    return fail(SG_ERR_MODEL, f + "the blob's joint, dof, tendon or actuator counts differ from the plan's");
+  if (const char* what = K.ok ? counts_differ(b->m, COUNTS_SMOOTH) : nullptr) return fail(SG_ERR_MODEL, f + what);
   if ((long long)n_ids * n_rhs > 0x7fffffffll / 36) return fail(SG_ERR_INVALID, f + "too many envs x right-hand sides or points for one launch");
   Readout r{b, fn, (hipStream_t)stream};
   if (int rc = r.prepare(env_ids, n_ids)) return rc;
   if (!x && !qacc && !qfrc && !W && !pivot) return SG_OK;
-  if (!b->dyn_d) {   // (on the side, as the pose tables)
-    SgArena A;
-    double* dd = nullptr;
-    int* di = nullptr;
-    if (!(A.upload(&dd, Dn.dbl) && A.upload(&di, Dn.ints))) return devmem_fail(A.nomem, std::string(fn) + " (dynamics tables)");
-    A.give_to(b->mem);
-    b->dyn_d = dd; b->dyn_i = di;
-  }
-  if (!b->smooth_d) {
-    SgArena A;
-    double* sd = nullptr;
-    int* si = nullptr;
-    if (!(A.upload(&sd, Sm.dbl) && A.upload(&si, Sm.ints))) return devmem_fail(A.nomem, std::string(fn) + " (smooth tables)");
-    A.give_to(b->mem);
-    b->smooth_d = sd; b->smooth_i = si;
-  }
-  if (!b->solve_i) {   // the solve table, and a row of nv zeros: the qvel the calls that need M alone walk at
-    SgArena A;
-    int* vi = nullptr;
-    double* z = nullptr;
-    if (!(A.upload(&vi, Sv.ints) && A.upload(&z, std::vector<double>(Dn.o.nv, 0.0)))) return devmem_fail(A.nomem, std::string(fn) + " (solve table)");
-    A.give_to(b->mem);
-    b->solve_i = vi; b->solve_zero = z;
-  }
+  if (int rc = r.need_solve()) return rc;   // (with the row of zeros: the qvel the calls that need M alone walk at)
   // a tile of SGV_MINRHS right-hand sides fits beside the fixed block (sgv_build); the launch asks for the tile it uses, no more
   const long long fixed = sgv_fixed_doubles(K.o.nbody, Dn.o.nv, Dn.o.ntendon, Sv.o.nM), room = sgv_tile(K.o.nbody, Dn.o.nv, Dn.o.ntendon, Sv.o.nM);
   const int tile = mode == SGV_MODE_FORWARD ? 1 : (int)std::min<long long>(n_rhs, mode == SGV_MODE_POINT ? room / 6 : room);
   const size_t lds = sizeof(double) * ((size_t)fixed + (size_t)tile * (mode == SGV_MODE_POINT ? 6 : 1) * Dn.o.nv);
-  if (!b->solve_attr_set) {   // per device, as the smooth read-out's attribute: above 64 KB the launch's dynamic LDS must be granted
-    HIPCHK(hipFuncSetAttribute((const void*)sg_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SGV_LDS_MAX - SGV_STATIC_LDS));
-    b->solve_attr_set = true;
-  }
-  if (mode == SGV_MODE_POINT) {   // the points: host arrays, read here and copied on the stream
-    if (int rc = r.reserve(b->sv_ids, (size_t)n_rhs, "point body ids")) return rc;
-    if (int rc = r.reserve(b->sv_pos, 3 * (size_t)n_rhs, "points")) return rc;
-    HIPCHK(hipMemcpyAsync(b->sv_ids.p, pt_body, sizeof(int) * n_rhs, hipMemcpyHostToDevice, r.s));
-    HIPCHK(hipMemcpyAsync(b->sv_pos.p, pt_pos, sizeof(double) * 3 * n_rhs, hipMemcpyHostToDevice, r.s));
-  }
+  if (int rc = r.grant_lds(b->solve_attr_set, sg_solve_kernel, SGV_LDS_MAX - SGV_STATIC_LDS)) return rc;
+  if (mode == SGV_MODE_POINT)
+    if (int rc = r.stage_points(b->sv_ids, b->sv_pos, 3, n_rhs, pt_body, pt_pos, nullptr)) return rc;
   SgSolveArgs a;
-  a.D = b->kin_d; a.I = b->kin_i; a.o = K.o; a.DD = b->dyn_d; a.DI = b->dyn_i; a.d = Dn.o; a.SD = b->smooth_d; a.SI = b->smooth_i; a.s = Sm.o;
-  a.VI = b->solve_i; a.v = Sv.o;
-  a.qpos = b->qpos; a.qvel = b->qvel; a.act = b->act; a.kenv = b->kenv; a.zero = b->solve_zero; a.kmask_jnt = b->kmask_jnt; a.kmask_ten = b->kmask_ten;
+  r.tables_smooth(a);
+  a.VI = b->solve.i; a.v = Sv.o;
+  a.qpos = b->qpos; a.qvel = b->qvel; a.act = b->act; a.kenv = b->kenv; a.zero = b->zero.d; a.kmask_jnt = b->kmask_jnt; a.kmask_ten = b->kmask_ten;
   a.env_ids = r.dids; a.n_ids = n_ids; a.mode = mode; a.n_rhs = mode == SGV_MODE_FORWARD ? 1 : n_rhs; a.tile = tile;
   a.y = y; a.x = x; a.applied = applied; a.qacc = qacc; a.qfrc = qfrc;
   a.pt_body = mode == SGV_MODE_POINT ? b->sv_ids.p : nullptr; a.pt_pos = mode == SGV_MODE_POINT ? b->sv_pos.p : nullptr; a.W = W; a.pivot = pivot;

@@ -117,9 +117,9 @@ inline void sgv_build(int nbody, const int* bpar, int nv, const int* dbody, cons
   SgSolveOff& o = V->o;
   o.nM = (int)nM; o.nlevel = nlevel;
   std::vector<int>& I = V->ints;
-  auto puti = [&](const std::vector<int>& p) { int at = (int)I.size(); I.insert(I.end(), p.begin(), p.end()); return at; };
-  o.depth = puti(depth); o.rstart = puti(rstart); o.anc = puti(anc); o.erow = puti(erow); o.lstart = puti(lstart); o.ldof = puti(ldof);
-  o.elstart = puti(elstart); o.eidx = puti(eidx); o.dstart = puti(dstart); o.desc = puti(desc); o.doff = puti(doff); o.drow = puti(drow); o.bdof = puti(bdof);
+  o.depth = sg_put(I, depth); o.rstart = sg_put(I, rstart); o.anc = sg_put(I, anc); o.erow = sg_put(I, erow); o.lstart = sg_put(I, lstart);
+  o.ldof = sg_put(I, ldof); o.elstart = sg_put(I, elstart); o.eidx = sg_put(I, eidx); o.dstart = sg_put(I, dstart); o.desc = sg_put(I, desc);
+  o.doff = sg_put(I, doff); o.drow = sg_put(I, drow); o.bdof = sg_put(I, bdof);
   V->ok = true;
 }
 

@@ -1,0 +1,321 @@
+// sg_tables.cpp -- the host builders of the read-outs' per-model tables, which sg_model_create (sg_api.hip) calls: kinematics and contact
+// pairs (sg_readout.h), dynamics (sg_dyn.h), smooth (sg_smooth.h) and point (sg_point.h); sg_solve.h builds its own from these.  Plain
+// host C++ without a HIP call: every variant of the library links it, and the host tests compile it with g++ (tests/emu/sg_tables_dump.cpp,
+// tests/test_tables_host.py, scripts/sanitize/host_main.cpp).  Every builder either sets ok or leaves a message in err.
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>   // (the library's build compiles every source as HIP: the shared headers' __forceinline__)
+#endif
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "sg_blob.h"   // sg_blob_find: the one (bounds-checked) reader of the model blob
+#include "sg_point.h"  // (sg_smooth.h, sg_dyn.h, sg_readout.h)
+
+// ---- the builders sg_model_create calls (sg_readout.h) ----
+// an array of the blob as `var`, its length in c (want >= 0: that many elements), or the builder ends with T->err set
+#define SG_FIELD(T, var, name, dt, want)                                                                                 \
+  const auto* var = (const std::conditional<dt == SG_DT_F64, double, int>::type*)sg_blob_find(blob, nbytes, name, dt, &c); \
+  if (!var || (want >= 0 && c != want)) { T->err = std::string("model blob lacks ") + name; return; }
+
+// the kinematics table: per body its parent, body_pos, body_quat and joints; per joint type, jnt_pos, jnt_axis, qposadr, qpos0; per geom body,
+// geom_pos, geom_quat (as a matrix), geom_size, geom_type, geom_rbound and a category from the plan; the bodies' depth-level schedule
+void sgk_build(const void* blob, size_t nbytes, const SgPlan& plan, const SgTreeDev* tree, bool fast, SgKinHost* K) {
+  long long nb = 0, nj = 0, ng = 0, nq = 0, c = 0;
+  SG_FIELD(K, par, "body_parentid", SG_DT_I32, -1);
+  nb = c;
+  SG_FIELD(K, bpos, "body_pos", SG_DT_F64, 3 * nb);
+  SG_FIELD(K, bquat, "body_quat", SG_DT_F64, 4 * nb);
+  SG_FIELD(K, jadr, "body_jntadr", SG_DT_I32, nb);
+  SG_FIELD(K, jnum, "body_jntnum", SG_DT_I32, nb);
+  SG_FIELD(K, jtype, "jnt_type", SG_DT_I32, -1);
+  nj = c;
+  SG_FIELD(K, jpos, "jnt_pos", SG_DT_F64, 3 * nj);
+  SG_FIELD(K, jaxis, "jnt_axis", SG_DT_F64, 3 * nj);
+  SG_FIELD(K, q0, "qpos0", SG_DT_F64, -1);
+  nq = c;
+  SG_FIELD(K, gtype, "geom_type", SG_DT_I32, -1);
+  ng = c;
+  SG_FIELD(K, gbody, "geom_bodyid", SG_DT_I32, ng);
+  SG_FIELD(K, gpos, "geom_pos", SG_DT_F64, 3 * ng);
+  SG_FIELD(K, gquat, "geom_quat", SG_DT_F64, 4 * ng);
+  SG_FIELD(K, gsize, "geom_size", SG_DT_F64, 3 * ng);
+  SG_FIELD(K, grb, "geom_rbound", SG_DT_F64, ng);
+  long long ca = 0;
+  const int* qadr = (const int*)sg_blob_find(blob, nbytes, "jnt_qposadr", SG_DT_I32, &ca);   // (only blobs with a free joint carry it)
+  if (qadr && ca != nj) qadr = nullptr;
+  if (nb < 1 || nb > 1024) { K->err = "the kinematic tree has more than 1024 bodies"; return; }
+  // checks: parents before children, joint / position addresses in range
+  std::vector<int> depth(nb, 0);
+  for (int i = 1; i < nb; i++) {
+    if (par[i] < 0 || par[i] >= i) { K->err = "body parents must precede their children"; return; }
+    depth[i] = depth[par[i]] + 1;
+    if (jnum[i] < 0 || (jnum[i] > 0 && (jadr[i] < 0 || jadr[i] + jnum[i] > nj))) { K->err = "joint address out of range"; return; }
+  }
+  for (int j = 0; j < nj; j++) {
+    const int qa = qadr ? qadr[j] : j;
+    if (qa < 0 || qa + (jtype[j] == SG_JNT_FREE ? 7 : 1) > nq) { K->err = "joint position address out of range"; return; }
+    if (jtype[j] != SG_JNT_FREE && jtype[j] != SG_JNT_SLIDE && jtype[j] != SG_JNT_HINGE) { K->err = "unsupported joint type"; return; }
+  }
+  for (int g = 0; g < ng; g++)
+    if (gbody[g] < 0 || gbody[g] >= nb) { K->err = "geom body out of range"; return; }
+  // categories from the plan
+  std::vector<int> cat(ng, SGR_CAT_STATIC);
+  if (plan.h.plane_geom >= 0 && plan.h.plane_geom < ng) cat[plan.h.plane_geom] = SGR_CAT_GROUND;
+  for (int g : plan.elem_geom)
+    if (g >= 0 && g < ng) cat[g] = SGR_CAT_ELEM;
+  if (fast)
+    for (int ch = 0; ch < plan.h.nchain; ch++)
+      for (int k = 0; k < plan.h.chain[ch].ngeom; k++) cat[plan.h.chain[ch].g_id[k]] = SGR_CAT_FINGER;
+  if (tree)
+    for (int k = 0; k < tree->NG; k++) cat[tree->g_id[k]] = SGR_CAT_FINGER;
+  if (plan.h.has_center && plan.h.center_geom >= 0 && plan.h.center_geom < ng) cat[plan.h.center_geom] = SGR_CAT_CENTER;
+  // level schedule (level 0 = the world body)
+  int nlevel = 0;
+  for (int i = 0; i < nb; i++) nlevel = std::max(nlevel, depth[i] + 1);
+  std::vector<int> lstart(nlevel + 1, 0), lbody;
+  for (int L = 0; L < nlevel; L++) {
+    lstart[L] = (int)lbody.size();
+    for (int i = 0; i < nb; i++)
+      if (depth[i] == L) lbody.push_back(i);
+  }
+  lstart[nlevel] = (int)lbody.size();
+  SgKinOff& o = K->o;
+  o.nbody = (int)nb; o.ngeom = (int)ng; o.njnt = (int)nj; o.nq = (int)nq; o.nlevel = nlevel;
+  std::vector<double>& D = K->dbl;
+  o.bpos = sg_put(D, bpos, 3 * nb); o.bquat = sg_put(D, bquat, 4 * nb); o.jpos = sg_put(D, jpos, 3 * nj); o.jaxis = sg_put(D, jaxis, 3 * nj);
+  std::vector<double> jq0(nj);
+  for (int j = 0; j < nj; j++) jq0[j] = q0[qadr ? qadr[j] : j];
+  o.jq0 = sg_put(D, jq0);
+  o.gpos = sg_put(D, gpos, 3 * ng);
+  std::vector<double> gm(9 * ng);
+  for (int g = 0; g < ng; g++) sgk_quat_mat(&gm[9 * g], gquat + 4 * g);
+  o.gmat = sg_put(D, gm);
+  o.gsize = sg_put(D, gsize, 3 * ng);
+  std::vector<int>& I = K->ints;
+  o.bpar = sg_put(I, par, nb); o.bjadr = sg_put(I, jadr, nb); o.bjnum = sg_put(I, jnum, nb); o.jtype = sg_put(I, jtype, nj);
+  std::vector<int> qa(nj), meta(ng);
+  for (int j = 0; j < nj; j++) qa[j] = qadr ? qadr[j] : j;
+  o.jqadr = sg_put(I, qa);
+  o.gbody = sg_put(I, gbody, ng);
+  for (int g = 0; g < ng; g++) {
+    meta[g] = (gtype[g] & 0xFF) | (cat[g] << 8);
+    if (K->bad_type < 0 && gtype[g] != SGR_PLANE && gtype[g] != SGR_SPHERE && gtype[g] != SGR_CAPSULE && gtype[g] != SGR_BOX) K->bad_type = gtype[g];
+  }
+  o.gmeta = sg_put(I, meta);
+  o.lstart = sg_put(I, lstart);
+  o.lbody = sg_put(I, lbody);
+  K->qpos0.assign(q0, q0 + nq);
+  K->rbound.assign(grb, grb + ng);
+  K->ok = true;
+}
+
+void sgk_host_fk(const SgKinHost& K, std::vector<double>* body) {
+  const SgKinOff& o = K.o;
+  body->assign((size_t)o.nbody * 7, 0.0);
+  (*body)[3] = 1.0;
+  for (int i = 1; i < o.nbody; i++) {   // (parents precede children)
+    const int p = K.ints[o.bpar + i];
+    sgk_body(K.dbl.data(), K.ints.data(), o, K.qpos0.data(), i, &(*body)[7 * p], &(*body)[7 * p + 3], &(*body)[7 * i]);
+  }
+}
+
+// the default free camera: lookat = centre of the bounding box of the non-plane geoms' centres at qpos0, distance = 2 x (its
+// half-diagonal + the largest bounding radius of those geoms), azimuth 90, elevation -30, fovy 45.  (1.5 x half-diagonal + radius cuts
+// the near finger off at the image border in every committed scene: the gripper's base box alone has a 1.36 m bounding radius.)
+void sgk_default_camera(const SgKinHost& K, double* cam) {
+  std::vector<double> body;
+  sgk_host_fk(K, &body);
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, rb = 0;
+  for (int g = 0; g < K.o.ngeom; g++) {
+    if ((K.ints[K.o.gmeta + g] & 0xFF) == SGR_PLANE) continue;   // (rb too: a plane's bounding radius is 0 or infinite)
+    double gx[3], gm[9];
+    sgk_geom(K.dbl.data(), K.ints.data(), K.o, &body[7 * K.ints[K.o.gbody + g]], g, gx, gm);
+    for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], gx[k]); hi[k] = std::max(hi[k], gx[k]); }
+    rb = std::max(rb, K.rbound[g]);
+  }
+  if (!(lo[0] <= hi[0])) { lo[0] = lo[1] = lo[2] = hi[0] = hi[1] = hi[2] = 0; }
+  double hd = 0;
+  for (int k = 0; k < 3; k++) { cam[k] = 0.5 * (lo[k] + hi[k]); hd += 0.25 * (hi[k] - lo[k]) * (hi[k] - lo[k]); }
+  cam[3] = 2.0 * (sqrt(hd) + rb);
+  if (!(cam[3] > 0)) cam[3] = 1.0;
+  cam[4] = 90.0; cam[5] = -30.0; cam[6] = 45.0;
+}
+
+void sgc_from_blob(const void* blob, size_t nbytes, const SgKinHost& K, SgConHost* C) {
+  if (!K.ok) { C->err = K.err; return; }
+  long long c = 0;
+  const long long nb = K.o.nbody, ng = K.o.ngeom;
+  SG_FIELD(C, par, "body_parentid", SG_DT_I32, nb);
+  SG_FIELD(C, weld, "body_weldid", SG_DT_I32, nb);
+  SG_FIELD(C, gadr, "body_geomadr", SG_DT_I32, nb);
+  SG_FIELD(C, gnum, "body_geomnum", SG_DT_I32, nb);
+  SG_FIELD(C, gbody, "geom_bodyid", SG_DT_I32, ng);
+  SG_FIELD(C, gtype, "geom_type", SG_DT_I32, ng);
+  SG_FIELD(C, ctype, "geom_contype", SG_DT_I32, ng);
+  SG_FIELD(C, caff, "geom_conaffinity", SG_DT_I32, ng);
+  SG_FIELD(C, gmargin, "geom_margin", SG_DT_F64, ng);
+  SG_FIELD(C, grb, "geom_rbound", SG_DT_F64, ng);
+  const int* oi = (const int*)sg_blob_find(blob, nbytes, "opt_i", SG_DT_I32, &c);
+  if (!oi || c < 2) { C->err = "model blob lacks opt_i"; return; }
+  C->cap = sgc_cap(oi[1]);
+  if (!sgc_build_pairs((int)nb, (int)ng, par, weld, gadr, gnum, gbody, gtype, ctype, caff, &C->pairs, &C->err)) return;
+  C->gaux.resize(2 * ng);
+  for (int g = 0; g < ng; g++) { C->gaux[2 * g] = gmargin[g]; C->gaux[2 * g + 1] = grb[g]; }
+  C->ok = true;
+}
+
+// the dynamics table (sg_dyn.h): per body mass, body_ipos, body_imat; per joint its dof, qpos_spring and stiffness; per dof the armature;
+// the sites, the tendons and their wraps; gravity.  Tendons of joint wraps only or of site wraps only: the class the blob allows
+void sgd_build(const void* blob, size_t nbytes, const SgKinHost& K, SgDynHost* T) {
+  if (!K.ok) { T->err = K.err; return; }
+  const long long nb = K.o.nbody, nj = K.o.njnt, nq = K.o.nq;
+  long long c = 0, nv = 0, ns = 0, nt = 0, nw = 0;
+  if (nb > SGD_MAXBODY) { T->err = "more than " + std::to_string(SGD_MAXBODY) + " bodies"; return; }
+  SG_FIELD(T, mass, "body_mass", SG_DT_F64, nb);
+  SG_FIELD(T, ipos, "body_ipos", SG_DT_F64, 3 * nb);
+  SG_FIELD(T, imat, "body_imat", SG_DT_F64, 9 * nb);
+  SG_FIELD(T, jstiff, "jnt_stiffness", SG_DT_F64, nj);
+  SG_FIELD(T, qspring, "qpos_spring", SG_DT_F64, nq);
+  SG_FIELD(T, arm, "dof_armature", SG_DT_F64, -1);
+  nv = c;
+  SG_FIELD(T, sbody, "site_bodyid", SG_DT_I32, -1);
+  ns = c;
+  SG_FIELD(T, spos, "site_pos", SG_DT_F64, 3 * ns);
+  SG_FIELD(T, tadr, "tendon_adr", SG_DT_I32, -1);
+  nt = c;
+  SG_FIELD(T, tnum, "tendon_num", SG_DT_I32, nt);
+  SG_FIELD(T, tstiff, "tendon_stiffness", SG_DT_F64, nt);
+  SG_FIELD(T, tspring, "tendon_lengthspring", SG_DT_F64, nt);
+  SG_FIELD(T, wtype, "wrap_type", SG_DT_I32, -1);
+  nw = c;
+  SG_FIELD(T, wobj, "wrap_objid", SG_DT_I32, nw);
+  SG_FIELD(T, wprm, "wrap_prm", SG_DT_F64, nw);
+  SG_FIELD(T, optd, "opt_d", SG_DT_F64, -1);
+  if (c < 4) { T->err = "model blob lacks opt_d"; return; }
+  long long ca = 0;
+  const int* dadr = (const int*)sg_blob_find(blob, nbytes, "jnt_dofadr", SG_DT_I32, &ca);   // (only blobs with a free joint carry it)
+  if (dadr && ca != nj) dadr = nullptr;
+  const int* jtype = K.ints.data() + K.o.jtype;
+  std::vector<int> jd(nj);
+  std::vector<double> jspring(nj);
+  for (int j = 0; j < nj; j++) {
+    jd[j] = dadr ? dadr[j] : j;
+    if (jd[j] < 0 || jd[j] + (jtype[j] == SG_JNT_FREE ? 6 : 1) > nv) { T->err = "joint dof address out of range"; return; }
+    jspring[j] = qspring[K.ints[K.o.jqadr + j]];
+  }
+  for (int s = 0; s < ns; s++)
+    if (sbody[s] < 0 || sbody[s] >= nb) { T->err = "site body out of range"; return; }
+  for (int t = 0; t < nt; t++) {
+    if (tadr[t] < 0 || tnum[t] < 1 || (long long)tadr[t] + tnum[t] > nw) { T->err = "tendon wrap address out of range"; return; }
+    const int type = wtype[tadr[t]];
+    if (type != SG_WRAP_JOINT && type != SG_WRAP_SITE) { T->err = "tendon wraps other than joints and sites"; return; }
+    for (int w = tadr[t]; w < tadr[t] + tnum[t]; w++) {
+      if (wtype[w] != type) { T->err = "a tendon that mixes joint and site wraps"; return; }
+      if (wobj[w] < 0 || wobj[w] >= (type == SG_WRAP_JOINT ? nj : ns)) { T->err = "tendon wrap object out of range"; return; }
+      if (type == SG_WRAP_JOINT && jtype[wobj[w]] == SG_JNT_FREE) { T->err = "a fixed tendon over a free joint"; return; }
+    }
+  }
+  SgDynOff& o = T->o;
+  o.nv = (int)nv; o.nsite = (int)ns; o.ntendon = (int)nt; o.nwrap = (int)nw;
+  std::vector<double>& D = T->dbl;
+  o.bmass = sg_put(D, mass, nb); o.bipos = sg_put(D, ipos, 3 * nb); o.bimat = sg_put(D, imat, 9 * nb); o.jspring = sg_put(D, jspring);
+  o.jstiff = sg_put(D, jstiff, nj); o.arm = sg_put(D, arm, nv); o.spos = sg_put(D, spos, 3 * ns); o.wprm = sg_put(D, wprm, nw); o.tstiff = sg_put(D, tstiff, nt);
+  o.tspring = sg_put(D, tspring, nt); o.grav = sg_put(D, optd + 1, 3);
+  std::vector<int>& I = T->ints;
+  o.jdof = sg_put(I, jd); o.sbody = sg_put(I, sbody, ns); o.tadr = sg_put(I, tadr, nt); o.tnum = sg_put(I, tnum, nt); o.wtype = sg_put(I, wtype, nw);
+  o.wobj = sg_put(I, wobj, nw);
+  if (I.empty()) I.push_back(0);   // (a model without joints, sites and tendons: the upload still has something to hold)
+  T->ok = true;
+}
+
+// the dof-parent chain of a model, from the bodies (bpar, bjadr, bjnum), their joints (jtype) and the joints' dofs (jdof): per dof its body
+// and its parent dof (the dof before it on the same body, else the last dof of the nearest ancestor that has one, else -1), per body the
+// last dof at or above it (-1: none).  The smooth and the point table are both cut from it.  false: *err says what the dofs break
+struct SgDofChain {
+  std::vector<int> dbody, dpar, last;
+};
+static bool sg_dof_chain(const SgKinHost& K, const SgDynHost& Dn, SgDofChain* C, std::string* err) {
+  const int nb = K.o.nbody, nv = Dn.o.nv;
+  const int *par = K.ints.data() + K.o.bpar, *jadr = K.ints.data() + K.o.bjadr, *jnum = K.ints.data() + K.o.bjnum, *jtype = K.ints.data() + K.o.jtype;
+  const int* jdof = Dn.ints.data() + Dn.o.jdof;
+  std::vector<int>&dbody = C->dbody, &dpar = C->dpar, &last = C->last;
+  dbody.assign(nv, -1); dpar.assign(nv, -1); last.assign(nb, -1);
+  for (int i = 1; i < nb; i++) {
+    last[i] = last[par[i]];
+    for (int j = jadr[i]; j < jadr[i] + jnum[i]; j++)
+      for (int e = 0; e < (jtype[j] == SG_JNT_FREE ? 6 : 1); e++) {
+        const int dof = jdof[j] + e;
+        if (dbody[dof] >= 0) { *err = "two joints share a dof"; return false; }
+        if (last[i] >= dof) { *err = "dofs must follow the order of the bodies and their joints"; return false; }
+        dbody[dof] = i; dpar[dof] = last[i]; last[i] = dof;
+      }
+  }
+  for (int i = 0; i < nv; i++)
+    if (dbody[i] < 0) { *err = "a dof without a joint"; return false; }
+  return true;
+}
+
+// the smooth table (sg_smooth.h): per dof its damping, its body and its parent dof (the dof before it on the same body, else the last dof
+// of the nearest ancestor that has one, else -1); per tendon its damping; the actuators on their tendons; the bodies' child lists
+void sgs_build(const void* blob, size_t nbytes, const SgKinHost& K, const SgDynHost& Dn, SgSmoothHost* T) {
+  if (!K.ok) { T->err = K.err; return; }
+  if (K.o.nbody > SGS_MAXBODY) { T->err = "more than " + std::to_string(SGS_MAXBODY) + " bodies"; return; }
+  if (!Dn.ok) { T->err = Dn.err; return; }
+  const long long nb = K.o.nbody, nv = Dn.o.nv, nt = Dn.o.ntendon;
+  if (nv > SGS_MAXDOF) { T->err = "more than " + std::to_string(SGS_MAXDOF) + " dofs"; return; }
+  if (nt > SGS_MAXTENDON) { T->err = "more than " + std::to_string(SGS_MAXTENDON) + " tendons"; return; }
+  long long c = 0, nu = 0;
+  SG_FIELD(T, ddamp, "dof_damping", SG_DT_F64, nv);
+  SG_FIELD(T, tdamp, "tendon_damping", SG_DT_F64, nt);
+  SG_FIELD(T, atrn, "actuator_trnid", SG_DT_I32, -1);
+  nu = c;
+  SG_FIELD(T, again, "actuator_gain", SG_DT_F64, nu);
+  SG_FIELD(T, abias, "actuator_bias", SG_DT_F64, 3 * nu);
+  SG_FIELD(T, agear, "actuator_gear", SG_DT_F64, nu);
+  for (int u = 0; u < nu; u++)
+    if (atrn[u] < 0 || atrn[u] >= nt) { T->err = "actuator tendon out of range"; return; }
+  SgDofChain ch;
+  if (!sg_dof_chain(K, Dn, &ch, &T->err)) return;
+  const int* par = K.ints.data() + K.o.bpar;
+  std::vector<int> cstart(nb + 1, 0), child;
+  for (int i = 0; i < nb; i++) {
+    cstart[i] = (int)child.size();
+    for (int k = i + 1; k < nb; k++)
+      if (par[k] == i) child.push_back(k);
+  }
+  cstart[nb] = (int)child.size();
+  SgSmoothOff& o = T->o;
+  o.nu = (int)nu; o.nspatial = 0;
+  for (int t = 0; t < nt; t++) o.nspatial += Dn.ints[Dn.o.wtype + Dn.ints[Dn.o.tadr + t]] == SG_WRAP_SITE;
+  std::vector<double>& D = T->dbl;
+  o.ddamp = sg_put(D, ddamp, nv); o.tdamp = sg_put(D, tdamp, nt); o.again = sg_put(D, again, nu); o.abias = sg_put(D, abias, 3 * nu); o.agear = sg_put(D, agear, nu);
+  if (D.empty()) D.push_back(0.0);
+  std::vector<int>& I = T->ints;
+  o.dbody = sg_put(I, ch.dbody); o.dpar = sg_put(I, ch.dpar); o.atrn = sg_put(I, atrn, nu); o.cstart = sg_put(I, cstart);
+  o.child = sg_put(I, child);
+  T->ok = true;
+}
+
+// the point table (sg_point.h): per body where it enters the dof-parent chain, per dof its parent dof; and the model's sites for
+// sg_model_sites.  The walk is the smooth table's (sg_dof_chain), the limits before it are its own: the smooth table's (bodies, tendons)
+// are not the point read-outs', so a model sgs_build refuses for its size can still have a point table
+void sgp_build(const void* blob, size_t nbytes, const SgKinHost& K, const SgDynHost& Dn, SgPointHost* T) {
+  if (!K.ok) { T->err = K.err; return; }
+  if (!Dn.ok) { T->err = Dn.err; return; }
+  const long long nb = K.o.nbody, nv = Dn.o.nv, ns = Dn.o.nsite;
+  if (nb > SGP_MAXBODY) { T->err = "more than " + std::to_string(SGP_MAXBODY) + " bodies"; return; }
+  if (nv > SGP_MAXDOF) { T->err = "more than " + std::to_string(SGP_MAXDOF) + " dofs"; return; }
+  long long c = 0;
+  SG_FIELD(T, squat, "site_quat", SG_DT_F64, 4 * ns);
+  SgDofChain ch;
+  if (!sg_dof_chain(K, Dn, &ch, &T->err)) return;
+  std::vector<int>& I = T->ints;
+  T->o.bdof = sg_put(I, ch.last); T->o.dpar = sg_put(I, ch.dpar);
+  T->site_body.assign(Dn.ints.begin() + Dn.o.sbody, Dn.ints.begin() + Dn.o.sbody + ns);
+  T->site_pos.assign(Dn.dbl.begin() + Dn.o.spos, Dn.dbl.begin() + Dn.o.spos + 3 * ns);
+  T->site_quat.assign(squat, squat + 4 * ns);
+  T->ok = true;
+}

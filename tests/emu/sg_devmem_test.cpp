@@ -1,5 +1,6 @@
-// Host test of soft-grip_amd/csrc/sg_devmem.h (SgArena, SgScratch) over counting fakes of the five HIP calls it uses: one fixed sequence,
-// run once clean and once with each allocation and each copy failing in turn.  Whatever fails, no block may outlive its owner.
+// Host test of soft-grip_amd/csrc/sg_devmem.h (SgArena, SgScratch, SgDevTable) over counting fakes of the five HIP calls it uses: one fixed
+// sequence, run once clean and once with each allocation and each copy failing in turn; then a table's ensure(), clean and with each
+// section's allocation and copy failing.  Whatever fails, no block may outlive its owner.
 // Driven by tests/test_devmem_host.py; prints a line per run, exit status 0 = every check held.
 #include <cstdio>
 #include <cstdlib>
@@ -111,10 +112,56 @@ static void run(int fail_alloc, int fail_copy) {
   printf("run fail_alloc=%d fail_copy=%d live=%d\n", fail_alloc, fail_copy, g_live);
 }
 
+// SgDevTable::ensure over the same fakes.  fail_alloc / fail_copy: the allocation / copy of the FIRST ensure that fails (0: none)
+static void run_table(int fail_alloc, int fail_copy) {
+  g_live = g_allocs = g_copies = g_syncs = g_empty_requests = 0;
+  g_fail_alloc = fail_alloc; g_fail_copy = fail_copy;
+  {
+    SgArena owner;
+    int* keep = nullptr;
+    CHECK(owner.zeros(&keep, 2));   // (what the batch holds already: allocation 1)
+    const std::vector<double> dbl = {1.5, 2.5, 3.5};
+    const std::vector<int> ints = {7, 8};
+    SgDevTable T;
+    const int allocs0 = g_allocs;
+    const bool ok = T.ensure(owner, &dbl, &ints);
+    CHECK(ok == (!fail_alloc && !fail_copy));
+    if (!ok) {   // the first section is freed, every pointer stays NULL, the owner is as it was
+      CHECK(T.d == nullptr && T.i == nullptr);
+      CHECK(T.nomem == (fail_alloc != 0));
+      CHECK(owner.bufs.size() == 1 && g_live == 1);
+      g_fail_alloc = g_fail_copy = 0;
+      const int allocs1 = g_allocs;
+      CHECK(T.ensure(owner, &dbl, &ints) && !T.nomem);   // a later ensure succeeds
+      CHECK(g_allocs == allocs1 + 2);
+    } else {
+      CHECK(g_allocs == allocs0 + 2);   // one allocation per section
+    }
+    CHECK(T.d && T.i && T.d[0] == 1.5 && T.d[2] == 3.5 && T.i[0] == 7 && T.i[1] == 8);
+    CHECK(owner.bufs.size() == 3 && g_live == 3);   // the owner holds them
+    const int allocs2 = g_allocs, copies2 = g_copies;
+    double* const d = T.d;
+    CHECK(T.ensure(owner, &dbl, &ints) && g_allocs == allocs2 && g_copies == copies2 && T.d == d);   // a second ensure allocates nothing
+    // a table of one section: the other pointer stays NULL, and the table counts as up
+    SgDevTable one;
+    CHECK(one.ensure(owner, nullptr, &ints) && one.d == nullptr && one.i && one.i[1] == 8 && owner.bufs.size() == 4);
+    const int allocs3 = g_allocs;
+    CHECK(one.ensure(owner, nullptr, &ints) && g_allocs == allocs3);
+  }
+  CHECK(g_live == 0);
+  CHECK(g_empty_requests == 0);
+  printf("table fail_alloc=%d fail_copy=%d live=%d\n", fail_alloc, fail_copy, g_live);
+}
+
 int main() {
   run(0, 0);
   for (int k = 1; k <= N_ALLOCS; k++) run(k, 0);
   for (int k = 1; k <= N_COPIES; k++) run(0, k);
+  run_table(0, 0);
+  run_table(2, 0);   // the first section's allocation (allocation 1 is the owner's own block)
+  run_table(3, 0);   // the second section's allocation
+  run_table(0, 1);   // the first section's copy
+  run_table(0, 2);   // the second section's copy
   printf(g_bad ? "FAIL\n" : "PASS\n");
   return g_bad ? 1 : 0;
 }
