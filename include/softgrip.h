@@ -427,6 +427,39 @@ int sg_forward_smooth(sg_batch* b, const int32_t* env_ids, int n_ids, const doub
 int sg_get_point_inertia(sg_batch* b, const int32_t* env_ids, int n_ids, int n_pts, const int32_t* pt_body, const double* pt_pos, double* W, double* pivot,
                          void* stream);
 
+/* ---- constraint and contact forces: replaces reading data.efc_force / data.qfrc_constraint / data.qacc after sim.forward() and
+ * mj_contactForce.  sg_get_forces is mj_forward's constraint stage at the batch's CURRENT state -- qpos, qvel, act, ctrl,
+ * qacc_warmstart and the per-env stiffness, in stream order against sg_set_stiffness and sg_set_state: what the env's next forward pass
+ * will compute (after sg_step: the NEXT pass's forces, as with sg_get_contacts).  It reads the batch and changes nothing in it --
+ * qacc_warmstart is not updated -- and does not synchronise the host.  env_ids as in sg_get_poses (HOST, NULL = all); every other array
+ * is a DEVICE pointer, row k belonging to the k-th listed env, and any may be NULL.
+ * Rows, in mj_makeConstraint's order: equalities by id (one- and two-joint polynomial equalities, tendon equalities); joint limits by
+ * joint id, lower side first, only where dist < margin; contacts in sg_get_contacts' order, only those with dist < includemargin, one
+ * row for condim 1 and three for condim 3 (elliptic cones).  Contact parameters are mixed as mj_contactParam does at equal priority;
+ * impedance, R and the reference acceleration as mj_makeImpedance (refsafe, impratio); njmax and nconmax cut the list as mj_forward does.
+ * The solver is mj_solPGS from mj_forward's warm start, with its early exit.
+ *   nefc, iters, ncon  [n_ids]: rows, sweeps run, contacts.  nefc may exceed max_rows.  nefc = ncon = -1 for an env whose state holds a
+ *                      NaN or inf (or whose mass matrix has a pivot that is not positive): such an env gets NaN in every double output
+ *                      and disturbs no other env
+ *   efc_type, efc_id, efc_force  [n_ids][max_rows]: type 0 equality, 3 limit, 5 frictionless contact, 7 elliptic contact; id the equality,
+ *                      the joint, or the contact's index in sg_get_contacts' list.  Only the first min(nefc, max_rows) are written
+ *   contact_force      [n_ids][max_contacts][3]: the force of contact i of sg_get_contacts' list in that contact's frame, normal first
+ *                      (mj_contactForce's first three numbers): the bits of its efc_force entries; zero for a contact without rows,
+ *                      zero tangential parts for condim 1.  Only the first min(ncon, max_contacts) are written
+ *   qfrc_constraint    [n_ids][nv] = J' f;   qacc [n_ids][nv] = qacc_smooth + M^-1 J' f, data.qacc after mj_forward
+ * sg_model_max_rows: the rows the call reserves per env -- every equality, both sides of every limited joint, three rows per contact
+ * the list can hold (cut by njmax).  The call needs about 2 x that x nv doubles per env (the rows' J and M^-1 J'), so the env list is
+ * processed in chunks, launched in stream order inside a work space that the batch allocates at the first call and that holds at most
+ * sg_set_forces_workspace's bytes (default 256 MiB; SG_ERR_INVALID below one env's need).  No atomics: two calls give the same bits,
+ * and an env's bits depend neither on the chunking, nor on the env list or its order, nor on which outputs are NULL.
+ * SG_ERR_INVALID (checked before anything touches the device): NULL batch, n_ids <= 0, an env id out of range, max_rows <= 0 with a row
+ * array given, max_contacts <= 0 with contact_force given.  SG_ERR_MODEL, with the limit named: a model sg_solve_mass refuses, a condim
+ * other than 1 or 3, an equality that is neither a joint nor a tendon equality, a row list that does not fit the 160 KB of LDS. */
+int sg_get_forces(sg_batch* b, const int32_t* env_ids, int n_ids, int max_rows, int max_contacts, int32_t* nefc, int32_t* iters, int32_t* efc_type,
+                  int32_t* efc_id, double* efc_force, int32_t* ncon, double* contact_force, double* qfrc_constraint, double* qacc, void* stream);
+int sg_model_max_rows(const sg_model* m);
+int sg_set_forces_workspace(sg_batch* b, size_t bytes);
+
 /* The recurrence of one direction of one fp64 LSTM layer with H = 128 hidden units (csrc/sg_lstm.hip), for the Conv-LSTM and
  * Conv-BiLSTM regressors (soft-grip_amd/lstm.py).  Keras' conventions: gate order i, f, g (the candidate), o along the 4H axis, sigmoid
  * for i, f and o, tanh for g and for the cell, row-major kernels.  The caller keeps what is regular -- the input projection

@@ -149,6 +149,7 @@ int sg_model_create(const void* blob, size_t nbytes, sg_model** out) {
   sgs_build(blob, nbytes, m->kin, m->dyn, &m->smooth);
   sgp_build(blob, nbytes, m->kin, m->dyn, &m->point);
   sgv_build(m->kin, m->dyn, m->smooth, &m->solve);
+  sgf_build(blob, nbytes, m->kin, m->con, m->dyn, m->solve, &m->forces);
   m->rounds = (m->plan.h.nelem + 63) / 64;
   if (m->rounds > 4) {
     delete m;

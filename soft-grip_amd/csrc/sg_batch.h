@@ -11,6 +11,7 @@
 #include "sg_smooth.h"
 #include "sg_point.h"
 #include "sg_solve.h"
+#include "sg_forces.h"
 #include "sg_skin.h"
 #include "sg_rows_host.h"   // (sg_work.h, sg_plan.h)
 #include "sg_devmem.h"   // SgArena, SgScratch: the owners of every device buffer below (after the HIP runtime's declarations)
@@ -40,6 +41,7 @@ struct sg_model {
   SgSmoothHost smooth;   // dampers, actuators, child lists and parent dofs of sg_get_mass_matrix / sg_get_joint_forces / sg_inverse_dynamics
   SgPointHost point;     // the dof-parent chain's entries and the sites of sg_get_point_motion / sg_get_jacobians / sg_model_sites
   SgSolveHost solve;     // the packed factor's schedule of sg_solve_mass / sg_forward_smooth / sg_get_point_inertia
+  SgForceHost forces;    // equality records, limited joints, solver parameters and opt's numbers of sg_get_forces
   SgSkinHost skin;  // the composite's skin (sg_skin.h; nvert == 0: none): sg_model_set_skin, drawn by sg_render_ex
 };
 
@@ -98,10 +100,10 @@ struct sg_batch {
   long long prof_pgs_n = 0;
   // ---- the read-outs (sg_readout.hip), everything allocated at first use ----
   // the per-model tables on the batch's device (sg_devmem.h SgDevTable; Readout::need_* in sg_readout.hip brings each up with what it
-  // is built on): kin the kinematics table; con the candidate pairs (i) and the margins / bounding radii (d); dyn, smooth, point and solve
-  // the tables of sg_dyn.h, sg_smooth.h, sg_point.h and sg_solve.h; zero a row of max(nv, 1) zeros, the qvel the point and solve calls
-  // that need none walk at
-  SgDevTable kin, con, dyn, smooth, point, solve, zero;
+  // is built on): kin the kinematics table; con the candidate pairs (i) and the margins / bounding radii (d); dyn, smooth, point, solve
+  // and forces the tables of sg_dyn.h, sg_smooth.h, sg_point.h, sg_solve.h and sg_forces.h; zero a row of max(nv, 1) zeros, the qvel the
+  // point and solve calls that need none walk at
+  SgDevTable kin, con, dyn, smooth, point, solve, forces, zero;
   // pose read-out / renderer
   SgScratch<int> kin_ids;    // the listed env ids on the device
   SgScratch<float> rrecs;    // [n_ids][ngeom][SGR_REC] fp32 geom records of the last sg_render
@@ -130,6 +132,11 @@ struct sg_batch {
   bool solve_attr_set = false;
   SgScratch<int> sv_ids;
   SgScratch<double> sv_pos;
+  // constraint forces (sg_get_forces): the chunk's work space (rows' J and W, scalar records, contact list, row directory), allocated at
+  // the first call and capped at forces_cap bytes (sg_set_forces_workspace; the env list is processed in chunks that fit)
+  SgScratch<double> forces_ws;
+  size_t forces_cap = (size_t)256 << 20;
+  bool forces_rows_attr_set = false, forces_pgs_attr_set = false;
   ~sg_batch() {   // (on the batch's device: sg_batch_destroy.  The arenas and scratch buffers free themselves)
     for (auto& e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (auto& e : ev_pgs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }

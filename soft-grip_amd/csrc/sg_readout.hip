@@ -1,6 +1,6 @@
 // sg_readout.hip -- the read-out half of the C ABI (include/softgrip.h): sg_get_poses, sg_render / sg_render_ex and the skin,
 // sg_get_contacts, sg_ray, sg_get_velocities / sg_get_tendons / sg_get_energy, sg_get_mass_matrix / sg_get_joint_forces /
-// sg_inverse_dynamics, sg_get_point_motion / sg_get_jacobians, sg_solve_mass / sg_forward_smooth / sg_get_point_inertia, with the kernels
+// sg_inverse_dynamics, sg_get_point_motion / sg_get_jacobians, sg_solve_mass / sg_forward_smooth / sg_get_point_inertia, sg_get_forces, with the kernels
 // they launch (the *_kernel*.h files, whose device assembly is sg_readout.device.s).  Entry points and launches only: the host builders of
 // the per-model tables are in sg_tables.cpp (sg_solve.h builds its own), what brings a table to a batch's device is SgDevTable
 // (sg_devmem.h) under Readout::need_*.  None of them writes the state: every pipeline is served.  No CPU fallback.
@@ -16,6 +16,7 @@
 #include "sg_smooth_kernel.h"
 #include "sg_point_kernel.h"
 #include "sg_solve_kernel.h"
+#include "sg_forces_kernel.h"
 
 // ---- the entry points' common prologue ----
 // One read-out call on stream s: prepare() puts the kinematics table on the batch's device and the listed env ids (host array,
@@ -295,18 +296,12 @@ int sg_model_ncollision_pairs(const sg_model* m) {
   return (int)(m->con.pairs.size() / 2);
 }
 
-int sg_get_contacts(sg_batch* b, const int32_t* env_ids, int n_ids, int max_contacts, int32_t* ncon, int32_t* geom, double* dist, double* pos,
-                    double* frame, void* stream) {
-  // (argument checks first, in an order that lets each be reached without a device)
-  if (n_ids <= 0) return fail(SG_ERR_INVALID, "sg_get_contacts: n_ids must be positive");
-  if (max_contacts <= 0 && (geom || dist || pos || frame)) return fail(SG_ERR_INVALID, "sg_get_contacts: max_contacts must be positive when a contact array is given");
-  if (!b) return fail(SG_ERR_INVALID, "sg_get_contacts: null batch");
+// the launch of sg_contacts_kernel over r's listed envs (sg_get_contacts; sg_get_forces for a chunk's list in its work space)
+static int contacts_launch(Readout& r, int max_contacts, int32_t* ncon, int32_t* geom, double* dist, double* pos, double* frame) {
+  sg_batch* b = r.b;
   const SgConHost& Cn = b->m->con;
   const SgKinHost& K = b->m->kin;
-  if (K.ok && !Cn.ok) return fail(SG_ERR_MODEL, "sg_get_contacts: " + Cn.err);
-  Readout r{b, "sg_get_contacts", (hipStream_t)stream};
-  if (int rc = r.prepare(env_ids, n_ids)) return rc;
-  if (!ncon && !geom && !dist && !pos && !frame) return SG_OK;
+  const int n_ids = r.n_ids;
   if (int rc = r.need_con()) return rc;
   const size_t npose = sgc_pose_doubles(K.o);
   const size_t lds = sizeof(double) * (SGC_FIXED_DBL + npose);
@@ -324,6 +319,21 @@ int sg_get_contacts(sg_batch* b, const int32_t* env_ids, int n_ids, int max_cont
   else hipLaunchKernelGGL(sg_contacts_kernel<false>, dim3(n_ids), dim3(64), sizeof(double) * SGC_FIXED_DBL, r.s, a);
   HIPCHK(hipGetLastError());
   return SG_OK;
+}
+
+int sg_get_contacts(sg_batch* b, const int32_t* env_ids, int n_ids, int max_contacts, int32_t* ncon, int32_t* geom, double* dist, double* pos,
+                    double* frame, void* stream) {
+  // (argument checks first, in an order that lets each be reached without a device)
+  if (n_ids <= 0) return fail(SG_ERR_INVALID, "sg_get_contacts: n_ids must be positive");
+  if (max_contacts <= 0 && (geom || dist || pos || frame)) return fail(SG_ERR_INVALID, "sg_get_contacts: max_contacts must be positive when a contact array is given");
+  if (!b) return fail(SG_ERR_INVALID, "sg_get_contacts: null batch");
+  const SgConHost& Cn = b->m->con;
+  const SgKinHost& K = b->m->kin;
+  if (K.ok && !Cn.ok) return fail(SG_ERR_MODEL, "sg_get_contacts: " + Cn.err);
+  Readout r{b, "sg_get_contacts", (hipStream_t)stream};
+  if (int rc = r.prepare(env_ids, n_ids)) return rc;
+  if (!ncon && !geom && !dist && !pos && !frame) return SG_OK;
+  return contacts_launch(r, max_contacts, ncon, geom, dist, pos, frame);
 }
 
 // ---- ray queries ----
@@ -563,6 +573,32 @@ int sg_get_jacobians(sg_batch* b, const int32_t* env_ids, int n_ids, int n_pts, 
                jacp, jacr, false, stream);
 }
 
+// the launch of sg_solve_kernel over r's listed envs in one of its modes (the three entry points below; sg_get_forces for qacc_smooth and
+// for W = M^-1 J' with rhs_count rows per env).  pt_body, pt_pos: the points on the device
+static int solve_launch(Readout& r, int mode, int n_rhs, const double* y, double* x, const int* rhs_count, const double* applied, double* qacc, double* qfrc,
+                        const int* pt_body, const double* pt_pos, double* W, double* pivot) {
+  sg_batch* b = r.b;
+  const SgKinHost& K = b->m->kin;
+  const SgDynHost& Dn = b->m->dyn;
+  const SgSolveHost& Sv = b->m->solve;
+  if (int rc = r.need_solve()) return rc;   // (with the row of zeros: the qvel the calls that need M alone walk at)
+  // a tile of SGV_MINRHS right-hand sides fits beside the fixed block (sgv_build); the launch asks for the tile it uses, no more
+  const long long fixed = sgv_fixed_doubles(K.o.nbody, Dn.o.nv, Dn.o.ntendon, Sv.o.nM), room = sgv_tile(K.o.nbody, Dn.o.nv, Dn.o.ntendon, Sv.o.nM);
+  const int tile = mode == SGV_MODE_FORWARD ? 1 : (int)std::min<long long>(n_rhs, mode == SGV_MODE_POINT ? room / 6 : room);
+  const size_t lds = sizeof(double) * ((size_t)fixed + (size_t)tile * (mode == SGV_MODE_POINT ? 6 : 1) * Dn.o.nv);
+  if (int rc = r.grant_lds(b->solve_attr_set, sg_solve_kernel, SGV_LDS_MAX - SGV_STATIC_LDS)) return rc;
+  SgSolveArgs a;
+  r.tables_smooth(a);
+  a.VI = b->solve.i; a.v = Sv.o;
+  a.qpos = b->qpos; a.qvel = b->qvel; a.act = b->act; a.kenv = b->kenv; a.zero = b->zero.d; a.kmask_jnt = b->kmask_jnt; a.kmask_ten = b->kmask_ten;
+  a.env_ids = r.dids; a.n_ids = r.n_ids; a.mode = mode; a.n_rhs = mode == SGV_MODE_FORWARD ? 1 : n_rhs; a.tile = tile; a.rhs_count = rhs_count;
+  a.y = y; a.x = x; a.applied = applied; a.qacc = qacc; a.qfrc = qfrc;
+  a.pt_body = pt_body; a.pt_pos = pt_pos; a.W = W; a.pivot = pivot;
+  hipLaunchKernelGGL(sg_solve_kernel, dim3(r.n_ids), dim3(64), lds, r.s, a);
+  HIPCHK(hipGetLastError());
+  return SG_OK;
+}
+
 // ---- mass-matrix solves, smooth forward dynamics and point inertias: one kernel (sg_solve_kernel), in the mode of the entry point fn ----
 static int solve(const char* fn, int mode, sg_batch* b, const int32_t* env_ids, int n_ids, int n_rhs, const double* y, double* x, const double* applied,
                  double* qacc, double* qfrc, const int32_t* pt_body, const double* pt_pos, double* W, double* pivot, void* stream) {
@@ -586,24 +622,10 @@ static int solve(const char* fn, int mode, sg_batch* b, const int32_t* env_ids, 
   Readout r{b, fn, (hipStream_t)stream};
   if (int rc = r.prepare(env_ids, n_ids)) return rc;
   if (!x && !qacc && !qfrc && !W && !pivot) return SG_OK;
-  if (int rc = r.need_solve()) return rc;   // (with the row of zeros: the qvel the calls that need M alone walk at)
-  // a tile of SGV_MINRHS right-hand sides fits beside the fixed block (sgv_build); the launch asks for the tile it uses, no more
-  const long long fixed = sgv_fixed_doubles(K.o.nbody, Dn.o.nv, Dn.o.ntendon, Sv.o.nM), room = sgv_tile(K.o.nbody, Dn.o.nv, Dn.o.ntendon, Sv.o.nM);
-  const int tile = mode == SGV_MODE_FORWARD ? 1 : (int)std::min<long long>(n_rhs, mode == SGV_MODE_POINT ? room / 6 : room);
-  const size_t lds = sizeof(double) * ((size_t)fixed + (size_t)tile * (mode == SGV_MODE_POINT ? 6 : 1) * Dn.o.nv);
-  if (int rc = r.grant_lds(b->solve_attr_set, sg_solve_kernel, SGV_LDS_MAX - SGV_STATIC_LDS)) return rc;
   if (mode == SGV_MODE_POINT)
     if (int rc = r.stage_points(b->sv_ids, b->sv_pos, 3, n_rhs, pt_body, pt_pos, nullptr)) return rc;
-  SgSolveArgs a;
-  r.tables_smooth(a);
-  a.VI = b->solve.i; a.v = Sv.o;
-  a.qpos = b->qpos; a.qvel = b->qvel; a.act = b->act; a.kenv = b->kenv; a.zero = b->zero.d; a.kmask_jnt = b->kmask_jnt; a.kmask_ten = b->kmask_ten;
-  a.env_ids = r.dids; a.n_ids = n_ids; a.mode = mode; a.n_rhs = mode == SGV_MODE_FORWARD ? 1 : n_rhs; a.tile = tile;
-  a.y = y; a.x = x; a.applied = applied; a.qacc = qacc; a.qfrc = qfrc;
-  a.pt_body = mode == SGV_MODE_POINT ? b->sv_ids.p : nullptr; a.pt_pos = mode == SGV_MODE_POINT ? b->sv_pos.p : nullptr; a.W = W; a.pivot = pivot;
-  hipLaunchKernelGGL(sg_solve_kernel, dim3(n_ids), dim3(64), lds, r.s, a);
-  HIPCHK(hipGetLastError());
-  return SG_OK;
+  return solve_launch(r, mode, n_rhs, y, x, nullptr, applied, qacc, qfrc, mode == SGV_MODE_POINT ? b->sv_ids.p : nullptr, mode == SGV_MODE_POINT ? b->sv_pos.p : nullptr, W,
+                      pivot);
 }
 
 int sg_solve_mass(sg_batch* b, const int32_t* env_ids, int n_ids, int n_rhs, const double* y, double* x, double* pivot, void* stream) {
@@ -617,6 +639,109 @@ int sg_forward_smooth(sg_batch* b, const int32_t* env_ids, int n_ids, const doub
 int sg_get_point_inertia(sg_batch* b, const int32_t* env_ids, int n_ids, int n_pts, const int32_t* pt_body, const double* pt_pos, double* W, double* pivot,
                          void* stream) {
   return solve("sg_get_point_inertia", SGV_MODE_POINT, b, env_ids, n_ids, n_pts, nullptr, nullptr, nullptr, nullptr, nullptr, pt_body, pt_pos, W, pivot, stream);
+}
+
+// ---- constraint and contact forces: the chunked launch chain of sg_forces_kernel.h ----
+int sg_model_max_rows(const sg_model* m) {
+  if (!m) return fail(SG_ERR_INVALID, "sg_model_max_rows: null model");
+  if (!m->forces.ok) return fail(SG_ERR_MODEL, "sg_model_max_rows: " + m->forces.err);
+  return m->forces.o.nrows;
+}
+
+// one env's share of the work space in bytes (its doubles, then its ints rounded up to whole doubles)
+static size_t forces_env_bytes(const sg_model* m) {
+  return 8 * (sgf_env_doubles(m->forces.o, m->dyn.o.nv) + (sgf_env_ints(m->forces.o) + 1) / 2);
+}
+
+int sg_set_forces_workspace(sg_batch* b, size_t bytes) {
+  if (!b) return fail(SG_ERR_INVALID, "sg_set_forces_workspace: null batch");
+  if (!b->m->forces.ok) return fail(SG_ERR_MODEL, "sg_set_forces_workspace: " + b->m->forces.err);
+  const size_t need = forces_env_bytes(b->m);
+  if (bytes < need) return fail(SG_ERR_INVALID, "sg_set_forces_workspace: " + std::to_string(bytes) + " bytes are below one env's need of " + std::to_string(need));
+  b->forces_cap = bytes;
+  return SG_OK;
+}
+
+int sg_get_forces(sg_batch* b, const int32_t* env_ids, int n_ids, int max_rows, int max_contacts, int32_t* nefc, int32_t* iters, int32_t* efc_type, int32_t* efc_id,
+                  double* efc_force, int32_t* ncon, double* contact_force, double* qfrc_constraint, double* qacc, void* stream) {
+  // (argument checks first, in an order that lets each be reached without a device)
+  const std::string fn = "sg_get_forces: ";
+  if (!b) return fail(SG_ERR_INVALID, fn + "null batch");
+  if (n_ids <= 0) return fail(SG_ERR_INVALID, fn + "n_ids must be positive");
+  if (max_rows <= 0 && (efc_type || efc_id || efc_force)) return fail(SG_ERR_INVALID, fn + "max_rows must be positive when a row array is given");
+  if (max_contacts <= 0 && contact_force) return fail(SG_ERR_INVALID, fn + "max_contacts must be positive when contact_force is given");
+  if (!env_ids && n_ids != b->n) return fail(SG_ERR_INVALID, fn + "env_ids == NULL needs n_ids == the batch's env count");
+  if (env_ids)
+    for (int i = 0; i < n_ids; i++)
+      if (env_ids[i] < 0 || env_ids[i] >= b->n)
+        return fail(SG_ERR_INVALID, fn + "env id " + std::to_string(env_ids[i]) + " out of range [0, " + std::to_string(b->n) + ")");
+  const sg_model* m = b->m;
+  const SgKinHost& K = m->kin;
+  const SgForceHost& Fo = m->forces;
+  if (K.ok && !Fo.ok) return fail(SG_ERR_MODEL, fn + Fo.err);
+  if (const char* what = K.ok ? counts_differ(m, COUNTS_SMOOTH) : nullptr) return fail(SG_ERR_MODEL, fn + what);
+  // (the kernels index the list: every env gets an id, also where the caller lists none)
+  std::vector<int32_t> all;
+  if (!env_ids) {
+    all.resize(n_ids);
+    for (int i = 0; i < n_ids; i++) all[i] = i;
+    env_ids = all.data();
+  }
+  Readout r{b, "sg_get_forces", (hipStream_t)stream};
+  if (int rc = r.prepare(env_ids, n_ids)) return rc;
+  if (!nefc && !iters && !efc_type && !efc_id && !efc_force && !ncon && !contact_force && !qfrc_constraint && !qacc) return SG_OK;
+  if (int rc = r.need_solve()) return rc;
+  if (int rc = r.need_con()) return rc;
+  if (int rc = r.need(b->forces, &Fo.dbl, &Fo.ints, "forces table")) return rc;
+  const SgForceOff& f = Fo.o;
+  const int nv = m->dyn.o.nv;
+  const size_t nrows = f.nrows, cap = f.cap, per_env = forces_env_bytes(m);
+  const int chunk = (int)std::min<size_t>((size_t)n_ids, std::max<size_t>(b->forces_cap / per_env, 1));
+  if (int rc = r.reserve(b->forces_ws, (size_t)chunk * (per_env / 8), "work space")) return rc;
+  const size_t lds_rows = sizeof(double) * ((size_t)SGS_REC * K.o.nbody + (size_t)SGS_DOF * nv) + sizeof(int) * (3 * nrows + cap);
+  const size_t lds_pgs = sizeof(double) * (nrows + nv);
+  if (int rc = r.grant_lds(b->forces_rows_attr_set, sg_forces_rows_kernel, SGF_LDS_MAX - SGF_STATIC_LDS)) return rc;
+  if (int rc = r.grant_lds(b->forces_pgs_attr_set, sg_forces_pgs_kernel, SGF_LDS_MAX - SGF_STATIC_LDS)) return rc;
+  // the work space of a chunk: every array for `chunk` envs, the doubles first
+  SgForcesArgs a;
+  r.tables_dyn(a);
+  a.VI = b->solve.i; a.v = m->solve.o; a.FD = b->forces.d; a.FI = b->forces.i; a.f = f;
+  a.qpos = b->qpos; a.qvel = b->qvel; a.warm = b->warm; a.zero = b->zero.d;
+  double* wd = b->forces_ws.p;
+  a.J = wd; wd += (size_t)chunk * nrows * nv;
+  a.W = wd; wd += (size_t)chunk * nrows * nv;
+  a.sc = wd; wd += (size_t)chunk * nrows * SGF_SC;
+  a.qs = wd; wd += (size_t)chunk * nv;
+  a.cdist = wd; wd += (size_t)chunk * cap;
+  a.cpos = wd; wd += (size_t)chunk * 3 * cap;
+  a.cframe = wd; wd += (size_t)chunk * 9 * cap;
+  int* wi = (int*)wd;
+  a.rows = wi; wi += (size_t)chunk * 3 * nrows;
+  a.cgeom = wi; wi += (size_t)chunk * 2 * cap;
+  a.caddr = wi; wi += (size_t)chunk * cap;
+  a.ncon_ws = wi; wi += chunk;
+  a.nefc_ws = wi;
+  a.max_rows = max_rows; a.max_contacts = max_contacts;
+  const int* ids = r.dids;
+  for (int c0 = 0; c0 < n_ids; c0 += chunk) {
+    const int nc = std::min(chunk, n_ids - c0);
+    r.dids = ids + c0; r.n_ids = nc;
+    if (int rc = contacts_launch(r, (int)cap, a.ncon_ws, a.cgeom, a.cdist, a.cpos, a.cframe)) return rc;
+    if (int rc = solve_launch(r, SGV_MODE_FORWARD, 1, nullptr, nullptr, nullptr, nullptr, a.qs, nullptr, nullptr, nullptr, nullptr, nullptr)) return rc;
+    a.env_ids = r.dids; a.n_ids = nc;
+    const size_t at = (size_t)c0;
+    a.nefc = nefc ? nefc + at : nullptr; a.iters = iters ? iters + at : nullptr; a.ncon = ncon ? ncon + at : nullptr;
+    a.efc_type = efc_type ? efc_type + at * max_rows : nullptr; a.efc_id = efc_id ? efc_id + at * max_rows : nullptr;
+    a.efc_force = efc_force ? efc_force + at * max_rows : nullptr;
+    a.contact_force = contact_force ? contact_force + at * 3 * max_contacts : nullptr;
+    a.qfrc = qfrc_constraint ? qfrc_constraint + at * nv : nullptr; a.qacc = qacc ? qacc + at * nv : nullptr;
+    hipLaunchKernelGGL(sg_forces_rows_kernel, dim3(nc), dim3(64), lds_rows, r.s, a);
+    HIPCHK(hipGetLastError());
+    if (int rc = solve_launch(r, SGV_MODE_SOLVE, (int)nrows, a.J, a.W, a.nefc_ws, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) return rc;
+    hipLaunchKernelGGL(sg_forces_pgs_kernel, dim3(nc), dim3(64), lds_pgs, r.s, a);
+    HIPCHK(hipGetLastError());
+  }
+  return SG_OK;
 }
 
 int sg_model_nsite(const sg_model* m) { return m ? (int)m->point.site_body.size() : 0; }

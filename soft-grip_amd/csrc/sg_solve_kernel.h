@@ -53,6 +53,8 @@ struct SgSolveArgs {
   const int* env_ids;   // device, n_ids entries (NULL: env k = k)
   int n_ids, mode;
   int n_rhs, tile;      // right-hand sides (SOLVE) or points (POINT) of an env, and how many of them a tile holds
+  const int* rhs_count; // SOLVE: [n_ids] how many of an env's n_rhs rows are there, or NULL: all.  The others are not read, and not written
+                        // either EXCEPT for an env that ends in NaN (sgv_fill): x must have room for all n_rhs rows of every env
   const double* y;      // SOLVE: [n_ids][n_rhs][nv]
   double* x;            //        [n_ids][n_rhs][nv] or NULL; may be y
   const double* applied;   // FORWARD: [n_ids][nv] or NULL: zero
@@ -138,6 +140,7 @@ __global__ __launch_bounds__(64) void sg_solve_kernel(SgSolveArgs a) {
   const double* q = a.qpos + (size_t)env * o.nq;
   const double* qd = a.mode == SGV_MODE_FORWARD ? a.qvel + (size_t)env * nv : a.zero;
   const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+  const int n_rhs = a.rhs_count ? max(0, min(a.n_rhs, a.rhs_count[k])) : a.n_rhs;   // (the rows' stride stays a.n_rhs)
   // 1. the NaN check
   bool bad = false;
   for (int i = lane; i < o.nq; i += 64) bad |= !isfinite(q[i]);
@@ -147,7 +150,7 @@ __global__ __launch_bounds__(64) void sg_solve_kernel(SgSolveArgs a) {
       for (int i = lane; i < nv; i += 64) bad |= !isfinite(a.applied[(size_t)k * nv + i]);
   }
   if (a.mode == SGV_MODE_SOLVE)
-    for (size_t i = lane; i < (size_t)a.n_rhs * nv; i += 64) bad |= !isfinite(a.y[(size_t)k * a.n_rhs * nv + i]);
+    for (size_t i = lane; i < (size_t)n_rhs * nv; i += 64) bad |= !isfinite(a.y[(size_t)k * a.n_rhs * nv + i]);
   bad = __syncthreads_or(bad);
   if (bad) {
     sgv_fill(a, k, lane, qnan);
@@ -217,8 +220,8 @@ __global__ __launch_bounds__(64) void sg_solve_kernel(SgSolveArgs a) {
   if (a.mode == SGV_MODE_SOLVE) {
     if (!a.x) return;
     const size_t at = (size_t)k * a.n_rhs * nv;
-    for (int r0 = 0; r0 < a.n_rhs; r0 += a.tile) {
-      const int nr = min(a.tile, a.n_rhs - r0);
+    for (int r0 = 0; r0 < n_rhs; r0 += a.tile) {
+      const int nr = min(a.tile, n_rhs - r0);
       for (int w = lane; w < nr * nv; w += 64) X[w] = a.y[at + (size_t)r0 * nv + w];
       __syncthreads();
       sgv_solve_tile(a, F, X, nr, lane);

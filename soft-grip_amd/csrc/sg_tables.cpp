@@ -1,5 +1,5 @@
 // sg_tables.cpp -- the host builders of the read-outs' per-model tables, which sg_model_create (sg_api.hip) calls: kinematics and contact
-// pairs (sg_readout.h), dynamics (sg_dyn.h), smooth (sg_smooth.h) and point (sg_point.h); sg_solve.h builds its own from these.  Plain
+// pairs (sg_readout.h), dynamics (sg_dyn.h), smooth (sg_smooth.h), point (sg_point.h) and forces (sg_forces.h); sg_solve.h builds its own.  Plain
 // host C++ without a HIP call: every variant of the library links it, and the host tests compile it with g++ (tests/emu/sg_tables_dump.cpp,
 // tests/test_tables_host.py, scripts/sanitize/host_main.cpp).  Every builder either sets ok or leaves a message in err.
 #if defined(__HIPCC__)
@@ -13,6 +13,7 @@
 
 #include "sg_blob.h"   // sg_blob_find: the one (bounds-checked) reader of the model blob
 #include "sg_point.h"  // (sg_smooth.h, sg_dyn.h, sg_readout.h)
+#include "sg_forces.h" // (sg_solve.h)
 
 // ---- the builders sg_model_create calls (sg_readout.h) ----
 // an array of the blob as `var`, its length in c (want >= 0: that many elements), or the builder ends with T->err set
@@ -317,5 +318,89 @@ void sgp_build(const void* blob, size_t nbytes, const SgKinHost& K, const SgDynH
   T->site_body.assign(Dn.ints.begin() + Dn.o.sbody, Dn.ints.begin() + Dn.o.sbody + ns);
   T->site_pos.assign(Dn.dbl.begin() + Dn.o.spos, Dn.dbl.begin() + Dn.o.spos + 3 * ns);
   T->site_quat.assign(squat, squat + 4 * ns);
+  T->ok = true;
+}
+
+// the forces table (sg_forces.h): the equality records, the limited joints, the per-geom solver parameters, the three *_invweight0
+// arrays and opt's tolerance, iterations, impratio, meaninertia and njmax.  A model sg_solve_mass refuses is refused with that
+// read-out's reason; a condim other than 1 or 3 and an LDS block that does not fit are refused by name
+void sgf_build(const void* blob, size_t nbytes, const SgKinHost& K, const SgConHost& C, const SgDynHost& Dn, const SgSolveHost& V, SgForceHost* T) {
+  if (!K.ok) { T->err = K.err; return; }
+  if (!C.ok) { T->err = C.err; return; }
+  if (!V.ok) { T->err = V.err; return; }
+  const long long nb = K.o.nbody, nj = K.o.njnt, ng = K.o.ngeom, nq = K.o.nq, nv = Dn.o.nv, nt = Dn.o.ntendon;
+  long long c = 0, ne = 0;
+  SG_FIELD(T, eqtype, "eq_type", SG_DT_I32, -1);
+  ne = c;
+  SG_FIELD(T, eqo1, "eq_obj1id", SG_DT_I32, ne);
+  SG_FIELD(T, eqo2, "eq_obj2id", SG_DT_I32, ne);
+  SG_FIELD(T, eqdata, "eq_data", SG_DT_F64, 5 * ne);
+  SG_FIELD(T, eqsolref, "eq_solref", SG_DT_F64, 2 * ne);
+  SG_FIELD(T, eqsolimp, "eq_solimp", SG_DT_F64, 5 * ne);
+  SG_FIELD(T, tlen0, "tendon_length0", SG_DT_F64, nt);
+  SG_FIELD(T, teninvw, "tendon_invweight0", SG_DT_F64, nt);
+  SG_FIELD(T, jlimited, "jnt_limited", SG_DT_I32, nj);
+  SG_FIELD(T, jrange, "jnt_range", SG_DT_F64, 2 * nj);
+  SG_FIELD(T, jmargin, "jnt_margin", SG_DT_F64, nj);
+  SG_FIELD(T, jsolref, "jnt_solref", SG_DT_F64, 2 * nj);
+  SG_FIELD(T, jsolimp, "jnt_solimp", SG_DT_F64, 5 * nj);
+  SG_FIELD(T, gfric, "geom_friction", SG_DT_F64, 3 * ng);
+  SG_FIELD(T, gsolref, "geom_solref", SG_DT_F64, 2 * ng);
+  SG_FIELD(T, gsolimp, "geom_solimp", SG_DT_F64, 5 * ng);
+  SG_FIELD(T, gsolmix, "geom_solmix", SG_DT_F64, ng);
+  SG_FIELD(T, ggap, "geom_gap", SG_DT_F64, ng);
+  SG_FIELD(T, gmargin, "geom_margin", SG_DT_F64, ng);
+  SG_FIELD(T, gcondim, "geom_condim", SG_DT_I32, ng);
+  SG_FIELD(T, dofinvw, "dof_invweight0", SG_DT_F64, nv);
+  SG_FIELD(T, binvw, "body_invweight0", SG_DT_F64, 2 * nb);
+  SG_FIELD(T, q0, "qpos0", SG_DT_F64, nq);
+  SG_FIELD(T, optd, "opt_d", SG_DT_F64, -1);
+  if (c < 7) { T->err = "model blob lacks opt_d"; return; }
+  SG_FIELD(T, opti, "opt_i", SG_DT_I32, -1);
+  if (c < 3) { T->err = "model blob lacks opt_i"; return; }
+  const int* jtype = K.ints.data() + K.o.jtype;
+  for (int e = 0; e < ne; e++) {
+    if (eqtype[e] == SG_EQ_JOINT) {
+      if (eqo1[e] < 0 || eqo1[e] >= nj || eqo2[e] >= nj || jtype[eqo1[e]] == SG_JNT_FREE || (eqo2[e] >= 0 && jtype[eqo2[e]] == SG_JNT_FREE)) {
+        T->err = "joint equality " + std::to_string(e) + " names no scalar joint";
+        return;
+      }
+    } else if (eqtype[e] == SG_EQ_TENDON) {
+      if (eqo1[e] < 0 || eqo1[e] >= nt) { T->err = "tendon equality " + std::to_string(e) + " names no tendon"; return; }
+    } else {
+      T->err = "equality type " + std::to_string(eqtype[e]) + " (joint and tendon equalities only)";
+      return;
+    }
+  }
+  // every candidate pair's condim (the larger of its geoms') must be 1 or 3
+  for (size_t p = 0; p + 1 < C.pairs.size(); p += 2) {
+    const int cd = std::max(gcondim[C.pairs[p]], gcondim[C.pairs[p + 1]]);
+    if (cd != 1 && cd != 3) { T->err = "condim " + std::to_string(cd) + " of geoms " + std::to_string(C.pairs[p]) + " and " + std::to_string(C.pairs[p + 1]) + " (1 and 3 only)"; return; }
+  }
+  std::vector<int> limj;
+  for (int j = 0; j < nj; j++)
+    if (jlimited[j] && jtype[j] != SG_JNT_FREE) limj.push_back(j);
+  SgForceOff& o = T->o;
+  o.neq = (int)ne; o.nlim = (int)limj.size(); o.cap = C.cap; o.njmax = opti[2]; o.iterations = opti[0];
+  o.nrows = sgf_row_capacity(o.neq, o.nlim, o.cap, o.njmax);
+  const long long rows_lds = 8ll * (SGS_REC * nb + SGS_DOF * nv) + 4ll * (3ll * o.nrows + o.cap), pgs_lds = 8ll * (o.nrows + nv);
+  if (std::max(rows_lds, pgs_lds) > SGF_LDS_MAX - SGF_STATIC_LDS) {
+    T->err = "the row list of " + std::to_string(o.nrows) + " rows beside the bodies' records (" + std::to_string(std::max(rows_lds, pgs_lds)) + " bytes) does not fit the " +
+             std::to_string(SGF_LDS_MAX / 1024) + " KB of LDS";
+    return;
+  }
+  std::vector<double>& D = T->dbl;
+  o.eqdata = sg_put(D, eqdata, 5 * ne); o.eqsolref = sg_put(D, eqsolref, 2 * ne); o.eqsolimp = sg_put(D, eqsolimp, 5 * ne); o.tlen0 = sg_put(D, tlen0, nt);
+  o.jrange = sg_put(D, jrange, 2 * nj); o.jmargin = sg_put(D, jmargin, nj); o.jsolref = sg_put(D, jsolref, 2 * nj); o.jsolimp = sg_put(D, jsolimp, 5 * nj);
+  o.gfric = sg_put(D, gfric, 3 * ng); o.gsolref = sg_put(D, gsolref, 2 * ng); o.gsolimp = sg_put(D, gsolimp, 5 * ng); o.gsolmix = sg_put(D, gsolmix, ng);
+  o.ggap = sg_put(D, ggap, ng); o.gmargin = sg_put(D, gmargin, ng); o.dofinvw = sg_put(D, dofinvw, nv);
+  std::vector<double> bw(nb);
+  for (int b = 0; b < nb; b++) bw[b] = binvw[2 * b];
+  o.bodyinvw = sg_put(D, bw); o.teninvw = sg_put(D, teninvw, nt); o.q0 = sg_put(D, q0, nq);
+  const double opt4[4] = {optd[0], optd[4], optd[5], optd[6]};   // timestep, tolerance, impratio, meaninertia
+  o.opt = sg_put(D, opt4, 4);
+  std::vector<int>& I = T->ints;
+  o.eqtype = sg_put(I, eqtype, ne); o.eqobj1 = sg_put(I, eqo1, ne); o.eqobj2 = sg_put(I, eqo2, ne); o.limj = sg_put(I, limj); o.gcondim = sg_put(I, gcondim, ng);
+  if (I.empty()) I.push_back(0);
   T->ok = true;
 }

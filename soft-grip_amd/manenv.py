@@ -402,6 +402,22 @@ class ManEnv(Env):
         out["geom_names"] = [n or "" for n in self.model.geom_names]
         return out
 
+    def get_forces(self, env_ids=None, max_rows=None, max_contacts=256):
+        """how hard the constraints push at the current state (data.efc_force, data.qfrc_constraint and data.qacc after sim.forward()):
+        NativeBatch.forces' dict of device tensors -- nefc, iters, ncon [k], efc_type, efc_id, efc_force [k, R], contact_force [k, C, 3],
+        qfrc_constraint, qacc [k, nv].  After step() these are the NEXT forward pass's forces, as with get_contacts()."""
+        return self.env.forces(env_ids=env_ids, max_rows=max_rows, max_contacts=max_contacts)
+
+    def get_contact_forces(self, env_ids=None, max_contacts=256):
+        """get_contacts()' dict plus ``force`` [k, C, 3], contact i's force in its own frame with the normal first (mj_contactForce's
+        first three numbers; zero for a contact without constraint rows), and ``force_world`` [k, C, 3] = frame' force, the force on
+        geom2 in world axes (geom1 feels its negative)"""
+        out = self.get_contacts(env_ids=env_ids, max_contacts=max_contacts)
+        out["force"] = self.env.forces(env_ids=env_ids, max_rows=1, max_contacts=max_contacts)["contact_force"]
+        frame = out["frame"].reshape(out["frame"].shape[0], -1, 3, 3)
+        out["force_world"] = (frame.transpose(2, 3) @ out["force"].unsqueeze(-1)).squeeze(-1)
+        return out
+
     def get_velocities(self, env_ids=None):
         """body velocities of the listed envs (None: all) at the current state, world axes: NativeBatch.velocities' dict of device
         tensors ang, lin, com_lin [k, nbody, 3] -- the time derivative of the poses when qpos moves as qvel says (data.cvel /

@@ -28,6 +28,7 @@ SYMBOLS = [
     "sg_get_mass_matrix", "sg_get_joint_forces", "sg_inverse_dynamics",
     "sg_get_point_motion", "sg_get_jacobians", "sg_model_nsite", "sg_model_sites",
     "sg_solve_mass", "sg_forward_smooth", "sg_get_point_inertia",
+    "sg_get_forces", "sg_model_max_rows", "sg_set_forces_workspace",
 ]
 SG_RENDER_SKIN = 1
 # sg_ray: category bits of cat_mask (ground plane, static, moving finger box, shell element, centre sphere) and flags
@@ -115,6 +116,9 @@ def load_library(path):
     L.sg_solve_mass.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, dp, dp, dp, vp]
     L.sg_forward_smooth.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, dp, dp, dp, vp]
     L.sg_get_point_inertia.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32), dp, dp, dp, vp]
+    L.sg_get_forces.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, ip, ip, ip, ip, dp, ip, dp, dp, dp, vp]
+    L.sg_model_max_rows.argtypes = [vp]
+    L.sg_set_forces_workspace.argtypes = [vp, C.c_size_t]
     L.sg_lstm_forward.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int, vp]
     L.sg_lstm_backward.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, vp]
     L.sg_profile_enable.argtypes = [vp, C.c_int]
@@ -471,6 +475,39 @@ class NativeBatch:
         self._check(self.L.sg_get_point_inertia(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, P,
                                                 body.ctypes.data_as(C.POINTER(C.c_int32)), pos.ctypes.data_as(C.c_void_p), _ptr(W), _ptr(pivot), self._stream()))
         return W, pivot
+
+    def forces(self, env_ids=None, max_rows=None, max_contacts=256):
+        """mj_forward's constraint stage of the listed envs (None: all) on the current state (sg_get_forces): dict of device tensors
+        nefc, iters, ncon [k] int32 (nefc may exceed max_rows; nefc = ncon = -1: the env's state is not finite, its double outputs are
+        NaN), efc_type, efc_id [k, max_rows] int32 and efc_force [k, max_rows] float64 (the first min(nefc, max_rows) rows in
+        mj_makeConstraint's order: type 0 equality, 3 limit, 5 frictionless contact, 7 elliptic contact; id the equality, the joint or the
+        contact's index in contacts()' list), contact_force [k, max_contacts, 3] (contact i's force in its own frame, normal first),
+        qfrc_constraint [k, nv] = J' f and qacc [k, nv], data.qacc after mj_forward.  max_rows=None: the model's row capacity
+        (sg_model_max_rows).  The slots past the written ones are zero.  Nothing in the batch changes."""
+        t = self.torch
+        ids, k = self._ids(env_ids)
+        nv = self.nmodel.nv
+        mr = self.max_rows() if max_rows is None else int(max_rows)
+        mc = int(max_contacts)
+        i32 = dict(dtype=t.int32, device=self.device)
+        f64 = dict(dtype=t.float64, device=self.device)
+        out = dict(nefc=t.zeros(k, **i32), iters=t.zeros(k, **i32), ncon=t.zeros(k, **i32), efc_type=t.zeros(k, mr, **i32), efc_id=t.zeros(k, mr, **i32),
+                   efc_force=t.zeros(k, mr, **f64), contact_force=t.zeros(k, mc, 3, **f64), qfrc_constraint=t.zeros(k, nv, **f64), qacc=t.zeros(k, nv, **f64))
+        self._check(self.L.sg_get_forces(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, mr, mc, _ptr(out["nefc"]), _ptr(out["iters"]),
+                                         _ptr(out["efc_type"]), _ptr(out["efc_id"]), _ptr(out["efc_force"]), _ptr(out["ncon"]), _ptr(out["contact_force"]),
+                                         _ptr(out["qfrc_constraint"]), _ptr(out["qacc"]), self._stream()))
+        return out
+
+    def max_rows(self):
+        """the constraint rows sg_get_forces reserves per env (sg_model_max_rows)"""
+        n = self.L.sg_model_max_rows(self.nmodel.ptr)
+        if n < 0:
+            self._check(n)
+        return n
+
+    def set_forces_workspace(self, nbytes):
+        """caps the device work space of forces() (sg_set_forces_workspace; the env list is processed in chunks that fit)"""
+        self._check(self.L.sg_set_forces_workspace(self.ptr, C.c_size_t(int(nbytes))))
 
     def contacts(self, env_ids=None, max_contacts=256):
         """mj_collision of the listed envs (None: all) on the current state (sg_get_contacts): dict of device tensors ncon [k] int32
