@@ -460,6 +460,54 @@ int sg_get_forces(sg_batch* b, const int32_t* env_ids, int n_ids, int max_rows, 
 int sg_model_max_rows(const sg_model* m);
 int sg_set_forces_workspace(sg_batch* b, size_t bytes);
 
+/* ---- the soft object as one thing: replaces downloading every element body's pose and twist to redo on the host what the renderer and
+ * sg_ray do on the chip -- the surface, its volume and width, and the body-tree sums mj_subtreeVel / data.subtree_com give.  The skin is
+ * the closed triangle mesh bound to bodies that sg_model_set_skin attaches (SG_RAY_SKIN and SG_RENDER_SKIN show the same vertices).
+ * Each call is a pure function of the batch's CURRENT qpos and qvel.  env_ids as in sg_get_velocities (HOST, NULL = all); outputs are
+ * DEVICE pointers, row k belonging to the k-th listed env, and any may be NULL.  The calls read the batch, change nothing in it and do
+ * not synchronise the host (the first call after sg_model_set_skin uploads the skin's tables again, as sg_render_ex does); free
+ * quaternions are normalised on the way in.  An env whose qpos or qvel holds a NaN or inf gets NaN in every double output and -1 in
+ * every int output, and disturbs no other env.  No atomics: two calls give the same bits; an env's bits depend neither on the env list,
+ * nor on its order, nor on which outputs are NULL; a direction's bits depend neither on n_dirs nor on its place in the list.
+ * Host-side model queries (no device):
+ *   sg_model_skin_closed   1 when every directed edge (a, b) of the skin's faces occurs once and (b, a) occurs once, else 0; -1 without
+ *                          a skin
+ *   sg_model_skin_root     the deepest body that is an ancestor of (or is) every body the skin's vertices are bound to, "the object";
+ *                          -1 without a skin
+ *   sg_model_skin_rest     rest [nvert][3] (HOST): the vertices at qpos0 in frame_body's frame (-1: world)
+ *   sg_model_subtree_mass  mass [nbody] (HOST): the mass of every body's subtree, row 0 the whole model's
+ * sg_get_skin_vertices: every array is [n_ids][nvert][3].  pos = xpos[body] + R(xquat[body]) vert_pos, the vertex SG_RAY_SKIN documents;
+ *   vel = lin + ang x (pos - xpos), the material point's velocity in sg_get_velocities' terms; local = R_f' (pos - xpos_f) in
+ *   frame_body's frame (-1: local equals pos).  Any skin, open or closed.
+ * sg_get_shape: shape [n_ids][SG_SHAPE_N]: volume V; area A; the centroid of the enclosed solid (3); its central second moments
+ *   int (x - c)(x - c)' dV as xx, yy, zz, xy, xz, yz (6); dV/dt.  The integrals are taken about p0, vertex 0's position: for face
+ *   (i, j, k) with a, b, c its vertices minus p0, det = a . (b x c) and s = a + b + c: V = sum det / 6, A = sum |(b - a) x (c - a)| / 2,
+ *   first moment sum det s / 24, second moment sum det (aa' + bb' + cc' + ss') / 120, dV/dt = sum (va . (b x c) + a . (vb x c) +
+ *   a . (b x vc)) / 6 with velocities relative to vertex 0's.  Centroid and central moments follow by one division and one subtraction,
+ *   without clamping: V = 0 gives NaN there, and V says why.  shape needs a CLOSED skin (wound outward for V > 0).
+ *   dir [n_dirs][3] and dir_body [n_dirs] (NULL: all -1) are HOST arrays, read before return and uploaded on `stream`.  lo, hi
+ *   [n_ids][n_dirs]: the min and max over the vertices of d . (pos - o), d the normalised direction -- in world axes with o = 0 for
+ *   dir_body -1, else turned with that body and o its xpos: hi - lo is the object's width along a palm-fixed grip axis.  lo_vert, hi_vert
+ *   [n_ids][n_dirs]: the vertex attaining it, the smallest index on a tie.  The extents need no closed skin.  n_dirs may be 0 with NULL
+ *   arrays and is at most 256.
+ * sg_get_subtree: every array is [n_ids][nbody][3].  For body i, the sums over i and its descendants in ascending body order:
+ *   com = sum m xipos / M_i; linvel = sum m com_lin / M_i (com_lin: sg_get_velocities'); angmom = sum (R I R' w + m (xipos - com_i) x
+ *   com_lin), about the subtree's own com, in world axes.  Row 0 is the whole model.  A subtree with M_i = 0 gets the body's own xipos
+ *   and com velocity, and a zero angmom.  Needs no skin.
+ * SG_ERR_INVALID (checked before anything touches the device; nothing is written): NULL batch, n_ids <= 0, an env id out of range,
+ * frame_body or a dir_body outside [-1, nbody), n_dirs < 0 or above 256, n_dirs > 0 with NULL dir, a direction that is not finite or of
+ * zero length.  SG_ERR_MODEL, with the limit named in the message: a model sg_get_velocities cannot run, no skin (the two skin calls),
+ * an open skin with shape given, an LDS block -- 22 doubles per body and 6 per vertex -- beyond 160 KB. */
+#define SG_SHAPE_N 12
+int sg_model_skin_closed(const sg_model* m);
+int sg_model_skin_root(const sg_model* m);
+int sg_model_skin_rest(const sg_model* m, int frame_body, double* rest);
+int sg_model_subtree_mass(const sg_model* m, double* mass);
+int sg_get_skin_vertices(sg_batch* b, const int32_t* env_ids, int n_ids, int frame_body, double* pos, double* vel, double* local, void* stream);
+int sg_get_shape(sg_batch* b, const int32_t* env_ids, int n_ids, int n_dirs, const double* dir, const int32_t* dir_body, double* shape, double* lo,
+                 double* hi, int32_t* lo_vert, int32_t* hi_vert, void* stream);
+int sg_get_subtree(sg_batch* b, const int32_t* env_ids, int n_ids, double* com, double* linvel, double* angmom, void* stream);
+
 /* The recurrence of one direction of one fp64 LSTM layer with H = 128 hidden units (csrc/sg_lstm.hip), for the Conv-LSTM and
  * Conv-BiLSTM regressors (soft-grip_amd/lstm.py).  Keras' conventions: gate order i, f, g (the candidate), o along the 4H axis, sigmoid
  * for i, f and o, tanh for g and for the cell, row-major kernels.  The caller keeps what is regular -- the input projection

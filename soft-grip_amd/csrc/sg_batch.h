@@ -13,6 +13,7 @@
 #include "sg_solve.h"
 #include "sg_forces.h"
 #include "sg_skin.h"
+#include "sg_shape.h"
 #include "sg_rows_host.h"   // (sg_work.h, sg_plan.h)
 #include "sg_devmem.h"   // SgArena, SgScratch: the owners of every device buffer below (after the HIP runtime's declarations)
 
@@ -137,6 +138,17 @@ struct sg_batch {
   SgScratch<double> forces_ws;
   size_t forces_cap = (size_t)256 << 20;
   bool forces_rows_attr_set = false, forces_pgs_attr_set = false;
+  // the soft object's read-outs (sg_get_skin_vertices / sg_get_shape / sg_get_subtree): the shape table (sg_shape.h) of the skin version
+  // shape_version, in an arena of its own -- the skin is no part of the blob and may change --, and the last call's directions
+  SgArena shape_mem;
+  SgShapeOff shape_off = {};
+  const double* shape_d = nullptr;
+  const int* shape_i = nullptr;
+  bool shape_up = false;
+  unsigned shape_version = 0;
+  bool shape_attr_set = false;
+  SgScratch<double> shape_dir;
+  SgScratch<int> shape_dir_body;
   ~sg_batch() {   // (on the batch's device: sg_batch_destroy.  The arenas and scratch buffers free themselves)
     for (auto& e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (auto& e : ev_pgs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }

@@ -1,6 +1,7 @@
 // sg_readout.hip -- the read-out half of the C ABI (include/softgrip.h): sg_get_poses, sg_render / sg_render_ex and the skin,
 // sg_get_contacts, sg_ray, sg_get_velocities / sg_get_tendons / sg_get_energy, sg_get_mass_matrix / sg_get_joint_forces /
-// sg_inverse_dynamics, sg_get_point_motion / sg_get_jacobians, sg_solve_mass / sg_forward_smooth / sg_get_point_inertia, sg_get_forces, with the kernels
+// sg_inverse_dynamics, sg_get_point_motion / sg_get_jacobians, sg_solve_mass / sg_forward_smooth / sg_get_point_inertia, sg_get_forces,
+// sg_get_skin_vertices / sg_get_shape / sg_get_subtree, with the kernels
 // they launch (the *_kernel*.h files, whose device assembly is sg_readout.device.s).  Entry points and launches only: the host builders of
 // the per-model tables are in sg_tables.cpp (sg_solve.h builds its own), what brings a table to a batch's device is SgDevTable
 // (sg_devmem.h) under Readout::need_*.  None of them writes the state: every pipeline is served.  No CPU fallback.
@@ -17,6 +18,7 @@
 #include "sg_point_kernel.h"
 #include "sg_solve_kernel.h"
 #include "sg_forces_kernel.h"
+#include "sg_shape_kernel.h"
 
 // ---- the entry points' common prologue ----
 // One read-out call on stream s: prepare() puts the kinematics table on the batch's device and the listed env ids (host array,
@@ -742,6 +744,149 @@ int sg_get_forces(sg_batch* b, const int32_t* env_ids, int n_ids, int max_rows, 
     HIPCHK(hipGetLastError());
   }
   return SG_OK;
+}
+
+// ---- the soft object: skin vertices, shape and subtrees, one kernel (sg_shape_kernel), whichever outputs the entry point fn passes ----
+// the shape table of the model's current skin, built for a host query (fn: its name) -> SG_OK or SG_ERR_MODEL
+static int shape_table(const char* fn, const sg_model* m, SgShapeHost* T) {
+  sgh_build(m->kin, m->dyn, m->skin, T);
+  return T->ok ? SG_OK : fail(SG_ERR_MODEL, std::string(fn) + ": " + T->err);
+}
+
+int sg_model_skin_closed(const sg_model* m) {
+  if (!m) return fail(SG_ERR_INVALID, "sg_model_skin_closed: null model");
+  SgShapeHost T;
+  if (int rc = shape_table("sg_model_skin_closed", m, &T)) return rc;
+  return T.o.closed;
+}
+int sg_model_skin_root(const sg_model* m) {
+  if (!m) return fail(SG_ERR_INVALID, "sg_model_skin_root: null model");
+  SgShapeHost T;
+  if (int rc = shape_table("sg_model_skin_root", m, &T)) return rc;
+  return T.o.root;
+}
+int sg_model_skin_rest(const sg_model* m, int frame_body, double* rest) {
+  if (!m || !rest) return fail(SG_ERR_INVALID, "sg_model_skin_rest: null argument");
+  if (!m->kin.ok) return fail(SG_ERR_MODEL, "sg_model_skin_rest: " + m->kin.err);
+  if (frame_body < -1 || frame_body >= m->kin.o.nbody) return fail(SG_ERR_INVALID, "sg_model_skin_rest: frame_body outside [-1, nbody)");
+  if (m->skin.nvert == 0) return fail(SG_ERR_MODEL, "sg_model_skin_rest: the model has no skin");
+  sgh_rest(m->kin, m->skin, frame_body, rest);
+  return SG_OK;
+}
+int sg_model_subtree_mass(const sg_model* m, double* mass) {
+  if (!m || !mass) return fail(SG_ERR_INVALID, "sg_model_subtree_mass: null argument");
+  SgShapeHost T;
+  if (int rc = shape_table("sg_model_subtree_mass", m, &T)) return rc;
+  std::copy(T.dbl.begin() + T.o.smass, T.dbl.begin() + T.o.smass + m->kin.o.nbody, mass);
+  return SG_OK;
+}
+
+// the shape table on the batch's device, uploaded again when the model's skin has changed since (an earlier call, on whatever stream it
+// went out, may still read the old one: the device is waited for first -- once per sg_model_set_skin, not per call)
+static int shape_prepare(sg_batch* b, const char* fn, const SgShapeHost& T) {
+  if (b->shape_up && b->shape_version == b->m->skin.version) return SG_OK;
+  HIPCHK(hipDeviceSynchronize());
+  b->shape_up = false;
+  b->shape_mem.release();
+  SgArena& A = b->shape_mem;
+  double* d = nullptr;
+  int* i = nullptr;
+  if (!(A.upload(&d, T.dbl) && A.upload(&i, T.ints))) {
+    const bool nomem = A.nomem;
+    A.release();
+    return devmem_fail(nomem, std::string(fn) + " (shape table)");
+  }
+  b->shape_d = d; b->shape_i = i; b->shape_off = T.o;
+  b->shape_version = b->m->skin.version;
+  b->shape_up = true;
+  return SG_OK;
+}
+
+static int shape(const char* fn, bool need_skin, sg_batch* b, const int32_t* env_ids, int n_ids, int frame_body, int n_dirs, const double* dir,
+                 const int32_t* dir_body, double* pos, double* vel, double* local, double* shp, double* lo, double* hi, int32_t* lo_vert, int32_t* hi_vert,
+                 double* com, double* linvel, double* angmom, void* stream) {
+  // (argument checks first, in an order that lets each be reached without a device)
+  const std::string f = std::string(fn) + ": ";
+  if (!b) return fail(SG_ERR_INVALID, f + "null batch");
+  if (n_ids <= 0) return fail(SG_ERR_INVALID, f + "n_ids must be positive");
+  if (n_dirs < 0 || n_dirs > SGH_MAXDIR) return fail(SG_ERR_INVALID, f + "n_dirs outside [0, " + std::to_string(SGH_MAXDIR) + "]");
+  if (n_dirs > 0 && !dir) return fail(SG_ERR_INVALID, f + "null dir with n_dirs > 0");
+  for (int j = 0; j < n_dirs; j++) {
+    double n2 = 0.0;
+    for (int c = 0; c < 3; c++) {
+      if (!std::isfinite(dir[3 * j + c])) return fail(SG_ERR_INVALID, f + "direction " + std::to_string(j) + " is not finite");
+      n2 += dir[3 * j + c] * dir[3 * j + c];
+    }
+    if (!(n2 > 0.0) || !std::isfinite(n2)) return fail(SG_ERR_INVALID, f + "direction " + std::to_string(j) + " has zero length (or overflows)");
+  }
+  const sg_model* m = b->m;
+  const SgKinHost& K = m->kin;
+  if (K.ok) {
+    if (frame_body < -1 || frame_body >= K.o.nbody)
+      return fail(SG_ERR_INVALID, f + "frame_body " + std::to_string(frame_body) + " outside [-1, " + std::to_string(K.o.nbody) + ")");
+    for (int j = 0; dir_body && j < n_dirs; j++)
+      if (dir_body[j] < -1 || dir_body[j] >= K.o.nbody)
+        return fail(SG_ERR_INVALID, f + "body id " + std::to_string(dir_body[j]) + " of direction " + std::to_string(j) + " outside [-1, " + std::to_string(K.o.nbody) + ")");
+  }
+  if (!env_ids && n_ids != b->n) return fail(SG_ERR_INVALID, f + "env_ids == NULL needs n_ids == the batch's env count");
+  if (env_ids)
+    for (int i = 0; i < n_ids; i++)
+      if (env_ids[i] < 0 || env_ids[i] >= b->n)
+        return fail(SG_ERR_INVALID, f + "env id " + std::to_string(env_ids[i]) + " out of range [0, " + std::to_string(b->n) + ")");
+  if (K.ok && !m->dyn.ok) return fail(SG_ERR_MODEL, f + m->dyn.err);
+  if (const char* what = K.ok ? counts_differ(m, COUNTS_DYN) : nullptr) return fail(SG_ERR_MODEL, f + what);
+  if (K.ok && need_skin && m->skin.nvert == 0) return fail(SG_ERR_MODEL, f + "the model has no skin (sg_model_set_skin)");
+  SgShapeHost T;
+  const bool stale = !(b->shape_up && b->shape_version == m->skin.version);
+  if (K.ok && stale) {
+    sgh_build(K, m->dyn, m->skin, &T);
+    if (!T.ok) return fail(SG_ERR_MODEL, f + T.err);
+  }
+  const SgShapeOff& h = stale ? T.o : b->shape_off;
+  if (K.ok && shp && h.closed != 1) return fail(SG_ERR_MODEL, f + "the skin is not closed: some directed edge of its faces lacks its reverse, or occurs twice");
+  if (K.ok && (long long)n_ids * std::max(std::max(h.nvert, K.o.nbody), std::max(n_dirs, SGH_SHAPE_N)) > 0x7fffffffll / 3)
+    return fail(SG_ERR_INVALID, f + "too many envs x vertices, bodies or directions for one launch");
+  Readout r{b, fn, (hipStream_t)stream};
+  if (int rc = r.prepare(env_ids, n_ids)) return rc;
+  const bool ext = n_dirs > 0 && (lo || hi || lo_vert || hi_vert);
+  if (!pos && !vel && !local && !shp && !ext && !com && !linvel && !angmom) return SG_OK;
+  if (int rc = r.need_dyn()) return rc;
+  if (int rc = shape_prepare(b, fn, T)) return rc;
+  if (ext) {
+    if (int rc = r.reserve(b->shape_dir, 3 * (size_t)n_dirs, "directions")) return rc;
+    HIPCHK(hipMemcpyAsync(b->shape_dir.p, dir, sizeof(double) * 3 * n_dirs, hipMemcpyHostToDevice, r.s));
+    if (dir_body) {
+      if (int rc = r.reserve(b->shape_dir_body, (size_t)n_dirs, "direction body ids")) return rc;
+      HIPCHK(hipMemcpyAsync(b->shape_dir_body.p, dir_body, sizeof(int) * n_dirs, hipMemcpyHostToDevice, r.s));
+    }
+  }
+  // (sgh_build: the block fits SGH_LDS_MAX beside the kernel's static LDS)
+  const size_t lds = (size_t)sgh_lds_bytes(K.o.nbody, b->shape_off.nvert);
+  if (int rc = r.grant_lds(b->shape_attr_set, sg_shape_kernel, SGH_LDS_MAX - SGH_STATIC_LDS)) return rc;
+  SgShapeArgs a;
+  r.tables_dyn(a);
+  a.HD = b->shape_d; a.HI = b->shape_i; a.h = b->shape_off;
+  a.qpos = b->qpos; a.qvel = b->qvel; a.env_ids = r.dids; a.n_ids = n_ids; a.frame_body = frame_body;
+  a.n_dirs = ext ? n_dirs : 0; a.dir = ext ? b->shape_dir.p : nullptr; a.dir_body = ext && dir_body ? b->shape_dir_body.p : nullptr;
+  a.pos = pos; a.vel = vel; a.local = local; a.shape = shp; a.lo = lo; a.hi = hi; a.lo_vert = lo_vert; a.hi_vert = hi_vert;
+  a.com = com; a.linvel = linvel; a.angmom = angmom;
+  hipLaunchKernelGGL(sg_shape_kernel, dim3(n_ids), dim3(64), lds, r.s, a);
+  HIPCHK(hipGetLastError());
+  return SG_OK;
+}
+
+int sg_get_skin_vertices(sg_batch* b, const int32_t* env_ids, int n_ids, int frame_body, double* pos, double* vel, double* local, void* stream) {
+  return shape("sg_get_skin_vertices", true, b, env_ids, n_ids, frame_body, 0, nullptr, nullptr, pos, vel, local, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+               nullptr, nullptr, stream);
+}
+int sg_get_shape(sg_batch* b, const int32_t* env_ids, int n_ids, int n_dirs, const double* dir, const int32_t* dir_body, double* shp, double* lo, double* hi,
+                 int32_t* lo_vert, int32_t* hi_vert, void* stream) {
+  return shape("sg_get_shape", true, b, env_ids, n_ids, -1, n_dirs, dir, dir_body, nullptr, nullptr, nullptr, shp, lo, hi, lo_vert, hi_vert, nullptr, nullptr, nullptr,
+               stream);
+}
+int sg_get_subtree(sg_batch* b, const int32_t* env_ids, int n_ids, double* com, double* linvel, double* angmom, void* stream) {
+  return shape("sg_get_subtree", false, b, env_ids, n_ids, -1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, com, linvel,
+               angmom, stream);
 }
 
 int sg_model_nsite(const sg_model* m) { return m ? (int)m->point.site_body.size() : 0; }

@@ -1,5 +1,6 @@
 // sg_tables.cpp -- the host builders of the read-outs' per-model tables, which sg_model_create (sg_api.hip) calls: kinematics and contact
-// pairs (sg_readout.h), dynamics (sg_dyn.h), smooth (sg_smooth.h), point (sg_point.h) and forces (sg_forces.h); sg_solve.h builds its own.  Plain
+// pairs (sg_readout.h), dynamics (sg_dyn.h), smooth (sg_smooth.h), point (sg_point.h), forces (sg_forces.h) and -- per skin, at the first call
+// after sg_model_set_skin -- shape (sg_shape.h); sg_solve.h builds its own.  Plain
 // host C++ without a HIP call: every variant of the library links it, and the host tests compile it with g++ (tests/emu/sg_tables_dump.cpp,
 // tests/test_tables_host.py, scripts/sanitize/host_main.cpp).  Every builder either sets ok or leaves a message in err.
 #if defined(__HIPCC__)
@@ -14,6 +15,7 @@
 #include "sg_blob.h"   // sg_blob_find: the one (bounds-checked) reader of the model blob
 #include "sg_point.h"  // (sg_smooth.h, sg_dyn.h, sg_readout.h)
 #include "sg_forces.h" // (sg_solve.h)
+#include "sg_shape.h"  // (sg_skin.h)
 
 // ---- the builders sg_model_create calls (sg_readout.h) ----
 // an array of the blob as `var`, its length in c (want >= 0: that many elements), or the builder ends with T->err set
@@ -403,4 +405,83 @@ void sgf_build(const void* blob, size_t nbytes, const SgKinHost& K, const SgConH
   o.eqtype = sg_put(I, eqtype, ne); o.eqobj1 = sg_put(I, eqo1, ne); o.eqobj2 = sg_put(I, eqo2, ne); o.limj = sg_put(I, limj); o.gcondim = sg_put(I, gcondim, ng);
   if (I.empty()) I.push_back(0);
   T->ok = true;
+}
+
+// the shape table (sg_shape.h): the skin's vertices (body, position) and faces, whether it is closed -- every directed edge (a, b) of
+// its faces once, and (b, a) once --, the deepest body that is an ancestor of every body a vertex is bound to ("the object"), and per
+// body its subtree (itself and its descendants, ascending) with the subtree's mass, summed in that order.  The masses, body_ipos and
+// body_imat are the dynamics table's.  The skin is no part of the blob and may be empty: the subtree read-out needs none
+void sgh_build(const SgKinHost& K, const SgDynHost& Dn, const SgSkinHost& S, SgShapeHost* T) {
+  if (!K.ok) { T->err = K.err; return; }
+  if (!Dn.ok) { T->err = Dn.err; return; }
+  const int nb = K.o.nbody, nvert = S.nvert, nface = S.nface;
+  const int* par = K.ints.data() + K.o.bpar;
+  const long long lds = sgh_lds_bytes(nb, nvert);
+  if (lds > SGH_LDS_MAX - SGH_STATIC_LDS) {
+    T->err = "the records of " + std::to_string(nb) + " bodies and " + std::to_string(nvert) + " skin vertices (" + std::to_string(lds) + " bytes) do not fit the " +
+             std::to_string(SGH_LDS_MAX / 1024) + " KB of LDS";
+    return;
+  }
+  for (int v = 0; v < nvert; v++)
+    if (S.vert_body[v] < 0 || S.vert_body[v] >= nb) { T->err = "skin vertex body out of range"; return; }
+  for (int f = 0; f < 3 * nface; f++)
+    if (S.face[f] < 0 || S.face[f] >= nvert) { T->err = "skin face vertex out of range"; return; }
+  SgShapeOff& o = T->o;
+  o.nvert = nvert; o.nface = nface; o.closed = -1; o.root = -1;
+  if (nvert > 0) {
+    std::vector<std::pair<int, int>> edge;
+    edge.reserve(3 * (size_t)nface);
+    for (int f = 0; f < nface; f++)
+      for (int e = 0; e < 3; e++) edge.push_back({S.face[3 * f + e], S.face[3 * f + (e + 1) % 3]});
+    std::sort(edge.begin(), edge.end());
+    bool closed = nface > 0 && std::adjacent_find(edge.begin(), edge.end()) == edge.end();
+    for (size_t e = 0; closed && e < edge.size(); e++) closed = std::binary_search(edge.begin(), edge.end(), std::make_pair(edge[e].second, edge[e].first));
+    o.closed = closed ? 1 : 0;
+    int root = S.vert_body[0];
+    for (int v = 1; v < nvert; v++) {
+      int other = S.vert_body[v];
+      while (root != other) {   // (parents precede their children: the larger id climbs)
+        if (root > other) root = par[root];
+        else other = par[other];
+      }
+    }
+    o.root = root;
+  }
+  std::vector<std::vector<int>> sub(nb);
+  for (int j = 0; j < nb; j++)
+    for (int i = j;; i = par[i]) {
+      sub[i].push_back(j);
+      if (i == 0) break;
+    }
+  std::vector<int> sstart(nb + 1, 0), slist;
+  std::vector<double> smass(nb, 0.0);
+  for (int i = 0; i < nb; i++) {
+    sstart[i] = (int)slist.size();
+    for (int j : sub[i]) { slist.push_back(j); smass[i] += Dn.dbl[Dn.o.bmass + j]; }
+  }
+  sstart[nb] = (int)slist.size();
+  o.nlist = (int)slist.size();
+  std::vector<double>& D = T->dbl;
+  o.vpos = sg_put(D, S.vert_pos.data(), 3 * (size_t)nvert); o.smass = sg_put(D, smass);
+  std::vector<int>& I = T->ints;
+  o.vbody = sg_put(I, (const int*)S.vert_body.data(), (size_t)nvert); o.face = sg_put(I, (const int*)S.face.data(), 3 * (size_t)nface);
+  o.sstart = sg_put(I, sstart); o.slist = sg_put(I, slist);
+  T->ok = true;
+}
+
+void sgh_rest(const SgKinHost& K, const SgSkinHost& S, int frame_body, double* rest) {
+  std::vector<double> body;
+  sgk_host_fk(K, &body);
+  double rec[SGD_REC] = {0}, frec[SGD_REC] = {0};
+  if (frame_body >= 0)
+    for (int c = 0; c < 7; c++) frec[c] = body[7 * (size_t)frame_body + c];
+  for (int v = 0; v < S.nvert; v++) {
+    for (int c = 0; c < 7; c++) rec[c] = body[7 * (size_t)S.vert_body[v] + c];
+    double pv[SGH_VREC];
+    sgh_vertex(rec, &S.vert_pos[3 * (size_t)v], pv);
+    if (frame_body < 0)
+      for (int c = 0; c < 3; c++) rest[3 * v + c] = pv[c];
+    else
+      sgh_local(frec, pv, rest + 3 * v);
+  }
 }

@@ -418,6 +418,41 @@ class ManEnv(Env):
         out["force_world"] = (frame.transpose(2, 3) @ out["force"].unsqueeze(-1)).squeeze(-1)
         return out
 
+    def object_body(self):
+        """the soft object's body: the deepest body that is an ancestor of every body its skin is bound to (sg_model_skin_root).  A
+        model without a skin gets ``model.composite_skin()`` attached first; -1 when there is none"""
+        self.env._need_skin()
+        return self.nmodel.skin_root()
+
+    def get_skin_vertices(self, frame=None, env_ids=None):
+        """the soft object's surface at the current state (sg_get_skin_vertices): dict of device tensors pos, vel, local [k, nvert, 3]
+        -- world position, the material point's velocity, and the position in body ``frame``'s frame (None: the object's own body)"""
+        body = self.object_body() if frame is None else int(frame)
+        return self.env.skin_vertices(frame_body=body, env_ids=env_ids)
+
+    def get_deformation(self, env_ids=None):
+        """how far the squeeze has moved the surface, in the object's own frame: dict of device tensors disp [k, nvert, 3] = local - rest
+        (rest: the vertices at qpos0, sg_model_skin_rest), max_disp [k] the largest |disp| of each env and max_vert [k] its vertex"""
+        import torch
+        body = self.object_body()
+        local = self.env.skin_vertices(frame_body=body, env_ids=env_ids, outputs=("local",))["local"]
+        disp = local - torch.from_numpy(self.nmodel.skin_rest(body)).to(local.device)
+        mag, vert = disp.norm(dim=-1).max(dim=-1)
+        return dict(disp=disp, max_disp=mag, max_vert=vert)
+
+    def get_shape(self, dirs=None, dir_body=None, env_ids=None):
+        """the soft object as one solid at the current state (sg_get_shape): NativeBatch.shape's dict of device tensors -- shape [k, 12]
+        = volume, area, centroid, central second moments (xx yy zz xy xz yz), dV/dt; with dirs [D, 3] in the frames of dir_body [D]
+        (-1 / None: world) also lo, hi [k, D], the extent along each (hi - lo: the width along a palm-fixed grip axis), and lo_vert,
+        hi_vert [k, D]"""
+        return self.env.shape(dirs=dirs, dir_body=dir_body, env_ids=env_ids)
+
+    def get_subtree(self, env_ids=None):
+        """centre of mass, its velocity and the angular momentum about it of every body's subtree at the current state
+        (data.subtree_com, mj_subtreeVel): NativeBatch.subtree's dict of device tensors com, linvel, angmom [k, nbody, 3]; row
+        object_body() is the soft object's, row 0 the whole model's"""
+        return self.env.subtree(env_ids=env_ids)
+
     def get_velocities(self, env_ids=None):
         """body velocities of the listed envs (None: all) at the current state, world axes: NativeBatch.velocities' dict of device
         tensors ang, lin, com_lin [k, nbody, 3] -- the time derivative of the poses when qpos moves as qvel says (data.cvel /
@@ -563,12 +598,15 @@ class ManEnv(Env):
         return res_
 
     # ---- fused episode: the create_dataset.py schedule without a host round trip per step ----
-    def rollout(self, schedule, out=None, reset=True, energy_out=None):
+    def rollout(self, schedule, out=None, reset=True, energy_out=None, shape_out=None, shape_dirs=None, shape_dir_body=None):
         """Runs ``len(schedule)`` env steps; ``schedule[t]`` is the broadcast ctrl (or None = unchanged) applied
         before step t.  Writes sensordata into ``out[n, T, 12]`` (allocated when None) and returns
         ``(out, flags_or[n])``.  Envs that fail are NOT reset here (their flags are returned).
         ``energy_out``: a ``[n, T, 4]`` float64 device tensor that receives get_energy() of the state after every env step (one
-        sg_get_energy per step, on the same stream); None: no such call is made."""
+        sg_get_energy per step, on the same stream); None: no such call is made.
+        ``shape_out``: a ``[n, T, 12 + 2 D]`` float64 device tensor that receives get_shape(shape_dirs, shape_dir_body) of the state
+        after every env step -- shape, lo, hi side by side, D the number of shape_dirs (one sg_get_shape per step, on the same
+        stream); None: no such call is made."""
         import torch
         T = len(schedule)
         dev = self.env.device
@@ -580,6 +618,9 @@ class ManEnv(Env):
         if energy_out is not None:
             assert energy_out.shape == (self.n_envs, T, 4) and energy_out.dtype == torch.float64 and energy_out.device == dev
             e_row = torch.empty(self.n_envs, 4, dtype=torch.float64, device=dev)
+        if shape_out is not None:
+            nd = 0 if shape_dirs is None else len(np.asarray(shape_dirs, dtype=np.float64).reshape(-1, 3))
+            assert shape_out.shape == (self.n_envs, T, 12 + 2 * nd) and shape_out.dtype == torch.float64 and shape_out.device == dev
         if reset:
             self.env.reset(max(self.sim_start, 0), sens=self._sens, flags=self._flags, touch=self._touch)
             self._ctrl[:] = 0
@@ -592,6 +633,9 @@ class ManEnv(Env):
             flags_or |= self._flags
             if energy_out is not None:
                 energy_out[:, t] = self.env.energy(out=e_row)
+            if shape_out is not None:
+                s = self.env.shape(dirs=shape_dirs, dir_body=shape_dir_body)
+                shape_out[:, t] = torch.cat([s["shape"]] + ([s["lo"], s["hi"]] if nd else []), dim=1)
         return out, flags_or
 
     # specs

@@ -29,7 +29,10 @@ SYMBOLS = [
     "sg_get_point_motion", "sg_get_jacobians", "sg_model_nsite", "sg_model_sites",
     "sg_solve_mass", "sg_forward_smooth", "sg_get_point_inertia",
     "sg_get_forces", "sg_model_max_rows", "sg_set_forces_workspace",
+    "sg_model_skin_closed", "sg_model_skin_root", "sg_model_skin_rest", "sg_model_subtree_mass",
+    "sg_get_skin_vertices", "sg_get_shape", "sg_get_subtree",
 ]
+SG_SHAPE_N = 12      # sg_get_shape's doubles per env: V, A, centroid 3, central second moments xx yy zz xy xz yz, dV/dt
 SG_RENDER_SKIN = 1
 # sg_ray: category bits of cat_mask (ground plane, static, moving finger box, shell element, centre sphere) and flags
 SG_RAY_GROUND, SG_RAY_STATIC, SG_RAY_FINGER, SG_RAY_ELEM, SG_RAY_CENTER, SG_RAY_ALL = 1, 2, 4, 8, 16, 31
@@ -119,6 +122,13 @@ def load_library(path):
     L.sg_get_forces.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, ip, ip, ip, ip, dp, ip, dp, dp, dp, vp]
     L.sg_model_max_rows.argtypes = [vp]
     L.sg_set_forces_workspace.argtypes = [vp, C.c_size_t]
+    L.sg_model_skin_closed.argtypes = [vp]
+    L.sg_model_skin_root.argtypes = [vp]
+    L.sg_model_skin_rest.argtypes = [vp, C.c_int, dp]
+    L.sg_model_subtree_mass.argtypes = [vp, dp]
+    L.sg_get_skin_vertices.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, dp, dp, dp, vp]
+    L.sg_get_shape.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, dp, C.POINTER(C.c_int32), dp, dp, dp, ip, ip, vp]
+    L.sg_get_subtree.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp, dp, dp, vp]
     L.sg_lstm_forward.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, C.c_int, vp]
     L.sg_lstm_backward.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, vp]
     L.sg_profile_enable.argtypes = [vp, C.c_int]
@@ -192,6 +202,33 @@ class NativeModel:
         check(self.L.sg_model_skin(self.ptr, None, None, vb.ctypes.data_as(C.c_void_p), vp.ctypes.data_as(C.c_void_p),
                                    fc.ctypes.data_as(C.c_void_p), rgba.ctypes.data_as(C.POINTER(C.c_float))), self.L)
         return dict(vert_body=vb, vert_pos=vp, face=fc, rgba=rgba)
+
+    def _code(self, n):
+        if n < -1:      # (-1 is an answer of the skin queries; SG_ERR_INVALID needs a null model, which this handle never is)
+            check(n, self.L)
+        return n
+
+    def skin_closed(self):
+        """1: every directed edge of the skin's faces has its reverse exactly once; 0: not; -1: no skin (sg_model_skin_closed)"""
+        return self._code(self.L.sg_model_skin_closed(self.ptr))
+
+    def skin_root(self):
+        """the deepest body that is an ancestor of every body the skin's vertices are bound to, "the object"; -1 without a skin"""
+        return self._code(self.L.sg_model_skin_root(self.ptr))
+
+    def skin_rest(self, frame_body=-1):
+        """[nvert, 3]: the skin's vertices at qpos0 in frame_body's frame (-1: world) (sg_model_skin_rest)"""
+        nv = C.c_int()
+        check(self.L.sg_model_skin(self.ptr, C.byref(nv), None, None, None, None, None), self.L)
+        rest = np.empty((nv.value, 3), np.float64)
+        check(self.L.sg_model_skin_rest(self.ptr, int(frame_body), rest.ctypes.data_as(C.c_void_p)), self.L)
+        return rest
+
+    def subtree_mass(self):
+        """[nbody]: the mass of every body's subtree, row 0 the whole model's (sg_model_subtree_mass)"""
+        mass = np.empty(self.nbody, np.float64)
+        check(self.L.sg_model_subtree_mass(self.ptr, mass.ctypes.data_as(C.c_void_p)), self.L)
+        return mass
 
     def sites(self):
         """the model's sites as points of NativeBatch.point_motion / jacobians (sg_model_sites): (body [nsite] int32, pos [nsite, 3],
@@ -508,6 +545,67 @@ class NativeBatch:
     def set_forces_workspace(self, nbytes):
         """caps the device work space of forces() (sg_set_forces_workspace; the env list is processed in chunks that fit)"""
         self._check(self.L.sg_set_forces_workspace(self.ptr, C.c_size_t(int(nbytes))))
+
+    def _need_skin(self):
+        """a model without a skin gets ``model.composite_skin()`` attached first, as raycast(skin=True) does"""
+        if self.nmodel.skin() is None and hasattr(self.nmodel.model, "composite_skin"):
+            made = self.nmodel.model.composite_skin()
+            if made is not None:
+                self.nmodel.set_skin(made)
+
+    def nvert(self):
+        """the vertices of the model's skin (0: none)"""
+        nv = C.c_int()
+        self._check(self.L.sg_model_skin(self.nmodel.ptr, C.byref(nv), None, None, None, None, None))
+        return nv.value
+
+    def skin_vertices(self, frame_body=-1, env_ids=None, outputs=None):
+        """the skin's vertices of the listed envs (None: all) on the current state (sg_get_skin_vertices): dict of float64 device tensors
+        [k, nvert, 3]: pos (world), vel (the material point's velocity, world axes), local (pos in frame_body's frame; -1: equal to
+        pos).  outputs: the names wanted (None: all)."""
+        t = self.torch
+        self._need_skin()
+        ids, k = self._ids(env_ids)
+        names = ("pos", "vel", "local")
+        out = {n: t.empty(k, self.nvert(), 3, dtype=t.float64, device=self.device) for n in (names if outputs is None else outputs)}
+        self._check(self.L.sg_get_skin_vertices(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, int(frame_body),
+                                                *[_ptr(out.get(n)) for n in names], self._stream()))
+        return out
+
+    def shape(self, dirs=None, dir_body=None, env_ids=None, shape=True):
+        """the soft object's shape of the listed envs (None: all) on the current state (sg_get_shape): dict of device tensors shape
+        [k, 12] float64 = volume, area, centroid (3), central second moments xx yy zz xy xz yz, dV/dt (closed skins only; shape=False
+        leaves it out); and for dirs [D, 3] (host; need not be unit) given in the frames of dir_body [D] (host ints, -1 / None: world)
+        lo, hi [k, D] float64, the object's extent along each, and lo_vert, hi_vert [k, D] int32, the vertices attaining them."""
+        t = self.torch
+        self._need_skin()
+        ids, k = self._ids(env_ids)
+        hd = None if dirs is None else np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        nd = 0 if hd is None else len(hd)
+        hb = None if dir_body is None or nd == 0 else np.ascontiguousarray(dir_body, dtype=np.int32).reshape(-1)
+        assert hb is None or len(hb) == nd
+        f64, i32 = dict(dtype=t.float64, device=self.device), dict(dtype=t.int32, device=self.device)
+        res = {}
+        if shape:
+            res["shape"] = t.empty(k, SG_SHAPE_N, **f64)
+        if nd:
+            res.update(lo=t.empty(k, nd, **f64), hi=t.empty(k, nd, **f64), lo_vert=t.empty(k, nd, **i32), hi_vert=t.empty(k, nd, **i32))
+        self._check(self.L.sg_get_shape(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, nd,
+                                        None if nd == 0 else hd.ctypes.data_as(C.c_void_p), None if hb is None else hb.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        _ptr(res.get("shape")), _ptr(res.get("lo")), _ptr(res.get("hi")), _ptr(res.get("lo_vert")), _ptr(res.get("hi_vert")),
+                                        self._stream()))
+        return res
+
+    def subtree(self, env_ids=None):
+        """the body-tree sums of the listed envs (None: all) on the current state (sg_get_subtree; data.subtree_com, mj_subtreeVel):
+        dict of float64 device tensors [k, nbody, 3], row i over body i and its descendants: com, linvel (of that centre of mass) and
+        angmom (about it, world axes).  Row 0 is the whole model."""
+        t = self.torch
+        ids, k = self._ids(env_ids)
+        out = {n: t.empty(k, self.nmodel.nbody, 3, dtype=t.float64, device=self.device) for n in ("com", "linvel", "angmom")}
+        self._check(self.L.sg_get_subtree(self.ptr, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)), k, _ptr(out["com"]), _ptr(out["linvel"]),
+                                          _ptr(out["angmom"]), self._stream()))
+        return out
 
     def contacts(self, env_ids=None, max_contacts=256):
         """mj_collision of the listed envs (None: all) on the current state (sg_get_contacts): dict of device tensors ncon [k] int32
