@@ -1,4 +1,5 @@
-// The row builder and a full solve of sg_get_forces (csrc/sg_forces.h through csrc/sg_forces_host.h: the text the kernels compile) under
+// The row builder and a full solve of sg_get_forces (csrc/sg_forces.h through csrc/sg_forces_host.h, and through it the smooth walk, the
+// factor and the sweep of csrc/sg_readout_host.h: the text the kernels compile) under
 // AddressSanitizer and UBSan: a stand-alone program, nothing of it is loaded into python.  tests/test_forces_host.py builds and runs it:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I soft-grip_amd/csrc scripts/sanitize/forces_main.cpp
 //       soft-grip_amd/csrc/sg_tables.cpp
@@ -11,7 +12,6 @@
 #include <cstdio>
 #include <fstream>
 #include <iterator>
-#include <memory>
 #include <string>
 #include <vector>
 
@@ -24,21 +24,12 @@ static std::string slurp(const char* path) {
 
 static int run(const char* blob_path, const char* state_path) {
   const std::string blob = slurp(blob_path), raw = slurp(state_path);
-  auto plan = std::make_unique<SgPlan>();
-  *plan = SgPlan{};
-  plan->h.plane_geom = plan->h.center_geom = -1;
-  SgKinHost K;
-  SgConHost C;
-  SgDynHost D;
-  SgSmoothHost S;
-  SgSolveHost V;
-  SgForceHost F;
-  sgk_build(blob.data(), blob.size(), *plan, nullptr, false, &K);
-  sgc_from_blob(blob.data(), blob.size(), K, &C);
-  sgd_build(blob.data(), blob.size(), K, &D);
-  sgs_build(blob.data(), blob.size(), K, D, &S);
-  sgv_build(K, D, S, &V);
-  sgf_build(blob.data(), blob.size(), K, C, D, V, &F);
+  SgHostTables T;
+  sg_host_tables(blob.data(), blob.size(), &T);
+  const SgKinHost& K = T.kin;
+  const SgDynHost& D = T.dyn;
+  const SgSmoothHost& S = T.smooth;
+  const SgForceHost& F = T.forces;
   if (!F.ok) { printf("%s refused: %s\n", blob_path, F.err.c_str()); return 1; }
   const int nq = K.o.nq, nv = D.o.nv, nu = S.o.nu > 0 ? S.o.nu : 1;
   if (raw.size() != sizeof(double) * (size_t)(nq + 2 * nv + nu + 1)) { printf("%s: state of %zu bytes\n", state_path, raw.size()); return 1; }
@@ -47,7 +38,7 @@ static int run(const char* blob_path, const char* state_path) {
   const double k = p[nq + 2 * nv + nu];
   const std::vector<int> kmj(K.o.njnt + 1, 0), kmt(D.o.ntendon + 1, 0);   // (no joint or tendon takes the per-env stiffness: k rides along unused)
   SgfHostOut o;
-  if (sgf_host_env(K, C, D, S, V, F, qpos.data(), qvel.data(), act.data(), warm.data(), k, kmj.data(), kmt.data(), &o)) { printf("%s: a state that is not finite\n", state_path); return 1; }
+  if (sgf_host_env(T, qpos.data(), qvel.data(), act.data(), warm.data(), k, kmj.data(), kmt.data(), &o)) { printf("%s: a state that is not finite\n", state_path); return 1; }
   double fmax_ = 0.0, bmax = 0.0, worst = 0.0;
   std::vector<double> a(nv, 0.0);
   for (int i = 0; i < o.nefc; i++)

@@ -1,6 +1,6 @@
 // Host program of scripts/sanitize/run.sh (ASan + UBSan, CPU only).
 //   host_main FILE.xml ...            compiles each scene in both composite variants and builds both plans (two-finger and tree)
-//   host_main --mutate FILE.sgmodel.. feeds both plan builders, and then the read-out tables' builders (csrc/sg_tables.cpp, sg_solve.h),
+//   host_main --mutate FILE.sgmodel.. feeds both plan builders, and then the read-out tables' builders (sg_tables_build of csrc/sg_tables.cpp),
 //                                     damaged copies of each blob: both plan builders must refuse every one with a message, every
 //                                     table builder must answer with ok or a message, and none may make a reader leave its buffer
 #include <cstdint>
@@ -13,9 +13,7 @@
 #include <vector>
 #include "../../soft-grip_amd/csrc/sg_blob.h"
 #include "../../soft-grip_amd/csrc/sg_mjcf.h"
-#include "../../soft-grip_amd/csrc/sg_plan.h"
-#include "../../soft-grip_amd/csrc/sg_point.h"
-#include "../../soft-grip_amd/csrc/sg_solve.h"
+#include "../../soft-grip_amd/csrc/sg_readout_host.h"
 
 static bool build_both(const void* blob, size_t n, std::string msg[2]) {
   SgPlan P, PT;
@@ -24,20 +22,16 @@ static bool build_both(const void* blob, size_t n, std::string msg[2]) {
   return a || b;
 }
 
-// kin, con, dyn, smooth, point, solve, as sg_model_create calls them (plan == NULL: a plan that names no geom) -> the first table that has
-// neither ok nor a message, or NULL
-static const char* build_tables(const void* blob, size_t n, const SgPlan* plan, const SgTreeDev* tree, bool fast) {
-  SgPlan none{};
-  none.h.plane_geom = none.h.center_geom = -1;
-  SgKinHost K{}; SgConHost C{}; SgDynHost D{}; SgSmoothHost S{}; SgPointHost P{}; SgSolveHost V{};
-  sgk_build(blob, n, plan ? *plan : none, tree, fast, &K);
-  sgc_from_blob(blob, n, K, &C);
-  sgd_build(blob, n, K, &D);
-  sgs_build(blob, n, K, D, &S);
-  sgp_build(blob, n, K, D, &P);
-  sgv_build(K, D, S, &V);
+// every table, on the plans as sg_model_create builds them (planned) or on a plan that names no geom -> the first table that has neither
+// ok nor a message, or NULL
+static const char* build_tables(const void* blob, size_t n, bool planned) {
+  SgHostTables T{};
+  bool fast, tree;
+  if (planned) sg_host_tables_planned(blob, n, &T, &fast, &tree);
+  else sg_host_tables(blob, n, &T);
   auto silent = [](const auto& t) { return !t.ok && t.err.empty(); };
-  return silent(K) ? "kin" : silent(C) ? "con" : silent(D) ? "dyn" : silent(S) ? "smooth" : silent(P) ? "point" : silent(V) ? "solve" : nullptr;
+  return silent(T.kin) ? "kin" : silent(T.con) ? "con" : silent(T.dyn) ? "dyn" : silent(T.smooth) ? "smooth" : silent(T.point) ? "point" : silent(T.solve) ? "solve"
+       : silent(T.forces) ? "forces" : nullptr;
 }
 
 static int n_mut = 0, n_bad = 0;
@@ -52,7 +46,7 @@ static void mutant(const char* what, long long at, const std::string& bytes) {
     printf("ACCEPTED: %s at %lld (%zu bytes): '%s' / '%s'\n", what, at, bytes.size(), msg[0].c_str(), msg[1].c_str());
     n_bad++;
   }
-  if (const char* silent = build_tables(buf.get(), bytes.size(), nullptr, nullptr, false)) {
+  if (const char* silent = build_tables(buf.get(), bytes.size(), false)) {
     printf("SILENT: %s at %lld (%zu bytes): the %s table has neither ok nor a message\n", what, at, bytes.size(), silent);
     n_bad++;
   }
@@ -63,14 +57,9 @@ static int mutate(const char* path) {
   const std::string blob((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
   std::string msg[2];
   if (!build_both(blob.data(), blob.size(), msg)) { printf("%s: no builder takes the intact blob: %s / %s\n", path, msg[0].c_str(), msg[1].c_str()); return 1; }
-  {   // the intact blob's tables, on the plans sg_model_create would use
-    SgPlan P, PT;
-    auto tree = std::make_unique<SgTreeDev>();
-    const bool fast = sg_plan_build(blob.data(), blob.size(), &P, &msg[0]), has_tree = sg_tree_plan_build(blob.data(), blob.size(), &PT, tree.get(), &msg[1]);
-    if (const char* silent = build_tables(blob.data(), blob.size(), fast ? &P : &PT, has_tree ? tree.get() : nullptr, fast)) {
-      printf("%s: the %s table of the intact blob has neither ok nor a message\n", path, silent);
-      return 1;
-    }
+  if (const char* silent = build_tables(blob.data(), blob.size(), true)) {   // the intact blob's tables, on the plans sg_model_create would use
+    printf("%s: the %s table of the intact blob has neither ok nor a message\n", path, silent);
+    return 1;
   }
   sg_blob_header hd;
   memcpy(&hd, blob.data(), sizeof hd);

@@ -12,10 +12,10 @@
 #include <cstdio>
 #include <fstream>
 #include <iterator>
-#include <memory>
 #include <string>
 #include <vector>
 
+#include "sg_readout_host.h"   // sg_host_tables
 #include "sg_shape.h"
 
 static std::string slurp(const char* path) {
@@ -54,13 +54,10 @@ static double run_env(const SgKinHost& K, const SgDynHost& D, const SgSkinHost& 
 
 static int run(const char* blob_path, const char* int_path, const char* dbl_path) {
   const std::string blob = slurp(blob_path), ri = slurp(int_path), rd = slurp(dbl_path);
-  auto plan = std::make_unique<SgPlan>();
-  *plan = SgPlan{};
-  plan->h.plane_geom = plan->h.center_geom = -1;
-  SgKinHost K;
-  SgDynHost D;
-  sgk_build(blob.data(), blob.size(), *plan, nullptr, false, &K);
-  sgd_build(blob.data(), blob.size(), K, &D);
+  SgHostTables T;
+  sg_host_tables(blob.data(), blob.size(), &T);
+  const SgKinHost& K = T.kin;
+  const SgDynHost& D = T.dyn;
   if (!D.ok) { printf("%s refused: %s\n", blob_path, D.err.c_str()); return 1; }
   const int* pi = (const int*)ri.data();
   if (ri.size() < 8) { printf("%s: too short\n", int_path); return 1; }

@@ -11,7 +11,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "sg_solve.h"
+#include "sg_readout_host.h"   // sgv_host_factor_levels, sgv_host_sweep: the kernel's order, stated once
 
 static unsigned long long g_seed = 88172645463325252ull;
 static double rnd() {   // xorshift, U(0, 1)
@@ -31,7 +31,8 @@ static int run(const char* name, const std::vector<int>& dpar, bool expect_ok) {
   }
   if (!expect_ok) { printf("%-28s accepted, but must be refused\n", name); return 1; }
   const SgSolveOff& v = V.o;
-  const std::vector<int> VI(V.ints);   // (its own allocation, exactly the table)
+  V.ints = std::vector<int>(V.ints);   // (a fresh allocation of exactly the table's size: one element past its end is a report)
+  const std::vector<int>& VI = V.ints;
   // L and D of the tree's sparsity, then the packed M = L' D L from the definition
   std::vector<double> Lp(v.nM), M(v.nM, 0.0);
   for (int e = 0; e < v.nM; e++) Lp[e] = VI[v.anc + e] == VI[v.erow + e] ? 0.5 + rnd() : rnd() - 0.5;   // slot 0: D
@@ -49,14 +50,7 @@ static int run(const char* name, const std::vector<int>& dpar, bool expect_ok) {
     }
   std::vector<double> F(M), mdiag(nv);
   for (int i = 0; i < nv; i++) mdiag[i] = M[VI[v.rstart + i]];
-  for (int L = v.nlevel - 1; L >= 0; L--) {
-    const int e0 = VI[v.elstart + L], e1 = VI[v.elstart + L + 1];
-    for (int q = e0; q < e1; q++) F[VI[v.eidx + q]] = sgv_factor_entry(VI.data(), v, F.data(), VI[v.eidx + q]);
-    for (int q = e0; q < e1; q++) {
-      const int e = VI[v.eidx + q];
-      if (VI[v.anc + e] != VI[v.erow + e]) F[e] = sgv_factor_scale(VI.data(), v, F.data(), e);
-    }
-  }
+  sgv_host_factor_levels(V, F.data());
   double worst = 0.0, pivot = INFINITY;
   for (int e = 0; e < v.nM; e++) worst = fmax(worst, fabs(F[e] - Lp[e]));
   for (int i = 0; i < nv; i++) pivot = fmin(pivot, sgv_pivot_ratio(VI.data(), v, F.data(), mdiag.data(), i));
@@ -69,11 +63,7 @@ static int run(const char* name, const std::vector<int>& dpar, bool expect_ok) {
       x[i] += M[VI[v.rstart + i] + t] * want[j];
       if (t) x[j] += M[VI[v.rstart + i] + t] * want[i];
     }
-  for (int L = v.nlevel - 2; L >= 0; L--)
-    for (int s = VI[v.lstart + L]; s < VI[v.lstart + L + 1]; s++) { const int j = VI[v.ldof + s]; x[j] = sgv_up(VI.data(), v, F.data(), x.data(), j); }
-  for (int i = 0; i < nv; i++) x[i] = sgv_scale(VI.data(), v, F.data(), x.data(), i);
-  for (int L = 1; L < v.nlevel; L++)
-    for (int s = VI[v.lstart + L]; s < VI[v.lstart + L + 1]; s++) { const int i = VI[v.ldof + s]; x[i] = sgv_down(VI.data(), v, F.data(), x.data(), i); }
+  sgv_host_sweep(V, nv, F.data(), x.data());
   double werr = 0.0;
   for (int i = 0; i < nv; i++) werr = fmax(werr, fabs(x[i] - want[i]));
   // a point inertia's pairs on random twists: every body's chain, and the world's

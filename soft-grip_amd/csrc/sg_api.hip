@@ -143,13 +143,7 @@ int sg_model_create(const void* blob, size_t nbytes, sg_model** out) {
     return fail(SG_ERR_MODEL, "sg_model_create: " + err + " (two-finger kernels); " + terr + " (tree pipeline)");
   }
   if (!m->has_fast) m->plan = m->tplan;
-  sgk_build(blob, nbytes, m->has_fast ? m->plan : m->tplan, m->has_tree ? &m->tree : nullptr, m->has_fast, &m->kin);
-  sgc_from_blob(blob, nbytes, m->kin, &m->con);
-  sgd_build(blob, nbytes, m->kin, &m->dyn);
-  sgs_build(blob, nbytes, m->kin, m->dyn, &m->smooth);
-  sgp_build(blob, nbytes, m->kin, m->dyn, &m->point);
-  sgv_build(m->kin, m->dyn, m->smooth, &m->solve);
-  sgf_build(blob, nbytes, m->kin, m->con, m->dyn, m->solve, &m->forces);
+  sg_tables_build(blob, nbytes, m->has_fast ? m->plan : m->tplan, m->has_tree ? &m->tree : nullptr, m->has_fast, m);
   m->rounds = (m->plan.h.nelem + 63) / 64;
   if (m->rounds > 4) {
     delete m;

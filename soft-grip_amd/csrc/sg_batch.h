@@ -6,12 +6,7 @@
 #include <string>
 #include <vector>
 
-#include "sg_readout.h"
-#include "sg_dyn.h"
-#include "sg_smooth.h"
-#include "sg_point.h"
-#include "sg_solve.h"
-#include "sg_forces.h"
+#include "sg_tables.h"   // (sg_readout.h, sg_dyn.h, sg_smooth.h, sg_point.h, sg_solve.h, sg_forces.h)
 #include "sg_skin.h"
 #include "sg_shape.h"
 #include "sg_rows_host.h"   // (sg_work.h, sg_plan.h)
@@ -27,7 +22,7 @@ int fail(int code, const std::string& msg);
 // a failed sg_devmem.h call on the buffers of `what`: SG_ERR_NOMEM for the allocation, SG_ERR_HIP for a memset, a copy or the synchronise
 int devmem_fail(bool nomem, const std::string& what);
 
-struct sg_model {
+struct sg_model : SgHostTables {   // (the base: kin, con, dyn, smooth, point, solve, forces -- the read-outs' tables, sg_tables.h)
   SgPlan plan;      // the fast kernels' plan (has_fast), else a copy of tplan: header, elements and sizes serve every entry point
   int rounds;       // ceil(nelem / 64)
   bool has_fast;    // the model is in the two-finger class of sg_plan.h
@@ -36,13 +31,6 @@ struct sg_model {
   SgTreeDev tree;
   size_t tree_lds = 0;       // the tree kernel's LDS block in bytes and an env's slice of its work space in doubles (sgt::lds_bytes,
   long long tree_cws = 0;    // sgt::cws_doubles: each walks lds_carve, so once per model)
-  SgKinHost kin;    // kinematics table of sg_get_poses / sg_render
-  SgConHost con;    // candidate pairs, margins and bounding radii of sg_get_contacts
-  SgDynHost dyn;    // masses, springs, sites and tendons of sg_get_velocities / sg_get_tendons / sg_get_energy
-  SgSmoothHost smooth;   // dampers, actuators, child lists and parent dofs of sg_get_mass_matrix / sg_get_joint_forces / sg_inverse_dynamics
-  SgPointHost point;     // the dof-parent chain's entries and the sites of sg_get_point_motion / sg_get_jacobians / sg_model_sites
-  SgSolveHost solve;     // the packed factor's schedule of sg_solve_mass / sg_forward_smooth / sg_get_point_inertia
-  SgForceHost forces;    // equality records, limited joints, solver parameters and opt's numbers of sg_get_forces
   SgSkinHost skin;  // the composite's skin (sg_skin.h; nvert == 0: none): sg_model_set_skin, drawn by sg_render_ex
 };
 

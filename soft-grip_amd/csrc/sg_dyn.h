@@ -1,7 +1,7 @@
 // sg_dyn.h -- the per-env arithmetic of the velocity, tendon and energy read-outs (sg_get_velocities, sg_get_tendons, sg_get_energy):
 // the dynamics table beside the kinematics table of sg_readout.h, and what one lane does for one body, one tendon segment, one joint.
 // Pure functions of their arguments, compiled for gfx950 (sg_dyn_kernel.h, inside sg_readout.hip) and by g++ for the CPU tests
-// (tests/dyn_ref.py), which drive the same text body by body.
+// (tests/dyn_ref.py), which drive the same text body by body through sgd_host_env (sg_readout_host.h).
 //
 // Definitions.  A body's record is 13 doubles: xpos, xquat (exactly what sgk_body gives), then its twist in world axes: the angular
 // velocity and the linear velocity of the body frame's origin.  The twist is the time derivative of the pose when qpos moves as qvel says
@@ -170,3 +170,15 @@ __host__ __device__ inline double sgd_tendon_spring(const double* DD, const SgDy
   const double k = masked ? kenv : DD[d.tstiff + t], x = L - DD[d.tspring + t];
   return 0.5 * k * x * x;
 }
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// ---- the host twins' walk (sgd_host_env in sg_readout_host.h, sgh_host_env in sg_shape.h): the records [nbody][SGD_REC] of one env, the
+// world at rest, then the bodies by index (parents precede children) -- the kernels' order, stated once ----
+inline void sgd_host_walk(const SgKinHost& K, const SgDynHost& Dn, const double* qpos, const double* qvel, std::vector<double>* rec) {
+  const SgKinOff& o = K.o;
+  rec->assign((size_t)SGD_REC * o.nbody, 0.0);
+  (*rec)[3] = 1.0;
+  for (int i = 1; i < o.nbody; i++)
+    sgd_body(K.dbl.data(), K.ints.data(), o, Dn.ints.data() + Dn.o.jdof, qpos, qvel, i, &(*rec)[SGD_REC * K.ints[o.bpar + i]], &(*rec)[SGD_REC * i]);
+}
+#endif

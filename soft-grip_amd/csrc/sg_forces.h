@@ -17,6 +17,8 @@
 // Sums over the dofs of a row are taken as the wavefront takes them -- lane l adds the columns l, l + 64, .. in ascending order, the 64
 // partial sums meet in a fixed butterfly (sgf_fold) -- so the result depends on nothing but the row.
 #pragma once
+#ifndef SG_FORCES_H   // (beside #pragma once: the host tests build from a patched COPY of this file, which sg_forces_host.h and sg_tables.cpp
+#define SG_FORCES_H   // include first; sg_tables.h's include of the file in this directory must then add nothing)
 #include "sg_solve.h"
 #include "sg_point.h"
 
@@ -419,3 +421,4 @@ __host__ __device__ inline double sgf_cost_change(const double* A, double* f, co
 // the sweep's early exit: the scaled improvement of a whole sweep below the tolerance
 __host__ __device__ inline double sgf_scale(double meaninertia, int nv) { return 1 / (meaninertia * (nv > 1 ? nv : 1)); }
 __host__ __device__ inline bool sgf_sweep_done(double improvement, double scale, double tolerance) { return improvement * scale < tolerance; }
+#endif   // SG_FORCES_H

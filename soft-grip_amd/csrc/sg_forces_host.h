@@ -8,7 +8,8 @@
 #include <cstring>
 #include <vector>
 
-#include "sg_forces.h"
+#include "sg_forces.h"         // (first: a test that builds from a patched copy beside this file gets the copy, sg_forces.h's SG_FORCES_H)
+#include "sg_readout_host.h"   // the smooth walk, the factor and the sweep
 
 struct SgfHostOut {
   int nefc = 0, ncon = 0, iters = 0, warm_kept = 0;
@@ -16,70 +17,6 @@ struct SgfHostOut {
   std::vector<double> cdist, cpos, cframe;
   std::vector<double> J, W, sc, f, qfrc, qacc, qacc_smooth;   // J, W [nefc][nv]; sc [nefc][SGF_SC]
 };
-
-// x <- M^-1 x with the packed factor F: up sweep by levels from the deepest, scaling, down sweep by levels from the roots
-inline void sgf_host_solve(const int* VI, const SgSolveOff& v, int nv, const double* F, double* x) {
-  for (int L = v.nlevel - 2; L >= 0; L--)
-    for (int s = VI[v.lstart + L]; s < VI[v.lstart + L + 1]; s++) { const int j = VI[v.ldof + s]; x[j] = sgv_up(VI, v, F, x, j); }
-  for (int i = 0; i < nv; i++) x[i] = sgv_scale(VI, v, F, x, i);
-  for (int L = 1; L < v.nlevel; L++)
-    for (int s = VI[v.lstart + L]; s < VI[v.lstart + L + 1]; s++) { const int i = VI[v.ldof + s]; x[i] = sgv_down(VI, v, F, x, i); }
-}
-
-// sg_solve_kernel's forward mode: the packed factor F [nM] and qacc_smooth [nv].  false: some D is not finite or not positive
-inline bool sgf_host_smooth(const SgKinHost& K, const SgDynHost& Dn, const SgSmoothHost& Sm, const SgSolveHost& V, const double* qpos, const double* qvel,
-                            const double* act, double kenv, const int* kmask_jnt, const int* kmask_ten, std::vector<double>* Fout, double* qacc_s) {
-  const SgKinOff& o = K.o;
-  const SgDynOff& d = Dn.o;
-  const SgSmoothOff& s = Sm.o;
-  const SgSolveOff& v = V.o;
-  const double *D = K.dbl.data(), *DD = Dn.dbl.data(), *SD = Sm.dbl.data();
-  const int *I = K.ints.data(), *DI = Dn.ints.data(), *SI = Sm.ints.data(), *VI = V.ints.data();
-  const int nv = d.nv;
-  std::vector<double> rec((size_t)SGS_REC * o.nbody), S((size_t)SGS_DOF * nv + 1), ften(2 * (size_t)d.ntendon + 1), &F = *Fout;
-  F.assign(v.nM, 0.0);
-  sgs_world(DD, d, rec.data());
-  for (int i = 1; i < o.nbody; i++) sgs_body(D, I, o, DD, d, DI + d.jdof, qpos, qvel, nullptr, i, &rec[SGS_REC * I[o.bpar + i]], &rec[SGS_REC * i], S.data());
-  for (int i = 1; i < o.nbody; i++) sgs_body_force(DD, d, &rec[SGS_REC * i], i);
-  for (int i = o.nbody - 1; i >= 1; i--) sgs_gather(SI, s, rec.data(), i, SGS_ACC, SGS_REC - SGS_ACC);
-  for (int i = 0; i < nv; i++) S[SGS_DOF * i + 6] = sgs_project(&S[SGS_DOF * i], &rec[SGS_REC * SI[s.dbody + i] + SGS_ACC]);
-  for (int e = 0; e < v.nM; e++) F[e] = sgv_mass_entry(VI, v, SI, s, DD, d, rec.data(), S.data(), e);
-  for (int L = v.nlevel - 1; L >= 0; L--) {
-    const int e0 = VI[v.elstart + L], e1 = VI[v.elstart + L + 1];
-    std::vector<double> val(e1 - e0);
-    for (int q = e0; q < e1; q++) val[q - e0] = sgv_factor_entry(VI, v, F.data(), VI[v.eidx + q]);
-    for (int q = e0; q < e1; q++) F[VI[v.eidx + q]] = val[q - e0];
-    for (int q = e0; q < e1; q++) {
-      const int e = VI[v.eidx + q];
-      if (VI[v.anc + e] != VI[v.erow + e]) F[e] = sgv_factor_scale(VI, v, F.data(), e);
-    }
-  }
-  for (int i = 0; i < nv; i++) {
-    const double Di = F[VI[v.rstart + i]];
-    if (!std::isfinite(Di) || !(Di > 0.0)) return false;
-  }
-  for (int t = 0; t < d.ntendon; t++) {
-    double L = 0, Vl = 0;
-    const int w0 = DI[d.tadr + t], n = sgd_nshare(DI, d, t);
-    for (int k = 0; k < n; k++) {
-      double l1, v1;
-      sgs_wrap(I, o, DD, DI, d, qpos, qvel, rec.data(), w0 + k, &l1, &v1);
-      L += l1; Vl += v1;
-    }
-    sgs_tendon_force(SD, SI, s, DD, d, act, t, L, Vl, kmask_ten[t], kenv, &ften[2 * t]);
-  }
-  if (s.nspatial) {
-    for (int i = 0; i < o.nbody; i++) sgs_body_tendons(DD, DI, d, ften.data(), rec.data(), i);
-    for (int i = o.nbody - 1; i >= 1; i--) sgs_gather(SI, s, rec.data(), i, SGS_ACC, 12);
-  }
-  for (int i = 0; i < nv; i++) {
-    double f[2];
-    sgs_dof_applied(SD, SI, s, I, o, DD, DI, d, qpos, qvel, rec.data(), S.data(), ften.data(), kmask_jnt, kenv, i, f);
-    qacc_s[i] = f[0] + f[1] + 0.0 - S[SGS_DOF * i + 6];
-  }
-  sgf_host_solve(VI, v, nv, F.data(), qacc_s);
-  return true;
-}
 
 // sg_contacts_kernel's flow on the records' poses: the list at cap slots.  Returns ncon, or -1 where a pose leaves the oracle's range
 inline int sgf_host_contacts(const SgKinHost& K, const SgConHost& C, const double* recs, std::vector<int>* geom, std::vector<double>* dist, std::vector<double>* pos,
@@ -121,6 +58,7 @@ inline int sgf_host_contacts(const SgKinHost& K, const SgConHost& C, const doubl
 inline int sgf_host_env(const SgKinHost& K, const SgConHost& C, const SgDynHost& Dn, const SgSmoothHost& Sm, const SgSolveHost& V, const SgForceHost& Fo,
                         const double* qpos, const double* qvel, const double* act, const double* warm, double kenv, const int* kmask_jnt, const int* kmask_ten,
                         SgfHostOut* out) {
+  const SgHostView T(K, Dn, Sm, V);
   const SgKinOff& o = K.o;
   const SgDynOff& d = Dn.o;
   const SgSolveOff& v = V.o;
@@ -131,17 +69,22 @@ inline int sgf_host_env(const SgKinHost& K, const SgConHost& C, const SgDynHost&
     if (!std::isfinite(qpos[i])) return -1;
   for (int i = 0; i < nv; i++)
     if (!std::isfinite(qvel[i]) || !std::isfinite(warm[i])) return -1;
-  // qacc_smooth and the factor
-  std::vector<double> F;
-  out->qacc_smooth.assign(nv, 0.0);
-  if (!sgf_host_smooth(K, Dn, Sm, V, qpos, qvel, act, kenv, kmask_jnt, kmask_ten, &F, out->qacc_smooth.data())) return -1;
+  // sg_solve_kernel's forward mode: the factor and qacc_smooth
+  SgvHostFactor fac;
+  {
+    std::vector<double> rec((size_t)SGS_REC * o.nbody), S((size_t)SGS_DOF * nv + 1), qfrc_smooth(nv + 1);
+    sgs_host_walk(T, qpos, qvel, nullptr, rec.data(), S.data());
+    sgv_host_factor(T, rec.data(), S.data(), &fac);
+    if (fac.bad) return -1;
+    out->qacc_smooth.assign(nv, 0.0);
+    sgv_host_forward_smooth(T, qpos, qvel, act, nullptr, kenv, kmask_jnt, kmask_ten, rec.data(), S.data(), fac.F.data(), qfrc_smooth.data(), out->qacc_smooth.data());
+  }
+  const std::vector<double>& F = fac.F;
   for (int i = 0; i < nv; i++)
     if (!std::isfinite(out->qacc_smooth[i])) return -1;
   // the rows kernel's walk: poses and dof twists, the stamp slots at zero
   std::vector<double> recs((size_t)SGS_REC * o.nbody), S((size_t)SGS_DOF * nv, 0.0), zero(nv + 1, 0.0);
-  sgs_world(Dn.dbl.data(), d, recs.data());
-  for (int i = 1; i < o.nbody; i++)
-    sgs_body(K.dbl.data(), K.ints.data(), o, Dn.dbl.data(), d, Dn.ints.data() + d.jdof, qpos, qvel, nullptr, i, &recs[SGS_REC * K.ints[o.bpar + i]], &recs[SGS_REC * i], S.data());
+  sgs_host_forward(T, qpos, qvel, nullptr, SGS_REC, recs.data(), S.data());
   out->ncon = sgf_host_contacts(K, C, recs.data(), &out->cgeom, &out->cdist, &out->cpos, &out->cframe);
   if (out->ncon < 0) return -1;
   SgfEnv E;
@@ -192,7 +135,7 @@ inline int sgf_host_env(const SgKinHost& K, const SgConHost& C, const SgDynHost&
   // W = M^-1 J'
   for (int i = 0; i < ne; i++) {
     memcpy(W + (size_t)i * nv, J + (size_t)i * nv, sizeof(double) * nv);
-    sgf_host_solve(VI, v, nv, F.data(), W + (size_t)i * nv);
+    sgv_host_sweep(V, nv, F.data(), W + (size_t)i * nv);
   }
   // the solver's prologue: the diagonal blocks, the warm start and its gate
   std::vector<double> a(nv, 0.0);
@@ -252,4 +195,9 @@ inline int sgf_host_env(const SgKinHost& K, const SgConHost& C, const SgDynHost&
     out->qacc[c] = out->qacc_smooth[c] + a[c];
   }
   return 0;
+}
+// ... on a model's tables
+inline int sgf_host_env(const SgHostTables& T, const double* qpos, const double* qvel, const double* act, const double* warm, double kenv, const int* kmask_jnt,
+                        const int* kmask_ten, SgfHostOut* out) {
+  return sgf_host_env(T.kin, T.con, T.dyn, T.smooth, T.solve, T.forces, qpos, qvel, act, warm, kenv, kmask_jnt, kmask_ten, out);
 }

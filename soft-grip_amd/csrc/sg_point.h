@@ -1,7 +1,7 @@
 // sg_point.h -- the per-env, per-point arithmetic of the point read-outs (sg_get_point_motion, sg_get_jacobians): pose, velocity and
 // acceleration of a point fixed on a body, what a gyro and an accelerometer there would read, and the point's Jacobians.  Pure
 // functions of their arguments, compiled for gfx950 (sg_point_kernel.h, inside sg_readout.hip) and by g++ for the CPU tests
-// (tests/point_ref.py), which drive the same text point by point.
+// (tests/point_ref.py), which drive the same text point by point through sgp_host_env (sg_readout_host.h).
 //
 // The forward walk is sg_smooth.h's: sgs_world / sgs_body leave in every body's record its pose (0 .. 6), its twist (7 .. 12: angular
 // velocity, linear velocity of the frame's origin xpos) and its acceleration (13 .. 18: angular, and that of xpos WITH THE WORLD

@@ -1,6 +1,7 @@
 // sg_readout.h -- what the read-outs (sg_get_poses, sg_render, sg_get_contacts, sg_ray) keep per model and per batch: the kinematics table
 // with mj_kinematics' per-body / per-geom routines, the contact read-out's pair table and the skin's device tables.  The builders are
-// defined in sg_tables.cpp (host C++, no HIP); sg_model_create (sg_api.hip) calls them, sg_model and sg_batch (sg_batch.h) hold the results.
+// defined in sg_tables.cpp (host C++, no HIP); sg_tables_build (sg_tables.h) calls them for sg_model_create (sg_api.hip) and for the host
+// twins alike, sg_model and sg_batch (sg_batch.h) hold the results.
 #pragma once
 #if !defined(__HIPCC__) && !defined(__host__)
 #define __host__

@@ -192,11 +192,10 @@ inline int sgh_host_env(const SgKinHost& K, const SgDynHost& Dn, const SgShapeHo
     if (!std::isfinite(qpos[i])) return 1;
   for (int i = 0; i < d.nv; i++)
     if (!std::isfinite(qvel[i])) return 1;
-  const double *D = K.dbl.data(), *DD = Dn.dbl.data(), *HD = T.dbl.data();
-  const int *I = K.ints.data(), *DI = Dn.ints.data(), *HI = T.ints.data();
-  std::vector<double> rec((size_t)SGD_REC * o.nbody, 0.0), V((size_t)SGH_VREC * (h.nvert ? h.nvert : 1), 0.0), sh((size_t)SGH_SHARE * o.nbody, 0.0);
-  rec[3] = 1.0;
-  for (int i = 1; i < o.nbody; i++) sgd_body(D, I, o, DI + d.jdof, qpos, qvel, i, &rec[SGD_REC * I[o.bpar + i]], &rec[SGD_REC * i]);
+  const double *DD = Dn.dbl.data(), *HD = T.dbl.data();
+  const int* HI = T.ints.data();
+  std::vector<double> rec, V((size_t)SGH_VREC * (h.nvert ? h.nvert : 1), 0.0), sh((size_t)SGH_SHARE * o.nbody, 0.0);
+  sgd_host_walk(K, Dn, qpos, qvel, &rec);
   for (int v = 0; v < h.nvert; v++) {
     sgh_vertex(&rec[SGD_REC * HI[h.vbody + v]], HD + h.vpos + 3 * v, &V[SGH_VREC * v]);
     for (int c = 0; c < 3; c++) {

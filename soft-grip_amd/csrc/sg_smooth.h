@@ -1,7 +1,7 @@
 // sg_smooth.h -- the per-env arithmetic of the mass-matrix, joint-force and inverse-dynamics read-outs (sg_get_mass_matrix,
 // sg_get_joint_forces, sg_inverse_dynamics): the smooth table beside the kinematics and dynamics tables, and what one lane does for one
 // body, one dof.  Pure functions of their arguments, compiled for gfx950 (sg_smooth_kernel.h, inside sg_readout.hip) and by g++ for the
-// CPU tests (tests/smooth_ref.py), which drive the same text body by body and dof by dof.
+// CPU tests (tests/smooth_ref.py), which drive the same text body by body and dof by dof through sgs_host_env (sg_readout_host.h).
 //
 // Definitions.  Everything is in world axes, and every moment, every angular momentum and every inertia is taken ABOUT THE WORLD ORIGIN,
 // so a parent gathers its children by plain addition.  A body's record is 29 doubles:

@@ -1,7 +1,7 @@
 // sg_solve.h -- the per-env arithmetic of the read-outs that start with the inverse of the mass matrix (sg_solve_mass, sg_forward_smooth,
 // sg_get_point_inertia): the solve table beside the smooth table, and what one lane does for one packed entry of M, one entry of its
 // factor, one dof of a sweep.  Pure functions of their arguments, compiled for gfx950 (sg_solve_kernel.h, inside sg_readout.hip) and by
-// g++ for the CPU tests (tests/solve_ref.py), which drive the same text entry by entry and dof by dof.
+// g++ for the CPU tests (tests/solve_ref.py), which drive the same text entry by entry and dof by dof through sgv_host_env (sg_readout_host.h).
 //
 // Definitions.  M is sg_smooth.h's: entry (i, j) is nonzero only where dof j is dof i or one of its ancestors on the dof-parent chain
 // (SgSmoothOff::dpar), so M is kept PACKED, row by row: row i holds depth(i) + 1 doubles, slot 0 the diagonal, slot t the entry with

@@ -1,8 +1,9 @@
-// sg_tables.cpp -- the host builders of the read-outs' per-model tables, which sg_model_create (sg_api.hip) calls: kinematics and contact
-// pairs (sg_readout.h), dynamics (sg_dyn.h), smooth (sg_smooth.h), point (sg_point.h), forces (sg_forces.h) and -- per skin, at the first call
-// after sg_model_set_skin -- shape (sg_shape.h); sg_solve.h builds its own.  Plain
-// host C++ without a HIP call: every variant of the library links it, and the host tests compile it with g++ (tests/emu/sg_tables_dump.cpp,
-// tests/test_tables_host.py, scripts/sanitize/host_main.cpp).  Every builder either sets ok or leaves a message in err.
+// sg_tables.cpp -- the host builders of the read-outs' per-model tables: kinematics and contact pairs (sg_readout.h), dynamics (sg_dyn.h),
+// smooth (sg_smooth.h), point (sg_point.h), forces (sg_forces.h) and -- per skin, at the first call after sg_model_set_skin -- shape
+// (sg_shape.h); sg_solve.h builds its own.  sg_tables_build (sg_tables.h) runs them in their one order: sg_model_create (sg_api.hip) calls
+// it, and so does everything on the host that wants a model's tables (sg_readout_host.h).  Plain host C++ without a HIP call: every
+// variant of the library links it, and the host tests and sanitizer programs compile it with g++.  Every builder either sets ok or
+// leaves a message in err.
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>   // (the library's build compiles every source as HIP: the shared headers' __forceinline__)
 #endif
@@ -14,7 +15,8 @@
 
 #include "sg_blob.h"   // sg_blob_find: the one (bounds-checked) reader of the model blob
 #include "sg_point.h"  // (sg_smooth.h, sg_dyn.h, sg_readout.h)
-#include "sg_forces.h" // (sg_solve.h)
+#include "sg_forces.h" // (sg_solve.h; before sg_tables.h: a patched copy beside this file wins, SG_FORCES_H)
+#include "sg_tables.h"
 #include "sg_shape.h"  // (sg_skin.h)
 
 // ---- the builders sg_model_create calls (sg_readout.h) ----
@@ -405,6 +407,16 @@ void sgf_build(const void* blob, size_t nbytes, const SgKinHost& K, const SgConH
   o.eqtype = sg_put(I, eqtype, ne); o.eqobj1 = sg_put(I, eqo1, ne); o.eqobj2 = sg_put(I, eqo2, ne); o.limj = sg_put(I, limj); o.gcondim = sg_put(I, gcondim, ng);
   if (I.empty()) I.push_back(0);
   T->ok = true;
+}
+
+void sg_tables_build(const void* blob, size_t nbytes, const SgPlan& plan, const SgTreeDev* tree, bool fast, SgHostTables* T) {
+  sgk_build(blob, nbytes, plan, tree, fast, &T->kin);
+  sgc_from_blob(blob, nbytes, T->kin, &T->con);
+  sgd_build(blob, nbytes, T->kin, &T->dyn);
+  sgs_build(blob, nbytes, T->kin, T->dyn, &T->smooth);
+  sgp_build(blob, nbytes, T->kin, T->dyn, &T->point);
+  sgv_build(T->kin, T->dyn, T->smooth, &T->solve);
+  sgf_build(blob, nbytes, T->kin, T->con, T->dyn, T->solve, &T->forces);
 }
 
 // the shape table (sg_shape.h): the skin's vertices (body, position) and faces, whether it is closed -- every directed edge (a, b) of

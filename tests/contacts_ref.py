@@ -1,11 +1,10 @@
 """Helpers of the contact read-out tests: the g++ build of csrc/sg_contacts.h run pair by pair as the kernel runs it (broadphase over the
 pair table in order, narrowphase per survivor, the cap), the oracle's list for a given qpos, and the comparison both test files use."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import host_build
 import render_ref as R
 
 TOL = 1e-9          # absolute, on dist / pos / frame: the project's per-step sensor tolerance (both sides are fp64 restatements of one formula)
@@ -77,13 +76,7 @@ extern "C" int contacts_host_stats(int nbody, int ngeom, const int* par, const i
 
 def build_host(tmpdir):
     """compiles sg_contacts.h with g++ into tmpdir -> the ctypes library with contacts_host / contacts_host_npairs"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = os.path.join(tmpdir, "contacts_host.cpp")
-    so = os.path.join(tmpdir, "libcontacts_host.so")
-    with open(src, "w") as f:
-        f.write(HOST_DRIVER)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(root, "soft-grip_amd", "csrc"), "-o", so, src])
-    return C.CDLL(so)
+    return host_build.build(tmpdir, "contacts_host", HOST_DRIVER)
 
 
 def _model_args(m):

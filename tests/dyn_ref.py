@@ -2,16 +2,17 @@
 
   * reference(): a NumPy (fp64) restatement written from the definitions, NOT from the header: Model.kinematics() for the poses, one
     Jacobian column per dof (axis, anchor, the bodies it moves), velocities as column sums, energies from the bodies' masses and inertias;
-  * build_host() / host(): the g++ build of csrc/sg_dyn.h run serially, body by body and wrap by wrap, as the kernel's lanes run it;
+  * build_host() / host(): the g++ build of csrc/sg_dyn.h run serially, body by body and wrap by wrap, as the kernel's lanes run it
+    (sgd_host_env of csrc/sg_readout_host.h, on the tables csrc/sg_tables.cpp builds of the model's blob);
   * the scenes and states every test uses: a few oracle steps into a squeeze, a seeded perturbation of qvel, a stiffness per env;
   * sweep(): contacts_ref's random grippers and poses with velocities and a stiffness per state, for the g++ build and the device alike.
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import readout_host as RH
 import softgrip_amd as sg
 from helpers import ROOT, model_path
 from softgrip_amd.mjcf import JNT_FREE, JNT_SLIDE, WRAP_JOINT
@@ -296,103 +297,15 @@ def length_scale(m, t, qpos, length):
     return float(length[t])
 
 
-# ---- the g++ build of csrc/sg_dyn.h ----
-HOST_DRIVER = r"""
-#include <cstring>
-#include <vector>
-#include "sg_dyn.h"
-// one env, serially, in the kernel's order: bodies by index (parents precede children), then per tendon its shares, then the energy terms
-extern "C" void dyn_host(const int* ko, const double* D, const int* I, const int* dof, const double* DD, const int* DI, const double* qpos,
-                         const double* qvel, double kenv, const int* kmask_jnt, const int* kmask_ten, double* ang, double* lin, double* com_lin,
-                         double* ten_len, double* ten_vel, double* energy, double* poses) {
-  SgKinOff o;
-  SgDynOff d;
-  static_assert(sizeof(SgKinOff) == 22 * sizeof(int) && sizeof(SgDynOff) == 21 * sizeof(int), "offset blocks are plain ints");
-  memcpy(&o, ko, sizeof o);
-  memcpy(&d, dof, sizeof d);
-  std::vector<double> rec((size_t)SGD_REC * o.nbody, 0.0);
-  rec[3] = 1.0;
-  for (int i = 1; i < o.nbody; i++) sgd_body(D, I, o, DI + d.jdof, qpos, qvel, i, &rec[SGD_REC * I[o.bpar + i]], &rec[SGD_REC * i]);
-  double e[4] = {0, 0, 0, 0};
-  for (int i = 0; i < o.nbody; i++) {
-    double xi[3], vc[3];
-    sgd_com(DD, d, &rec[SGD_REC * i], i, xi, vc);
-    for (int c = 0; c < 3; c++) { ang[3 * i + c] = rec[SGD_REC * i + 7 + c]; lin[3 * i + c] = rec[SGD_REC * i + 10 + c]; com_lin[3 * i + c] = vc[c]; }
-    for (int c = 0; c < 7; c++) poses[7 * i + c] = rec[SGD_REC * i + c];
-    if (i > 0) {
-      double g1, k1;
-      sgd_body_energy(DD, d, &rec[SGD_REC * i], i, &g1, &k1);
-      e[0] += g1; e[3] += k1;
-    }
-  }
-  for (int t = 0; t < d.ntendon; t++) {
-    double L = 0, V = 0;
-    const int w0 = DI[d.tadr + t], n = sgd_nshare(DI, d, t);
-    for (int s = 0; s < n; s++) {
-      double l1, v1;
-      sgd_wrap(D, I, o, DD, DI, d, qpos, qvel, rec.data(), w0 + s, &l1, &v1);
-      L += l1; V += v1;
-    }
-    ten_len[t] = L; ten_vel[t] = V;
-    e[2] += sgd_tendon_spring(DD, d, t, L, kmask_ten[t], kenv);
-  }
-  for (int j = 0; j < o.njnt; j++) e[1] += sgd_joint_spring(I, o, DD, d, qpos, j, kmask_jnt[j], kenv);
-  for (int i = 0; i < d.nv; i++) e[3] += 0.5 * DD[d.arm + i] * qvel[i] * qvel[i];
-  memcpy(energy, e, sizeof e);
-}
-"""
-
-
+# ---- the g++ build of csrc/sg_dyn.h: sgd_host_env of csrc/sg_readout_host.h through tests/readout_host.py's shim ----
 def build_host(tmpdir):
-    """compiles sg_dyn.h with g++ into tmpdir -> the ctypes library with dyn_host"""
-    src = os.path.join(str(tmpdir), "dyn_host.cpp")
-    so = os.path.join(str(tmpdir), "libdyn_host.so")
-    with open(src, "w") as f:
-        f.write(HOST_DRIVER)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(ROOT, "soft-grip_amd", "csrc"), "-o", so, src])
-    return C.CDLL(so)
-
-
-def _tables(m):
-    """the kinematics and dynamics tables as the library lays them out (the sections the header's routines read)"""
-    dbl, ints = [], []
-
-    def put(store, arr, dt):
-        at = sum(len(x) for x in store)
-        store.append(np.ascontiguousarray(arr, dtype=dt).reshape(-1))
-        return at
-
-    f, i = np.float64, np.int32
-    qa = np.asarray(m.jnt_qposadr)
-    ko = dict(nbody=m.nbody, ngeom=0, njnt=m.njnt, nq=m.nq, nlevel=0)
-    for name, arr in (("bpos", m.body_pos), ("bquat", m.body_quat), ("jpos", m.jnt_pos), ("jaxis", m.jnt_axis), ("jq0", np.asarray(m.qpos0)[qa])):
-        ko[name] = put(dbl, arr, f)
-    ko["gpos"] = ko["gmat"] = ko["gsize"] = 0
-    for name, arr in (("bpar", m.body_parentid), ("bjadr", m.body_jntadr), ("bjnum", m.body_jntnum), ("jtype", m.jnt_type), ("jqadr", qa)):
-        ko[name] = put(ints, arr, i)
-    ko["gbody"] = ko["gmeta"] = ko["lstart"] = ko["lbody"] = 0
-    order = ["nbody", "ngeom", "njnt", "nq", "nlevel", "bpos", "bquat", "jpos", "jaxis", "jq0", "gpos", "gmat", "gsize", "bpar", "bjadr", "bjnum", "jtype",
-             "jqadr", "gbody", "gmeta", "lstart", "lbody"]
-    K = (np.array([ko[k] for k in order], i), np.concatenate(dbl), np.concatenate(ints))
-    dbl, ints = [], []
-    do = dict(nv=m.nv, nsite=m.nsite, ntendon=m.ntendon, nwrap=len(m.wrap_type))
-    for name, arr in (("bmass", m.body_mass), ("bipos", m.body_ipos), ("bimat", m.body_imat), ("jspring", np.asarray(m.qpos_spring)[qa]),
-                      ("jstiff", m.jnt_stiffness), ("arm", m.dof_armature), ("spos", m.site_pos), ("wprm", m.wrap_prm), ("tstiff", m.tendon_stiffness),
-                      ("tspring", m.tendon_lengthspring), ("grav", m.opt_gravity)):
-        do[name] = put(dbl, arr, f)
-    for name, arr in (("jdof", m.jnt_dofadr), ("sbody", m.site_bodyid), ("tadr", m.tendon_adr), ("tnum", m.tendon_num), ("wtype", m.wrap_type),
-                      ("wobj", m.wrap_objid)):
-        do[name] = put(ints, arr, i)
-    order = ["nv", "nsite", "ntendon", "nwrap", "bmass", "bipos", "bimat", "jspring", "jstiff", "arm", "spos", "wprm", "tstiff", "tspring", "grav", "jdof",
-             "sbody", "tadr", "tnum", "wtype", "wobj"]
-    Dn = (np.array([do[k] for k in order], i), np.concatenate(dbl), np.concatenate(ints + [np.zeros(1, i)]))
-    return K, Dn
+    """the ctypes library with dyn_host"""
+    return RH.build(tmpdir)
 
 
 def host(L, m, scene, qpos, qvel, k, jids=None, tids=None):
     """the host build's outputs for one env at stiffness k (None: no joint or tendon is listed): reference()'s dict, plus poses [nbody, 7].
     jids / tids as in stiffness()"""
-    K, Dn = _tables(m)
     jids, tids = _ids(scene, jids, tids)
     kmj, kmt = np.zeros(m.njnt, np.int32), np.zeros(max(m.ntendon, 1), np.int32)
     if k is not None:
@@ -403,8 +316,8 @@ def host(L, m, scene, qpos, qvel, k, jids=None, tids=None):
                poses=np.zeros((nb, 7)))
     p = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
     q, v = np.ascontiguousarray(qpos, np.float64), np.ascontiguousarray(qvel, np.float64)
-    L.dyn_host(p(K[0]), p(K[1]), p(K[2]), p(Dn[0]), p(Dn[1]), p(Dn[2]), p(q), p(v), C.c_double(0.0 if k is None else k), p(kmj), p(kmt), p(out["ang"]),
-               p(out["lin"]), p(out["com_lin"]), p(out["length"]), p(out["velocity"]), p(out["energy"]), p(out["poses"]))
+    RH.call(L.dyn_host, RH.tables(L, m), p(q), p(v), C.c_double(0.0 if k is None else k), p(kmj), p(kmt), p(out["ang"]), p(out["lin"]), p(out["com_lin"]),
+            p(out["length"]), p(out["velocity"]), p(out["energy"]), p(out["poses"]))
     return out
 
 

@@ -1,8 +1,8 @@
 // sg_tables_dump.cpp -- digests of the read-out tables csrc/sg_tables.cpp and sg_solve.h build of a model (tests/test_tables_host.py holds
 // them against tests/golden/readout_table_digests.json, so an edit of a builder cannot change a table unnoticed).
 //   usage: sg_tables_dump FILE...    FILE = a model blob, or an .xml scene (compiled by sg_mjcf_compile_file in both composite variants)
-// Per input the plans are built as sg_model_create builds them (a scene both plan builders refuse gets a plan that names no geom: the
-// table builders take any blob), then the six tables.  Per table one line: the ok flag, the err text, and
+// Per input the tables are built on the plans as sg_model_create builds them (sg_host_tables_planned: a scene both plan builders refuse
+// gets a plan that names no geom, the table builders take any blob).  Per table -- the forces table is not among them -- one line: the ok flag, the err text, and
 // an FNV-1a hash (64 bits) over the raw bytes of the offset block and of every vector with its element count, and the scalars.  The
 // tables are zero-initialised before the builder fills them (as `new sg_model()` leaves them), so the bytes are deterministic.
 #include <cstdint>
@@ -10,13 +10,10 @@
 #include <cstring>
 #include <fstream>
 #include <iterator>
-#include <memory>
 #include <string>
 
 #include "../../soft-grip_amd/csrc/sg_mjcf.h"
-#include "../../soft-grip_amd/csrc/sg_solve.h"   // (sg_smooth.h, sg_dyn.h, sg_readout.h, sg_plan.h)
-#include "../../soft-grip_amd/csrc/sg_point.h"
-#include "../../soft-grip_amd/csrc/sg_tree.h"    // sgt::lds_bytes: the tree pipeline's size check of sg_model_create
+#include "../../soft-grip_amd/csrc/sg_readout_host.h"   // sg_host_tables_planned
 
 static uint64_t fnv1a(const void* p, size_t n) {
   uint64_t h = 0xcbf29ce484222325ull;
@@ -37,30 +34,16 @@ static void off(const O& o) {
 }
 
 static void dump(const std::string& label, const std::string& blob) {
-  auto plan = std::make_unique<SgPlan>(), tplan = std::make_unique<SgPlan>();
-  auto tree = std::make_unique<SgTreeDev>();
-  memset(tree.get(), 0, sizeof(SgTreeDev));
-  std::string err, terr;
-  const bool has_fast = sg_plan_build(blob.data(), blob.size(), plan.get(), &err);
-  bool has_tree = sg_tree_plan_build(blob.data(), blob.size(), tplan.get(), tree.get(), &terr);
-  if (has_tree && sgt::lds_bytes(*tree, tplan->h.nelem, tplan->h.has_free, tplan->h.nnb) > 160 * 1024) has_tree = false;
+  SgHostTables T{};
+  bool has_fast, has_tree;
+  sg_host_tables_planned(blob.data(), blob.size(), &T, &has_fast, &has_tree);
   printf("%s plans: fast=%d tree=%d\n", label.c_str(), (int)has_fast, (int)has_tree);
-  if (!has_fast && !has_tree) {   // sg_model_create stops here; the builders still take the blob, with a plan that names no geom
-    *tplan = SgPlan{};
-    tplan->h.plane_geom = tplan->h.center_geom = -1;
-  }
-  SgKinHost K{};
-  SgConHost C{};
-  SgDynHost D{};
-  SgSmoothHost S{};
-  SgPointHost P{};
-  SgSolveHost V{};
-  sgk_build(blob.data(), blob.size(), has_fast ? *plan : *tplan, has_tree ? tree.get() : nullptr, has_fast, &K);
-  sgc_from_blob(blob.data(), blob.size(), K, &C);
-  sgd_build(blob.data(), blob.size(), K, &D);
-  sgs_build(blob.data(), blob.size(), K, D, &S);
-  sgp_build(blob.data(), blob.size(), K, D, &P);
-  sgv_build(K, D, S, &V);
+  const SgKinHost& K = T.kin;
+  const SgConHost& C = T.con;
+  const SgDynHost& D = T.dyn;
+  const SgSmoothHost& S = T.smooth;
+  const SgPointHost& P = T.point;
+  const SgSolveHost& V = T.solve;
   head(label, "kin", K); off(K.o); part("dbl", K.dbl); part("ints", K.ints); part("qpos0", K.qpos0); part("rbound", K.rbound);
   printf(" bad_type=%d\n", K.bad_type);
   head(label, "con", C); part("pairs", C.pairs); part("gaux", C.gaux);

@@ -13,15 +13,13 @@
 """
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 
 import contacts_ref as CR
 import dyn_ref as DR
+import host_build
 import softgrip_amd as sg
-from helpers import ROOT
 
 TOL = CR.TOL
 KS = DR.KS
@@ -222,40 +220,29 @@ def dev(got, ref, q):
 
 # ---- the g++ build ----
 HOST_DRIVER = r"""
-#include <memory>
-#include <string>
 #include "sg_forces_host.h"
-struct Model { SgKinHost K; SgConHost C; SgDynHost D; SgSmoothHost S; SgPointHost P; SgSolveHost V; SgForceHost F; };
 extern "C" void* forces_model_new(const void* blob, size_t n, char* err) {
-  auto plan = std::make_unique<SgPlan>();
-  *plan = SgPlan{};
-  plan->h.plane_geom = plan->h.center_geom = -1;
-  Model* m = new Model();
-  sgk_build(blob, n, *plan, nullptr, false, &m->K);
-  sgc_from_blob(blob, n, m->K, &m->C);
-  sgd_build(blob, n, m->K, &m->D);
-  sgs_build(blob, n, m->K, m->D, &m->S);
-  sgv_build(m->K, m->D, m->S, &m->V);
-  sgf_build(blob, n, m->K, m->C, m->D, m->V, &m->F);
-  if (!m->F.ok) { strncpy(err, m->F.err.c_str(), 255); delete m; return nullptr; }
+  SgHostTables* m = new SgHostTables();
+  sg_host_tables(blob, n, m);
+  if (!m->forces.ok) { strncpy(err, m->forces.err.c_str(), 255); delete m; return nullptr; }
   return m;
 }
-extern "C" void forces_model_free(void* h) { delete (Model*)h; }
+extern "C" void forces_model_free(void* h) { delete (SgHostTables*)h; }
 // info: nv, nrows, cap, neq, nlim, njmax, iterations, env bytes (two ints)
 extern "C" void forces_model_info(void* h, long long* info) {
-  const Model* m = (const Model*)h;
-  const SgForceOff& f = m->F.o;
-  info[0] = m->D.o.nv; info[1] = f.nrows; info[2] = f.cap; info[3] = f.neq; info[4] = f.nlim; info[5] = f.njmax; info[6] = f.iterations;
-  info[7] = (long long)sgf_env_bytes(f, m->D.o.nv);
+  const SgHostTables* m = (const SgHostTables*)h;
+  const SgForceOff& f = m->forces.o;
+  info[0] = m->dyn.o.nv; info[1] = f.nrows; info[2] = f.cap; info[3] = f.neq; info[4] = f.nlim; info[5] = f.njmax; info[6] = f.iterations;
+  info[7] = (long long)sgf_env_bytes(f, m->dyn.o.nv);
 }
 // counts: nefc, ncon, iters, warm start kept.  rows [nrows][3]: type, id, aux; caddr [cap]; f [nrows]; J, W [nrows][nv]; sc [nrows][SGF_SC]
 extern "C" int forces_host(void* h, const double* qpos, const double* qvel, const double* act, const double* warm, double kenv, const int* kmj, const int* kmt,
                            int* counts, int* rows, int* caddr, double* f, double* J, double* W, double* sc, double* qfrc, double* qacc, double* qacc_smooth) {
-  const Model* m = (const Model*)h;
+  const SgHostTables* m = (const SgHostTables*)h;
   SgfHostOut o;
-  const int rc = sgf_host_env(m->K, m->C, m->D, m->S, m->V, m->F, qpos, qvel, act, warm, kenv, kmj, kmt, &o);
+  const int rc = sgf_host_env(*m, qpos, qvel, act, warm, kenv, kmj, kmt, &o);
   if (rc) return rc;
-  const int nv = m->D.o.nv, ne = o.nefc;
+  const int nv = m->dyn.o.nv, ne = o.nefc;
   counts[0] = ne; counts[1] = o.ncon; counts[2] = o.iters; counts[3] = o.warm_kept;
   for (int i = 0; i < ne; i++) { rows[3 * i] = o.rtype[i]; rows[3 * i + 1] = o.rid[i]; rows[3 * i + 2] = o.raux[i]; f[i] = o.f[i]; }
   for (int c = 0; c < o.ncon; c++) caddr[c] = o.caddr[c];
@@ -283,25 +270,9 @@ BREAKS = {
 
 
 def build_host(tmpdir, patch=None):
-    """compiles csrc/sg_forces.h, sg_forces_host.h and sg_tables.cpp with g++ from copies in a directory of their own under tmpdir
-    (so that every include of sg_forces.h finds the copy) -> the ctypes library.  patch: a key of BREAKS"""
-    tag = "plain" if patch is None else "break%d" % sorted(BREAKS).index(patch)
-    d = os.path.join(str(tmpdir), tag)
-    os.makedirs(d, exist_ok=True)
-    csrc = os.path.join(ROOT, "soft-grip_amd", "csrc")
-    for name in ("sg_forces.h", "sg_forces_host.h", "sg_tables.cpp"):
-        shutil.copy(os.path.join(csrc, name), os.path.join(d, name))
-    if patch is not None:
-        old, new = BREAKS[patch]
-        text = open(os.path.join(d, "sg_forces.h")).read()
-        assert text.count(old) == 1, (patch, text.count(old))
-        with open(os.path.join(d, "sg_forces.h"), "w") as f:
-            f.write(text.replace(old, new))
-    src, so = os.path.join(d, "forces_host.cpp"), os.path.join(d, "libforces_host.so")
-    with open(src, "w") as f:
-        f.write(HOST_DRIVER)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-I", d, "-I", csrc, "-o", so, src, os.path.join(d, "sg_tables.cpp")])
-    L = C.CDLL(so)
+    """csrc/sg_forces.h through sg_forces_host.h, with sg_tables.cpp -> the ctypes library.  patch: a key of BREAKS, made in sg_forces.h"""
+    L = host_build.build(tmpdir, "forces_host", HOST_DRIVER, copy=("sg_forces.h", "sg_tables.h", "sg_readout_host.h", "sg_forces_host.h", "sg_tables.cpp"),
+                         patch=None if patch is None else ("sg_forces.h",) + BREAKS[patch], tag="plain" if patch is None else "break%d" % sorted(BREAKS).index(patch))
     L.forces_model_new.restype = C.c_void_p
     L.forces_model_new.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p]
     L.forces_model_free.argtypes = [C.c_void_p]

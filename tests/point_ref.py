@@ -8,16 +8,14 @@
   * points(): the point lists the tests use -- the model's sites, every body's centre of mass, the world body, seeded random points
     with unnormalised quaternions;
   * build_host() / host(): the g++ build of csrc/sg_point.h run serially, body by body and point by point, as the kernel's lanes run
-    it; patch= builds a header with one piece of arithmetic broken (the tests that show the tests bite).
+    it (sgp_host_env of csrc/sg_readout_host.h, on the tables csrc/sg_tables.cpp builds of the model's blob); patch= builds a header with one piece of arithmetic broken (the tests that show the tests bite).
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import dyn_ref as DR
-from helpers import ROOT
+import readout_host as RH
 from softgrip_amd.mjcf import JNT_FREE, SENS_ACCELEROMETER, SENS_GYRO, quat_to_mat
 
 MAXBODY, MAXDOF = 672, 1024      # SGP_MAXBODY, SGP_MAXDOF of csrc/sg_point.h
@@ -125,46 +123,7 @@ def deviations(got, ref, qacc, names=NAMES):
     return out
 
 
-# ---- the g++ build of csrc/sg_point.h ----
-HOST_DRIVER = r"""
-#include <cstring>
-#include <vector>
-#include "sg_point.h"
-// one env, serially, in the kernel's order: bodies by index (parents precede children), then the points' motion, then the Jacobians
-// point by point: the chain walk that stamps the dofs, then column by column
-extern "C" void point_host(const int* ko, const double* D, const int* I, const int* dof, const double* DD, const int* DI, const int* po, const int* PI,
-                           const double* qpos, const double* qvel, const double* qacc, int n_pts, const int* pt_body, const double* pt_pos, const double* pt_quat,
-                           double* pos, double* mat, double* vel, double* acc, double* gyro, double* accel, double* jacp, double* jacr) {
-  SgKinOff o;
-  SgDynOff d;
-  SgPointOff pt;
-  static_assert(sizeof(SgKinOff) == 22 * sizeof(int) && sizeof(SgDynOff) == 21 * sizeof(int) && sizeof(SgPointOff) == 2 * sizeof(int), "offset blocks are plain ints");
-  memcpy(&o, ko, sizeof o);
-  memcpy(&d, dof, sizeof d);
-  memcpy(&pt, po, sizeof pt);
-  std::vector<double> rec((size_t)SGP_REC * o.nbody), S((size_t)SGP_DOF * d.nv + 1, 0.0);
-  sgp_world(DD, d, rec.data());
-  for (int i = 1; i < o.nbody; i++) sgs_body(D, I, o, DD, d, DI + d.jdof, qpos, qvel, qacc, i, &rec[SGP_REC * I[o.bpar + i]], &rec[SGP_REC * i], S.data());
-  const size_t nv = d.nv;
-  for (int p = 0; p < n_pts; p++) {
-    sgp_motion(DD, d, &rec[SGP_REC * pt_body[p]], pt_pos + 3 * p, pt_quat ? pt_quat + 4 * p : nullptr, pos + 3 * p, mat + 9 * p, vel + 6 * p, acc + 6 * p,
-               gyro + 3 * p, accel + 3 * p);
-    double P[3];
-    sgp_pos(&rec[SGP_REC * pt_body[p]], pt_pos + 3 * p, P);
-    sgp_mark(PI, pt, PI + pt.dpar, pt_body[p], S.data(), (double)(p + 1));
-    for (int i = 0; i < d.nv; i++) {
-      double jp[3], jr[3];
-      sgp_jac_col(&S[SGP_DOF * i], (double)(p + 1), P, jp, jr);
-      for (int r = 0; r < 3; r++) { jacp[(3 * p + r) * nv + i] = jp[r]; jacr[(3 * p + r) * nv + i] = jr[r]; }
-    }
-  }
-}
-extern "C" int point_limits(int* out) {
-  out[0] = SGP_MAXBODY; out[1] = SGP_MAXDOF; out[2] = SGP_STATIC_LDS; out[3] = SGP_LDS_MAX; out[4] = SGP_REC; out[5] = SGP_DOF;
-  return 6;
-}
-"""
-
+# ---- the g++ build of csrc/sg_point.h: sgp_host_env of csrc/sg_readout_host.h through tests/readout_host.py's shim ----
 # the arithmetic-only breaks (name -> header, text to replace, its replacement); each text occurs exactly once.  The free joint's dof
 # convention lives in the walk sg_point.h takes from sg_smooth.h, so that break is made there
 BREAKS = {
@@ -177,67 +136,19 @@ BREAKS = {
 
 
 def build_host(tmpdir, patch=None):
-    """compiles sg_point.h with g++ into tmpdir -> the ctypes library with point_host.  patch: a key of BREAKS -- sg_point.h and
-    sg_smooth.h are compiled from copies, one of them with that one replacement made"""
-    tmpdir = str(tmpdir)
-    csrc = os.path.join(ROOT, "soft-grip_amd", "csrc")
-    inc = [csrc]
-    if patch is not None:
-        tmpdir = os.path.join(tmpdir, "break_%d" % sorted(BREAKS).index(patch))
-        os.makedirs(tmpdir, exist_ok=True)
-        which, old, new = BREAKS[patch]
-        for name in ("sg_point.h", "sg_smooth.h"):
-            text = open(os.path.join(csrc, name)).read()
-            if name == which:
-                assert text.count(old) == 1, (patch, text.count(old))
-                text = text.replace(old, new)
-            with open(os.path.join(tmpdir, name), "w") as f:
-                f.write(text)
-        inc = [tmpdir, csrc]
-    src = os.path.join(tmpdir, "point_host.cpp")
-    so = os.path.join(tmpdir, "libpoint_host.so")
-    with open(src, "w") as f:
-        f.write(HOST_DRIVER)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC"] + [x for d in inc for x in ("-I", d)] + ["-o", so, src])
-    L = C.CDLL(so)
-    L.point_host.restype = None
-    return L
-
-
-_TABLES = {}
-
-
-def point_table(m):
-    """the point table as the library lays it out (sgp_build), from the model alone: per body the last dof of its nearest
-    ancestor-or-self that has one, per dof the dof before it on the chain"""
-    i = np.int32
-    nv, nb = m.nv, m.nbody
-    own = [[] for _ in range(nb)]
-    for b in range(1, nb):
-        for j in range(m.body_jntadr[b], m.body_jntadr[b] + m.body_jntnum[b]):
-            own[b] += list(range(m.jnt_dofadr[j], m.jnt_dofadr[j] + (6 if m.jnt_type[j] == JNT_FREE else 1)))
-    bdof, dpar = np.full(nb, -1, i), np.full(nv, -1, i)
-    for b in range(1, nb):
-        enter = bdof[m.body_parentid[b]]
-        for d in own[b]:
-            dpar[d], enter = enter, d
-        bdof[b] = enter
-    return np.array([0, nb], i), np.concatenate([bdof, dpar, np.zeros(1, i)])
+    """the ctypes library with point_host.  patch: a key of BREAKS -- its header is compiled from a copy with that one replacement made"""
+    return RH.build(tmpdir, BREAKS, patch)
 
 
 def host(L, m, qpos, qvel, qacc, body, pos, quat=None):
     """the host build's outputs for one env: reference()'s dict.  qacc / quat None: NULL"""
-    if id(m) not in _TABLES:
-        _TABLES[id(m)] = (m,) + DR._tables(m) + (point_table(m),)
-    _, K, Dn, Pt = _TABLES[id(m)]
     P, nv = len(body), m.nv
     out = {n: np.full((P, WIDTH[n]), np.nan) for n in MOTION}
     out.update(jacp=np.full((P, 3, nv), np.nan), jacr=np.full((P, 3, nv), np.nan))
     p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
     c = lambda x, dt=np.float64: None if x is None else np.ascontiguousarray(x, dt)  # noqa: E731
     q, v, a, pb, pp, pq = c(qpos), c(qvel), c(qacc), c(body, np.int32), c(pos), c(quat)
-    L.point_host(p(K[0]), p(K[1]), p(K[2]), p(Dn[0]), p(Dn[1]), p(Dn[2]), p(Pt[0]), p(Pt[1]), p(q), p(v), p(a), C.c_int(P), p(pb), p(pp), p(pq),
-                 *[p(out[n]) for n in NAMES])
+    RH.call(L.point_host, RH.tables(L, m), p(q), p(v), p(a), C.c_int(P), p(pb), p(pp), p(pq), *[p(out[n]) for n in NAMES])
     return out
 
 

@@ -6,11 +6,10 @@ Rules: entry hits only (the smallest t > 0 at which the ray enters the primitive
 planes one-sided, of equal distances the smaller geom id, a hit beyond max_dist (> 0) is a miss; a direction without length or with a
 non-finite component is a miss.  Results: dist (-1 miss), geom (-1), outward unit normal in world axes (zeros)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import host_build
 from render_ref import BOX, CAPSULE, PLANE, SPHERE, categories, geom_poses  # noqa: F401
 from softgrip_amd.mjcf import quat_to_mat
 
@@ -255,13 +254,7 @@ extern "C" void ray_host(int layout, int ng, const double* gx, const double* gm,
 
 def build_host(tmpdir):
     """compiles the driver above with g++ into tmpdir -> the ctypes library (ray_host, skin_vertex_host)"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = os.path.join(tmpdir, "ray_host.cpp")
-    so = os.path.join(tmpdir, "libray_host.so")
-    with open(src, "w") as f:
-        f.write(HOST_DRIVER)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(root, "soft-grip_amd", "csrc"), "-o", so, src])
-    L = C.CDLL(so)
+    L = host_build.build(tmpdir, "ray_host", HOST_DRIVER)
     L.ray_host.restype = None
     L.skin_vertex_host.restype = None
     return L

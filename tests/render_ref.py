@@ -2,11 +2,10 @@
 rules and shading as the header documents, written from those rules and not from the header's code.  Poses come from
 mjcf.Model.kinematics() plus each geom's local pose; categories from the model's structure alone."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import host_build
 from softgrip_amd.mjcf import quat_to_mat
 
 PLANE, SPHERE, CAPSULE, BOX = 0, 2, 3, 6
@@ -245,13 +244,7 @@ extern "C" void render_host(const double* cam, int W, int H, int ng, const doubl
 
 def build_host(tmpdir):
     """compiles sg_render.h with g++ into tmpdir -> ctypes function render_host"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = os.path.join(tmpdir, "render_host.cpp")
-    so = os.path.join(tmpdir, "librender_host.so")
-    with open(src, "w") as f:
-        f.write(HOST_DRIVER)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(root, "soft-grip_amd", "csrc"), "-o", so, src])
-    L = C.CDLL(so)
+    L = host_build.build(tmpdir, "render_host", HOST_DRIVER)
     L.render_host.restype = None
     return L.render_host
 

@@ -22,13 +22,11 @@ Tolerances (dyn_ref's: n eps with two orders of margin).
     A massless subtree's row is the body's own xipos and com velocity (the array bounds) and an exact zero.
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import dyn_ref as DR
-from helpers import ROOT
+import host_build
 
 REL, ARR = DR.REL, DR.ARR
 SHAPE_N = 12
@@ -237,23 +235,19 @@ def skin_of(vert_body, vert_pos, face):
 # ---- the g++ build of csrc/sg_shape.h and the builder in csrc/sg_tables.cpp ----
 HOST_DRIVER = r"""
 #include <cstdio>
-#include <cstring>
-#include <memory>
+#include "sg_readout_host.h"
 #include "sg_shape.h"
 struct Shp {
-  SgKinHost K;
-  SgDynHost D;
+  SgHostTables M;
+  SgKinHost& K = M.kin;
+  SgDynHost& D = M.dyn;
   SgSkinHost S;
   SgShapeHost T;
 };
 extern "C" {
 void* shp_create(const void* blob, size_t n, char* err, int nerr) {
-  auto plan = std::make_unique<SgPlan>();
-  *plan = SgPlan{};
-  plan->h.plane_geom = plan->h.center_geom = -1;
   Shp* h = new Shp;
-  sgk_build(blob, n, *plan, nullptr, false, &h->K);
-  sgd_build(blob, n, h->K, &h->D);
+  sg_host_tables(blob, n, &h->M);
   sgh_build(h->K, h->D, h->S, &h->T);
   if (!h->T.ok) { snprintf(err, nerr, "%s", h->T.err.c_str()); delete h; return nullptr; }
   return h;
@@ -312,13 +306,7 @@ int shp_limits(int* out) { out[0] = SGH_LDS_MAX; out[1] = SGH_STATIC_LDS; out[2]
 
 def build_host(tmpdir):
     """compiles the driver above with csrc/sg_tables.cpp by g++ into tmpdir -> the ctypes library"""
-    src, so = os.path.join(str(tmpdir), "shape_host.cpp"), os.path.join(str(tmpdir), "libshape_host.so")
-    with open(src, "w") as f:
-        f.write(HOST_DRIVER)
-    csrc = os.path.join(ROOT, "soft-grip_amd", "csrc")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-I", csrc, "-I", os.path.join(ROOT, "include"), "-o", so, src,
-                           os.path.join(csrc, "sg_tables.cpp")])
-    L = C.CDLL(so)
+    L = host_build.build(tmpdir, "shape_host", HOST_DRIVER, sources=("sg_tables.cpp",))
     L.shp_create.restype = C.c_void_p
     L.shp_create.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_int]
     L.shp_destroy.argtypes = [C.c_void_p]

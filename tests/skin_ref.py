@@ -13,11 +13,10 @@ geoms through tests/render_ref.py's primitives, the skin's triangles from the ru
 compare() is render_ref.compare with the one extension for a surface that can fold over itself: the reference also returns the face
 index, and a pixel counts as silhouette when a 4-neighbour has another segid or a face that shares no vertex with its own."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import host_build
 import render_ref as R
 
 
@@ -259,13 +258,7 @@ extern "C" void mesh_host(int n, const float* d, int nvert, const float* verts, 
 
 def build_host(tmpdir):
     """compiles the driver above (sg_render.h, sg_skin.h) with g++ into tmpdir -> the ctypes library"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = os.path.join(tmpdir, "skin_host.cpp")
-    so = os.path.join(tmpdir, "libskin_host.so")
-    with open(src, "w") as f:
-        f.write(HOST_DRIVER)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(root, "soft-grip_amd", "csrc"), "-o", so, src])
-    L = C.CDLL(so)
+    L = host_build.build(tmpdir, "skin_host", HOST_DRIVER)
     for fn in (L.skin_render_host, L.tri_host, L.mesh_host):
         fn.restype = None
     return L

@@ -6,17 +6,15 @@ sg_inverse_dynamics; csrc/sg_smooth.h), on top of tests/dyn_ref.py:
     actuator apply the tendons' scalar forces through tendon Jacobians built from the same columns; bias differentiates the columns in
     time analytically (d/dt u = W x u, d/dt (x - anchor) = v_x - v_anchor) and projects every body's m a_com and I al + w x I w through
     its Jacobians -- no recursion over parents anywhere, where the header has two; inverse = M qacc + bias - passive;
-  * build_host() / host(): the g++ build of csrc/sg_smooth.h run serially, body by body and dof by dof, as the kernel's lanes run it;
-    patch= builds a header with one piece of arithmetic broken (the tests that show the tests bite).
+  * build_host() / host(): the g++ build of csrc/sg_smooth.h run serially, body by body and dof by dof, as the kernel's lanes run it
+    (sgs_host_env of csrc/sg_readout_host.h, on the tables csrc/sg_tables.cpp builds of the model's blob); patch= builds a header with one piece of arithmetic broken (the tests that show the tests bite).
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import dyn_ref as DR
-from helpers import ROOT
+import readout_host as RH
 from softgrip_amd.mjcf import JNT_FREE, WRAP_JOINT
 
 MAXBODY, MAXDOF, MAXTENDON = 449, 1024, 128      # SGS_MAXBODY, SGS_MAXDOF, SGS_MAXTENDON of csrc/sg_smooth.h
@@ -140,135 +138,25 @@ def sweep_refs(gripper, tmpdir, offset=False):
     return _SWEEP_REFS[gripper, offset]
 
 
-# ---- the g++ build of csrc/sg_smooth.h ----
-HOST_DRIVER = r"""
-#include <cstring>
-#include <vector>
-#include "sg_smooth.h"
-// one env, serially, in the kernel's order: bodies by index (parents precede children) out, by descending index back, then the dofs;
-// then the tendons, the bodies' tendon pulls, the dofs again.  The walk runs once at qacc = 0 and, where qacc is given, once more with it
-static void walk(const SgKinOff& o, const double* D, const int* I, const SgDynOff& d, const double* DD, const int* DI, const SgSmoothOff& s, const double* SD,
-                 const int* SI, const double* qpos, const double* qvel, const double* qacc, std::vector<double>& rec, std::vector<double>& S) {
-  sgs_world(DD, d, rec.data());
-  for (int i = 1; i < o.nbody; i++) sgs_body(D, I, o, DD, d, DI + d.jdof, qpos, qvel, qacc, i, &rec[SGS_REC * I[o.bpar + i]], &rec[SGS_REC * i], S.data());
-  for (int i = 1; i < o.nbody; i++) sgs_body_force(DD, d, &rec[SGS_REC * i], i);
-  for (int i = o.nbody - 1; i >= 1; i--) sgs_gather(SI, s, rec.data(), i, SGS_ACC, SGS_REC - SGS_ACC);
-  for (int i = 0; i < d.nv; i++) S[SGS_DOF * i + 6] = sgs_project(&S[SGS_DOF * i], &rec[SGS_REC * SI[s.dbody + i] + SGS_ACC]);
-}
-extern "C" void smooth_host(const int* ko, const double* D, const int* I, const int* dof, const double* DD, const int* DI, const int* so, const double* SD,
-                            const int* SI, const double* qpos, const double* qvel, const double* act, const double* qacc, double kenv, const int* kmask_jnt,
-                            const int* kmask_ten, double* M, double* bias, double* passive, double* actuator, double* inverse) {
-  SgKinOff o;
-  SgDynOff d;
-  SgSmoothOff s;
-  static_assert(sizeof(SgKinOff) == 22 * sizeof(int) && sizeof(SgDynOff) == 21 * sizeof(int) && sizeof(SgSmoothOff) == 12 * sizeof(int), "offset blocks are plain ints");
-  memcpy(&o, ko, sizeof o);
-  memcpy(&d, dof, sizeof d);
-  memcpy(&s, so, sizeof s);
-  std::vector<double> rec((size_t)SGS_REC * o.nbody), S((size_t)SGS_DOF * d.nv + 1), ften(2 * (size_t)d.ntendon + 1), tau(d.nv + 1);
-  if (qacc) {
-    walk(o, D, I, d, DD, DI, s, SD, SI, qpos, qvel, qacc, rec, S);
-    for (int i = 0; i < d.nv; i++) tau[i] = S[SGS_DOF * i + 6];
-  }
-  walk(o, D, I, d, DD, DI, s, SD, SI, qpos, qvel, nullptr, rec, S);
-  for (int i = 0; i < d.nv; i++) bias[i] = S[SGS_DOF * i + 6];
-  for (int i = 0; i < d.nv; i++) sgs_mass_row(SI, s, DD, d, rec.data(), S.data(), i, M);
-  for (int t = 0; t < d.ntendon; t++) {
-    double L = 0, V = 0;
-    const int w0 = DI[d.tadr + t], n = sgd_nshare(DI, d, t);
-    for (int k = 0; k < n; k++) {
-      double l1, v1;
-      sgs_wrap(I, o, DD, DI, d, qpos, qvel, rec.data(), w0 + k, &l1, &v1);
-      L += l1; V += v1;
-    }
-    sgs_tendon_force(SD, SI, s, DD, d, act, t, L, V, kmask_ten[t], kenv, &ften[2 * t]);
-  }
-  if (s.nspatial) {
-    for (int i = 0; i < o.nbody; i++) sgs_body_tendons(DD, DI, d, ften.data(), rec.data(), i);
-    for (int i = o.nbody - 1; i >= 1; i--) sgs_gather(SI, s, rec.data(), i, SGS_ACC, 12);
-  }
-  for (int i = 0; i < d.nv; i++) {
-    double f[2];
-    sgs_dof_applied(SD, SI, s, I, o, DD, DI, d, qpos, qvel, rec.data(), S.data(), ften.data(), kmask_jnt, kenv, i, f);
-    passive[i] = f[0]; actuator[i] = f[1];
-    if (qacc) inverse[i] = tau[i] + DD[d.arm + i] * qacc[i] - f[0];
-  }
-}
-extern "C" int smooth_limits(int* out) {
-  out[0] = SGS_MAXBODY; out[1] = SGS_MAXDOF; out[2] = SGS_MAXTENDON; out[3] = SGS_STATIC_LDS; out[4] = SGS_LDS_MAX; out[5] = SGS_REC; out[6] = SGS_DOF;
-  return 7;
-}
-"""
-
-# the four arithmetic-only breaks of csrc/sg_smooth.h (name -> text to replace, its replacement); each text occurs exactly once
+# ---- the g++ build of csrc/sg_smooth.h: sgs_host_env of csrc/sg_readout_host.h through tests/readout_host.py's shim ----
+# the four arithmetic-only breaks of csrc/sg_smooth.h (name -> header, text to replace, its replacement); each text occurs exactly once
 BREAKS = {
-    "gyroscopic term dropped": ("nl[k] = Ia[k] + t1[k];", "nl[k] = Ia[k];"),
-    "free angular columns in world axes": ("const double u[3] = {R[k], R[3 + k], R[6 + k]};", "const double u[3] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0};"),
-    "tendon damper sign flipped": ("- SD[s.tdamp + t] * Ld;", "+ SD[s.tdamp + t] * Ld;"),
-    "armature left out of M": ("if (c == i) val += DD[d.arm + i];", ""),
+    "gyroscopic term dropped": ("sg_smooth.h", "nl[k] = Ia[k] + t1[k];", "nl[k] = Ia[k];"),
+    "free angular columns in world axes": ("sg_smooth.h", "const double u[3] = {R[k], R[3 + k], R[6 + k]};",
+                                           "const double u[3] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0};"),
+    "tendon damper sign flipped": ("sg_smooth.h", "- SD[s.tdamp + t] * Ld;", "+ SD[s.tdamp + t] * Ld;"),
+    "armature left out of M": ("sg_smooth.h", "if (c == i) val += DD[d.arm + i];", ""),
 }
 
 
 def build_host(tmpdir, patch=None):
-    """compiles sg_smooth.h with g++ into tmpdir -> the ctypes library with smooth_host.  patch: a key of BREAKS -- the header is
-    compiled from a copy with that one replacement made"""
-    tmpdir = str(tmpdir)
-    tag = "" if patch is None else "_%d" % sorted(BREAKS).index(patch)
-    src = os.path.join(tmpdir, "smooth_host%s.cpp" % tag)
-    so = os.path.join(tmpdir, "libsmooth_host%s.so" % tag)
-    csrc = os.path.join(ROOT, "soft-grip_amd", "csrc")
-    driver = HOST_DRIVER
-    if patch is not None:
-        old, new = BREAKS[patch]
-        text = open(os.path.join(csrc, "sg_smooth.h")).read()
-        assert text.count(old) == 1, (patch, text.count(old))
-        with open(os.path.join(tmpdir, "sg_smooth%s.h" % tag), "w") as f:
-            f.write(text.replace(old, new))
-        driver = driver.replace('#include "sg_smooth.h"', '#include "sg_smooth%s.h"' % tag)
-    with open(src, "w") as f:
-        f.write(driver)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", tmpdir, "-I", csrc, "-o", so, src])
-    L = C.CDLL(so)
-    L.smooth_host.restype = None
-    return L
-
-
-_TABLES = {}
-
-
-def smooth_table(m):
-    """the smooth table as the library lays it out (sgs_build), from the model alone"""
-    f, i = np.float64, np.int32
-    nv, nb = m.nv, m.nbody
-    dbody, dpar, last = np.full(nv, -1, i), np.full(nv, -1, i), np.full(nb, -1, i)
-    for b in range(1, nb):
-        last[b] = last[m.body_parentid[b]]
-        for j in range(m.body_jntadr[b], m.body_jntadr[b] + m.body_jntnum[b]):
-            for e in range(6 if m.jnt_type[j] == JNT_FREE else 1):
-                d = m.jnt_dofadr[j] + e
-                dbody[d], dpar[d], last[b] = b, last[b], d
-    par = np.asarray(m.body_parentid)
-    child = [np.flatnonzero(par[1:] == b) + 1 for b in range(nb)]
-    cstart = np.concatenate([[0], np.cumsum([len(c) for c in child])])
-    nspatial = sum(int(m.wrap_type[m.tendon_adr[t]] != WRAP_JOINT) for t in range(m.ntendon))
-    dbl = [np.asarray(m.dof_damping, f), np.asarray(m.tendon_damping, f), np.asarray(m.actuator_gain, f), np.asarray(m.actuator_bias, f).reshape(-1),
-           np.asarray(m.actuator_gear, f)]
-    ints = [dbody, dpar, np.asarray(m.actuator_trnid, i), cstart.astype(i), np.concatenate(child + [np.zeros(0, int)]).astype(i)]
-    off = [m.nu, nspatial]
-    for store in (dbl, ints):
-        at = 0
-        for arr in store:
-            off.append(at)
-            at += len(arr)
-    return np.array(off, i), np.concatenate(dbl + [np.zeros(1, f)]), np.concatenate(ints + [np.zeros(1, i)])
+    """the ctypes library with smooth_host.  patch: a key of BREAKS -- the header is compiled from a copy with that one replacement made"""
+    return RH.build(tmpdir, BREAKS, patch)
 
 
 def host(L, m, scene, qpos, qvel, k, jids=None, tids=None, act=None, qacc=None):
     """the host build's outputs for one env at stiffness k (None: no joint or tendon is listed): dict of M, bias, passive, actuator and,
     with qacc, inverse.  jids / tids as in dyn_ref.stiffness()"""
-    if id(m) not in _TABLES:
-        _TABLES[id(m)] = (m,) + DR._tables(m) + (smooth_table(m),)
-    _, K, Dn, Sm = _TABLES[id(m)]
     jids, tids = DR._ids(scene, jids, tids)
     kmj, kmt = np.zeros(m.njnt, np.int32), np.zeros(max(m.ntendon, 1), np.int32)
     if k is not None:
@@ -281,8 +169,8 @@ def host(L, m, scene, qpos, qvel, k, jids=None, tids=None, act=None, qacc=None):
     p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
     c = lambda x: None if x is None else np.ascontiguousarray(x, np.float64)  # noqa: E731
     q, v, a, acc = c(qpos), c(qvel), c(np.zeros(max(m.nu, 1)) if act is None else act), c(qacc)
-    L.smooth_host(p(K[0]), p(K[1]), p(K[2]), p(Dn[0]), p(Dn[1]), p(Dn[2]), p(Sm[0]), p(Sm[1]), p(Sm[2]), p(q), p(v), p(a), p(acc),
-                  C.c_double(0.0 if k is None else k), p(kmj), p(kmt), p(out["M"]), p(out["bias"]), p(out["passive"]), p(out["actuator"]), p(out.get("inverse")))
+    RH.call(L.smooth_host, RH.tables(L, m), p(q), p(v), p(a), p(acc), C.c_double(0.0 if k is None else k), p(kmj), p(kmt), p(out["M"]), p(out["bias"]),
+            p(out["passive"]), p(out["actuator"]), p(out.get("inverse")))
     return out
 
 

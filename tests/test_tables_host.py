@@ -5,8 +5,8 @@ without a GPU.
     its err text and a hash of the offset block, of every vector and of the scalars.  tests/golden/readout_table_digests.json holds that
     output for the committed models/*.sgmodel and every tests/data/*.xml the MJCF compiler accepts, in both composite variants; the
     comparison is exact.  The file was recorded when the builders had just moved out of sg_readout.hip, unedited.
-  * restatements: a ctypes build of sg_tables.cpp + sg_plan.cpp against the layouts tests/dyn_ref.py, smooth_ref.py and point_ref.py
-    restate in Python from the model alone -- offset by offset, element by element, exactly.
+  * restatements: a ctypes build of sg_tables.cpp + sg_plan.cpp against the layouts tests/tables_ref.py restates in Python from the
+    model alone -- offset by offset, element by element, exactly.
   * refusals: blobs with one array removed or one address moved reach the builders, which answer with their message.
   * scripts/sanitize/host_main.cpp --mutate under ASan + UBSan: every damaged copy of a model through the real builders.
 
@@ -64,33 +64,13 @@ def test_tables_match_the_pinned_digests():
 
 # ---- 2. the ctypes build of the builders ----
 HOST_DRIVER = r"""
-#include <cstring>
-#include <memory>
-#include <string>
-#include "sg_blob.h"
-#include "sg_solve.h"
-#include "sg_point.h"
-struct Tables {
-  SgKinHost kin{}; SgConHost con{}; SgDynHost dyn{}; SgSmoothHost smooth{}; SgPointHost point{}; SgSolveHost solve{};
-};
-// the plans as sg_model_create builds them (a blob both refuse: a plan that names no geom), then the six tables
+#include "sg_readout_host.h"
+typedef SgHostTables Tables;
+// the tables on the plans as sg_model_create builds them (a blob both refuse: a plan that names no geom)
 extern "C" Tables* tables_new(const void* blob, size_t n) {
-  auto plan = std::make_unique<SgPlan>(), tplan = std::make_unique<SgPlan>();
-  auto tree = std::make_unique<SgTreeDev>();
-  memset(tree.get(), 0, sizeof(SgTreeDev));
-  std::string err, terr;
-  const bool fast = sg_plan_build(blob, n, plan.get(), &err), has_tree = sg_tree_plan_build(blob, n, tplan.get(), tree.get(), &terr);
-  if (!fast && !has_tree) {
-    *tplan = SgPlan{};
-    tplan->h.plane_geom = tplan->h.center_geom = -1;
-  }
   Tables* T = new Tables();
-  sgk_build(blob, n, fast ? *plan : *tplan, has_tree ? tree.get() : nullptr, fast, &T->kin);
-  sgc_from_blob(blob, n, T->kin, &T->con);
-  sgd_build(blob, n, T->kin, &T->dyn);
-  sgs_build(blob, n, T->kin, T->dyn, &T->smooth);
-  sgp_build(blob, n, T->kin, T->dyn, &T->point);
-  sgv_build(T->kin, T->dyn, T->smooth, &T->solve);
+  bool fast, tree;
+  sg_host_tables_planned(blob, n, T, &fast, &tree);
   return T;
 }
 extern "C" void tables_free(Tables* T) { delete T; }
@@ -114,13 +94,8 @@ extern "C" long long tables_part(const Tables* T, int t, int part, void* out) {
 
 @pytest.fixture(scope="module")
 def hostlib(tmp_path_factory):
-    tmp = str(tmp_path_factory.mktemp("tables_host"))
-    src, so = os.path.join(tmp, "tables_host.cpp"), os.path.join(tmp, "libtables_host.so")
-    with open(src, "w") as f:
-        f.write(HOST_DRIVER)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-I", CSRC, "-o", so, src, os.path.join(CSRC, "sg_tables.cpp"),
-                           os.path.join(CSRC, "sg_plan.cpp")])
-    L = C.CDLL(so)
+    import host_build
+    L = host_build.build(tmp_path_factory.mktemp("tables_host"), "tables_host", HOST_DRIVER, opt="-O1", sources=("sg_tables.cpp", "sg_plan.cpp"))
     L.tables_new.restype = C.c_void_p
     L.tables_new.argtypes = [C.c_char_p, C.c_size_t]
     L.tables_free.argtypes = [C.c_void_p]
@@ -174,12 +149,10 @@ def _same_padded(got, ref, what):
 
 
 def test_builders_match_the_python_restatements(hostlib, models):
-    """the kin sections dyn_ref._tables restates (counts, the body and joint sections of both arrays, which come first), the whole dyn
-    table, smooth_ref.smooth_table and point_ref.point_table, exactly.  free_body.xml and the gripper on a free joint carry
-    jnt_qposadr / jnt_dofadr.  The geom sections of kin, which _tables leaves at zero, are not compared: the digests hold them"""
-    import dyn_ref as DR
-    import point_ref as PR
-    import smooth_ref as SR
+    """the kin sections tables_ref.kin_dyn_tables restates (counts, the body and joint sections of both arrays, which come first), the
+    whole dyn table, tables_ref.smooth_table and tables_ref.point_table, exactly.  free_body.xml and the gripper on a free joint carry
+    jnt_qposadr / jnt_dofadr.  The geom sections of kin, which kin_dyn_tables leaves at zero, are not compared: the digests hold them"""
+    import tables_ref as TR
     kin_names = ["nbody", "ngeom", "njnt", "nq", "nlevel", "bpos", "bquat", "jpos", "jaxis", "jq0", "gpos", "gmat", "gsize", "bpar", "bjadr", "bjnum", "jtype",
                  "jqadr", "gbody", "gmeta", "lstart", "lbody"]
     free = 0
@@ -188,7 +161,7 @@ def test_builders_match_the_python_restatements(hostlib, models):
         got = build(hostlib, m.to_blob())
         for t in ("kin", "dyn", "smooth", "point"):
             assert got[t]["ok"] and not got[t]["err"], (name, t, got[t]["err"])
-        (ko, kd, ki), (do, dd, di) = DR._tables(m)
+        (ko, kd, ki), (do, dd, di) = TR.kin_dyn_tables(m)
         o, ro = dict(zip(kin_names, got["kin"]["off"])), dict(zip(kin_names, ko))
         assert len(got["kin"]["off"]) == len(kin_names)
         for k in ("nbody", "njnt", "nq", "bpos", "bquat", "jpos", "jaxis", "jq0", "bpar", "bjadr", "bjnum", "jtype", "jqadr"):
@@ -198,11 +171,11 @@ def test_builders_match_the_python_restatements(hostlib, models):
         assert got["dyn"]["off"].tobytes() == do.tobytes(), (name, got["dyn"]["off"], do)
         _same_padded(got["dyn"]["dbl"], dd, (name, "dyn dbl"))
         _same_padded(got["dyn"]["ints"], di, (name, "dyn ints"))
-        so, sd, si = SR.smooth_table(m)
+        so, sd, si = TR.smooth_table(m)
         assert got["smooth"]["off"].tobytes() == so.tobytes(), (name, got["smooth"]["off"], so)
         _same_padded(got["smooth"]["dbl"], sd, (name, "smooth dbl"))
         _same_padded(got["smooth"]["ints"], si, (name, "smooth ints"))
-        po, pi = PR.point_table(m)
+        po, pi = TR.point_table(m)
         assert got["point"]["off"].tobytes() == po.tobytes(), (name, got["point"]["off"], po)
         _same_padded(got["point"]["ints"], pi, (name, "point ints"))
     assert free >= 2
